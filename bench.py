@@ -18,6 +18,12 @@ weights, CrossEntropy + Adam (ref.py:703-704).  Inside the timed region every st
 renders its batch in HBM (the trainer's own device input pipeline, ``synth_tiles``
 kernel, distinct sample indices per rank and step), then runs the full forward +
 backward + gradient all-reduce + optimizer step.
+
+A plain run does only what the headline figure needs: set up, warm up (with the untimed
+schedule / bucket calibration that picks the timed configuration), time the K steps, print
+the line.  ``--dump-outputs DIR`` also writes the state the last timed step produced as
+``.npy`` files (same arguments, same inputs: two builds compare output for output).
+Anything measured beyond the headline belongs behind ``--full``.
 """
 from __future__ import annotations
 
@@ -97,6 +103,16 @@ def _parse():
     ap.add_argument("--ab-rounds", type=int, default=4)
     ap.add_argument("--heartbeat", type=float, default=0.0,
                     help="seconds between 'alive' lines on stderr (long first-step autotuning)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step left with its "
+                         "caller as DIR/<name>.npy (see _dump_outputs); same arguments = same "
+                         "inputs, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure.  A plain run "
+                         "sets up, warms up, times --steps steps and prints the result line; "
+                         "the passes that take runs of their own (--bucket-sweep, --ab) are "
+                         "requested by their own options and there is no other one today, so "
+                         "--full adds nothing yet — further measurements belong behind it")
     a = ap.parse_args()
     if a.batch is None:
         a.batch = 384 if (a.tile == 256 and a.dims == 2) else 128
@@ -146,6 +162,39 @@ def _baseline(args):
          128: b.get("batch_128_images_per_sec"), 256: b.get("batch_256_images_per_sec"),
          384: b.get("batch_384_images_per_sec")}.get(args.batch)
     return float(v) if v else None
+
+
+DUMP_MAX_BYTES = {"params": 48 << 20, "buffers": 8 << 20, "meter": 1 << 10}   # < 64 MB in all
+
+
+def _dump_outputs(out_dir, tr) -> None:
+    """``train_step`` returns nothing: what its caller receives is the trainer's state after
+    the step.  Written as float32 / float64 ``.npy`` files:
+
+    * ``params``   every trainable parameter (the fp32 master weights), flattened in
+      ``model.parameters()`` order and logical (NCHW / OIHW) element order;
+    * ``buffers``  the module buffers (BatchNorm running statistics), same convention;
+    * ``meter``    float64 [sum of micro-batch losses, correct pixels, pixels, micro-batches]
+      accumulated on this rank since the start of the run.
+
+    An array above its DUMP_MAX_BYTES is written as a fixed sample of its elements (indices drawn
+    once from seed 0, sorted), so two runs of the same configuration sample alike."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, ts, dtype):
+        ts = [t.detach().to(dtype).reshape(-1) for t in ts]
+        a = (torch.cat(ts) if ts else torch.zeros(0, dtype=dtype)).cpu().numpy()
+        keep = DUMP_MAX_BYTES[name] // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    with torch.no_grad():
+        save("params", tr.model.parameters(), torch.float32)
+        save("buffers", tr.model.buffers(), torch.float32)
+        save("meter", [tr.meter.buf], torch.float64)
 
 
 def main():
@@ -274,6 +323,8 @@ def main():
     first = args.warmup + 100
     tr.ms_host_s = 0.0
     dt = timed(args.steps, first)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, tr)       # (before any later pass steps again)
     phases = tr.phases.read() if tr.phases is not None else {}
     ms_host = getattr(tr, "ms_host_s", 0.0)
     mstats = torch.cuda.memory_stats(device) if dev == "cuda" else {}
@@ -449,6 +500,7 @@ def main():
                        "bucket_sweep": sweep or None,
                        "ab": ab,
                        "engine_set": args.engine_set or None,
+                       "full": bool(args.full),
                        "input_prefetch": pf is not None,
                        "alloc_retries": mstats.get("num_alloc_retries"),
                        "side_lag_waits": (getattr(tr.model._engine, "lag_waits", None)

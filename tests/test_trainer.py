@@ -105,6 +105,45 @@ def test_bench_cpu_json_contract():
     assert rec["n_gpus"] == 1 and rec["steps"] == 1 and rec["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the state the last timed step produced as float .npy
+    arrays, and two runs with the same arguments (one of them ``--full``) start from the same
+    weights and see the same batches: the dumps agree."""
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--impl", "torch",
+                              "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "64",
+                              "--width-divisor", "16", "--dump-outputs", str(tmp_path / name)]
+                             + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads(out.stdout.strip().splitlines()[-1])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["config"]["full"] is bool(extra)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["buffers.npy", "meter.npy", "params.npy"]
+        d = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert sum(a.nbytes for a in d.values()) <= 64 << 20
+        assert d["params"].dtype == np.float32 and d["meter"].dtype == np.float64
+        assert all(np.isfinite(a).all() for a in d.values())
+        dumps.append(d)
+    a, b = dumps
+    from ddlpc.config import ModelConfig
+    from ddlpc.models import UNet
+    n = sum(p.numel() for p in UNet.from_config(ModelConfig(width_divisor=16)).parameters())
+    assert a["params"].size == n
+    # 3 steps x 1 micro-batch of 2 x 64 x 64 pixels went through the meter
+    assert a["meter"][2] == 3 * 2 * 64 * 64 and a["meter"][3] == 3
+    # same inputs, same code: equal up to the summation order of threaded fp32 reductions
+    # (2^-24 relative per operation, a few thousand operations deep, three Adam steps)
+    for k in a:
+        assert a[k].shape == b[k].shape
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-3, atol=1e-4)
+    assert np.abs(a["params"]).max() > 0
+
+
 def test_bench_torchrun_two_ranks_gloo():
     """The driver's N>1 launch line (torch.distributed.run, 127.0.0.1) on CPU/gloo: one JSON
     line from rank 0 with the whole-job aggregate, and the run's self-validation: the
