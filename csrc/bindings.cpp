@@ -1562,6 +1562,93 @@ std::vector<at::Tensor> tile_gather(const at::Tensor& src, const at::Tensor& lab
   return {x, y};
 }
 
+// ------------------------------------------------------------------------ scene prediction
+static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
+  CHECK_DEV(origins); CHECK_CONTIG(origins);
+  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(1) == 2,
+              "origins must be int32 [B, 2] (y0, x0)");
+  TORCH_CHECK(origins.device() == like.device(), "origins must be on the scene's device");
+}
+
+// HBM-resident uint8 scene [H, W, Cin] -> bf16 windows [B, tile, tile, cpad], mirrored borders
+at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int64_t tile,
+                         int64_t cpad) {
+  CHECK_DEV(scene); CHECK_CONTIG(scene);
+  TORCH_CHECK(scene.scalar_type() == at::kByte && scene.dim() == 3, "scene must be uint8 [H, W, Cin]");
+  check_origins(origins, scene);
+  const int64_t H = scene.size(0), W = scene.size(1), in_ch = scene.size(2);
+  TORCH_CHECK(H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30), "scene size out of range");
+  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  c10::DeviceGuard guard(scene.device());
+  const int64_t B = origins.size(0);
+  TORCH_CHECK(B < (1 << 30), "too many windows");
+  at::Tensor x = at::empty({B, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
+  if (B > 0)
+    window_gather_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, (int)H, (int)W,
+                         (int)in_ch, (int)tile, (int)cpad, bptr_mut(x), cur_stream());
+  return x;
+}
+
+// acc[y0 + y, x0 + x, :K] += win[y] win[x] softmax(head(a)), acc[.., K] += win[y] win[x]
+// PRECONDITION: the windows of one call are pairwise disjoint (plan_windows' colour groups):
+// the kernel accumulates with plain read-modify-write, no atomics
+void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+                        const at::Tensor& origins, const at::Tensor& win, at::Tensor& acc,
+                        const c10::optional<at::Tensor>& bn4) {
+  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
+  TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2), "a must be [B, tile, tile, C]");
+  const int64_t B = a.size(0), tile = a.size(1);
+  const int C = (int)a.size(3);
+  CHECK_DEV(Wh); CHECK_F32(Wh); CHECK_CONTIG(Wh); CHECK_DEV(bh); CHECK_F32(bh); CHECK_CONTIG(bh);
+  TORCH_CHECK(Wh.dim() == 2 && Wh.size(1) == C && bh.numel() == Wh.size(0), "Wh [K, C] / bh [K]");
+  const int K = (int)Wh.size(0);
+  TORCH_CHECK(head_supported(C, K), "head kernel: unsupported (C, K)");
+  check_origins(origins, a);
+  TORCH_CHECK(origins.size(0) == B, "one origin per window");
+  CHECK_DEV(win); CHECK_F32(win); CHECK_CONTIG(win);
+  TORCH_CHECK(win.dim() == 1 && win.size(0) == tile, "win must be fp32 [tile]");
+  CHECK_DEV(acc); CHECK_F32(acc); CHECK_CONTIG(acc);
+  TORCH_CHECK(acc.dim() == 3 && acc.size(2) == 4 * ((K + 4) / 4),
+              "acc must be fp32 [H, W, 4 * ceil((K + 1) / 4)]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(acc.data_ptr()) % 16 == 0, "acc must be 16-byte aligned");
+  TORCH_CHECK(acc.size(0) < (1 << 30) && acc.size(1) < (1 << 30) && tile <= 32768 && B < (1 << 30),
+              "scene / window size out of range");
+  TORCH_CHECK(Wh.device() == a.device() && bh.device() == a.device() && win.device() == a.device() &&
+              acc.device() == a.device(), "device mismatch");
+  c10::DeviceGuard guard(a.device());
+  const float* pbn = bn4_ptr(bn4, C);
+  if (B == 0) return;
+  head_predict_accum_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), origins.data_ptr<int>(),
+                            win.data_ptr<float>(), acc.data_ptr<float>(), (int)B, (int)tile,
+                            (int)acc.size(0), (int)acc.size(1), (int)acc.size(2), C, K, pbn, cur_stream());
+}
+
+// accumulator [H, W, KA] -> {class map uint8 [H, W], confusion matrix int64 [K, K]}
+std::vector<at::Tensor> scene_finalize(const at::Tensor& acc, int64_t K,
+                                       const c10::optional<at::Tensor>& labels, int64_t ignore_index) {
+  CHECK_DEV(acc); CHECK_F32(acc); CHECK_CONTIG(acc);
+  TORCH_CHECK(acc.dim() == 3 && acc.size(2) % 4 == 0, "acc must be fp32 [H, W, KA], KA % 4 == 0");
+  TORCH_CHECK(K >= 1 && K <= 16 && K <= acc.size(2), "1 <= K <= min(16, KA)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(acc.data_ptr()) % 16 == 0, "acc must be 16-byte aligned");
+  c10::DeviceGuard guard(acc.device());
+  const int64_t H = acc.size(0), W = acc.size(1);
+  const uint8_t* lp = nullptr;
+  if (labels.has_value() && labels->defined()) {
+    CHECK_DEV(*labels); CHECK_CONTIG(*labels);
+    TORCH_CHECK(labels->scalar_type() == at::kByte && labels->dim() == 2 && labels->size(0) == H &&
+                labels->size(1) == W && labels->device() == acc.device(), "labels must be uint8 [H, W]");
+    lp = labels->data_ptr<uint8_t>();
+  }
+  at::Tensor pred = at::empty({H, W}, acc.options().dtype(at::kByte));
+  at::Tensor cm = at::zeros({K, K}, acc.options().dtype(at::kLong));
+  if (H * W > 0)
+    scene_finalize_launch(acc.data_ptr<float>(), (long long)H * W, (int)K, (int)acc.size(2), lp,
+                          (int)ignore_index, pred.data_ptr<uint8_t>(), cm.data_ptr<int64_t>(),
+                          cur_stream());
+  return {pred, cm};
+}
+
 // -> the CU count grids are sized for after reserving k CUs (k < 0: query only)
 int64_t set_cu_reserve(int64_t k) {
   if (k >= 0) g_cu_reserve = (int)std::min<int64_t>(k, std::max(0, phys_cus() - 8));
@@ -1646,6 +1733,11 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("synth_tiles(Tensor idx, int seed, int classes, int in_ch, int tile, int dims, int grid, "
         "float k, Tensor palette, int cpad) -> Tensor[]");
   m.def("tile_gather(Tensor src, Tensor lab, Tensor idx, int cpad) -> Tensor[]");
+  m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad) -> Tensor");
+  // (the windows of one call must be pairwise disjoint: acc is updated without atomics)
+  m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
+        "Tensor? bn4=None) -> ()");
+  m.def("scene_finalize(Tensor acc, int K, Tensor? labels=None, int ignore_index=-100) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
@@ -1686,5 +1778,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("to_nhwc_bf16", &ddlpc::to_nhwc_bf16);
   m.impl("synth_tiles", &ddlpc::synth_tiles);
   m.impl("tile_gather", &ddlpc::tile_gather);
+  m.impl("window_gather", &ddlpc::window_gather);
+  m.impl("head_predict_accum", &ddlpc::head_predict_accum);
+  m.impl("scene_finalize", &ddlpc::scene_finalize);
   m.impl("comm_proxy", &ddlpc::comm_proxy);
 }

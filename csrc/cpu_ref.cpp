@@ -946,6 +946,114 @@ std::vector<Tensor> tile_gather(const Tensor& src, const Tensor& lab, const Tens
   return {x, y};
 }
 
+// ------------------------------------------------------------------------ scene prediction
+int64_t reflect_index(int64_t i, int64_t n) {
+  if (n == 1) return 0;
+  const int64_t p = 2 * (n - 1);
+  i %= p;
+  if (i < 0) i += p;
+  return i >= n ? p - i : i;
+}
+
+Tensor window_gather(const Tensor& scene, const Tensor& origins, int64_t tile, int64_t cpad) {
+  TORCH_CHECK(scene.scalar_type() == at::kByte && scene.dim() == 3, "scene must be uint8 [H, W, Cin]");
+  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(1) == 2,
+              "origins must be int32 [B, 2] (y0, x0)");
+  const int64_t H = scene.size(0), W = scene.size(1), in_ch = scene.size(2), B = origins.size(0);
+  TORCH_CHECK(H >= 1 && W >= 1 && tile >= 1, "empty scene / window");
+  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
+  const Tensor sc = scene.contiguous(), oc = origins.contiguous();
+  const uint8_t* sp = sc.data_ptr<uint8_t>();
+  const int* op = oc.data_ptr<int>();
+  Tensor x = at::empty({B, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
+  auto* xp = x.data_ptr<c10::BFloat16>();
+  for (int64_t b = 0; b < B; ++b)
+    for (int64_t wy = 0; wy < tile; ++wy) {
+      const int64_t sy = reflect_index(op[2 * b] + wy, H);
+      for (int64_t wx = 0; wx < tile; ++wx) {
+        const int64_t sx = reflect_index(op[2 * b + 1] + wx, W);
+        const uint8_t* q = sp + (sy * W + sx) * in_ch;
+        c10::BFloat16* o = xp + ((b * tile + wy) * tile + wx) * cpad;
+        for (int64_t c = 0; c < cpad; ++c) o[c] = c10::BFloat16(c < in_ch ? (float)q[c] / 255.0f : 0.f);
+      }
+    }
+  return x;
+}
+
+void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& origins,
+                        const Tensor& win, Tensor& acc, const optional<Tensor>& bn4) {
+  TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2) && a.scalar_type() == at::kBFloat16,
+              "a must be bf16 [B, tile, tile, C]");
+  const int64_t B = a.size(0), tile = a.size(1), K = Wh.size(0);
+  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(0) == B &&
+              origins.size(1) == 2, "origins must be int32 [B, 2] (y0, x0)");
+  TORCH_CHECK(win.scalar_type() == at::kFloat && win.dim() == 1 && win.size(0) == tile,
+              "win must be fp32 [tile]");
+  TORCH_CHECK(acc.scalar_type() == at::kFloat && acc.is_contiguous() && acc.dim() == 3 &&
+              acc.size(2) == 4 * ((K + 4) / 4), "acc must be fp32 [H, W, 4 * ceil((K + 1) / 4)]");
+  const int64_t C = a.size(3);
+  TORCH_CHECK(K >= 1 && K <= 16 && (C == 8 || C == 16 || C == 32 || C == 64) && Wh.numel() == K * C,
+              "head kernel: unsupported (C, K)");
+  const int64_t H = acc.size(0), W = acc.size(1), KA = acc.size(2);
+  const Tensor A = head_act(a, bn4, 1);
+  const Tensor l = (at::matmul(A, f32(Wh).reshape({K, -1}).t()) + f32(bh).reshape({K})).contiguous();
+  const Tensor oc = origins.contiguous(), wc = win.contiguous();
+  const float* lp = l.data_ptr<float>();
+  const int* op = oc.data_ptr<int>();
+  const float* wp = wc.data_ptr<float>();
+  float* ap = acc.data_ptr<float>();
+  for (int64_t b = 0; b < B; ++b)
+    for (int64_t wy = 0; wy < tile; ++wy) {
+      const int64_t sy = op[2 * b] + wy;
+      if (sy < 0 || sy >= H) continue;
+      for (int64_t wx = 0; wx < tile; ++wx) {
+        const int64_t sx = op[2 * b + 1] + wx;
+        const float w2 = wp[wy] * wp[wx];
+        if (sx < 0 || sx >= W || w2 == 0.f) continue;
+        const float* z = lp + ((b * tile + wy) * tile + wx) * K;
+        float m = z[0], e[16], se = 0.f;
+        for (int64_t k = 1; k < K; ++k) m = std::max(m, z[k]);
+        for (int64_t k = 0; k < K; ++k) {
+          e[k] = std::exp(z[k] - m);
+          se += e[k];
+        }
+        float* o = ap + (sy * W + sx) * KA;
+        for (int64_t k = 0; k < K; ++k) o[k] += w2 * (e[k] / se);
+        o[K] += w2;
+      }
+    }
+}
+
+std::vector<Tensor> scene_finalize(const Tensor& acc, int64_t K, const optional<Tensor>& labels,
+                                   int64_t ignore_index) {
+  TORCH_CHECK(acc.scalar_type() == at::kFloat && acc.dim() == 3, "acc must be fp32 [H, W, KA]");
+  TORCH_CHECK(K >= 1 && K <= 16 && K <= acc.size(2), "1 <= K <= min(16, KA)");
+  const int64_t H = acc.size(0), W = acc.size(1), KA = acc.size(2);
+  const Tensor ac = acc.contiguous();
+  const float* ap = ac.data_ptr<float>();
+  Tensor pred = at::empty({H, W}, acc.options().dtype(at::kByte));
+  Tensor cm = at::zeros({K, K}, acc.options().dtype(at::kLong));
+  uint8_t* pp = pred.data_ptr<uint8_t>();
+  int64_t* cp = cm.data_ptr<int64_t>();
+  Tensor lc;
+  const uint8_t* lp = nullptr;
+  if (has(labels)) {
+    TORCH_CHECK(labels->scalar_type() == at::kByte && labels->dim() == 2 && labels->size(0) == H &&
+                labels->size(1) == W, "labels must be uint8 [H, W]");
+    lc = labels->contiguous();
+    lp = lc.data_ptr<uint8_t>();
+  }
+  for (int64_t px = 0; px < H * W; ++px) {
+    const float* z = ap + px * KA;
+    int64_t am = 0;
+    for (int64_t k = 1; k < K; ++k)
+      if (z[k] > z[am]) am = k;
+    pp[px] = (uint8_t)am;
+    if (lp != nullptr && lp[px] < K && lp[px] != ignore_index) cp[lp[px] * K + am] += 1;
+  }
+  return {pred, cm};
+}
+
 }  // namespace
 }  // namespace ddlpc_cpu
 
@@ -988,4 +1096,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("to_nhwc_bf16", &to_nhwc_bf16);
   m.impl("synth_tiles", &synth_tiles);
   m.impl("tile_gather", &tile_gather);
+  m.impl("window_gather", &window_gather);
+  m.impl("head_predict_accum", &head_predict_accum);
+  m.impl("scene_finalize", &scene_finalize);
 }

@@ -1099,6 +1099,67 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const bf16_t* __restri
   }
 }
 
+// Whole-scene prediction (overlap-tile inference, ddlpc/infer.py): the head of a batch of
+// windows, softmax and the blend into the scene's fp32 accumulator acc [H][W][KA]
+// (KA = 4 ceil((K + 1) / 4): one pixel = KA / 4 aligned float4s) in one pass — the logits
+// never reach HBM.  Window b covers scene rows origins[b][0] .. + tile, columns
+// origins[b][1] .. + tile; a window pixel inside the scene with weight w2 = win[y] * win[x]
+// != 0 adds w2 * softmax_k to channel k < K and w2 to channel K; channels above K keep their
+// bits, every other pixel is not touched.  The windows of one launch are pairwise disjoint
+// (the colour plan), so a scene pixel belongs to at most one thread: plain read-modify-write,
+// no atomics, the same bits on every run.
+template <int C, int K, bool DEFER>
+__global__ __launch_bounds__(256) void head_predict_accum_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int* __restrict__ origins, const float* __restrict__ win, float* __restrict__ acc,
+    long long P, int tile, int H, int W, int KA, const float* __restrict__ bn4, int Kreal) {
+  __shared__ __attribute__((aligned(16))) float sBNm[4 * C];
+  __shared__ float sW[K * C], sb[K];
+  load_head<C, K>(Wh, bh, Kreal, sW, sb);
+  const float* sBN = DEFER ? load_bn<C>(bn4, sBNm, false) : nullptr;
+  __syncthreads();
+  const int S = tile * tile;
+#pragma unroll 1
+  for (long long px = blockIdx.x * (long long)blockDim.x + threadIdx.x; px < P;
+       px += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(px / S);
+    const int p = (int)(px - (long long)b * S);
+    const int wy = p / tile, wx = p - wy * tile;
+    const int sy = origins[2 * b] + wy, sx = origins[2 * b + 1] + wx;
+    const float w2 = win[wy] * win[wx];
+    if (sy < 0 || sy >= H || sx < 0 || sx >= W || w2 == 0.f) continue;
+    float z[K];
+    logits_of<C, K, DEFER>(a + px * C, sW, sb, sBN, z);
+    float m = z[0];
+#pragma unroll
+    for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      z[k] = __expf(z[k] - m);
+      se += z[k];
+    }
+    const float ws = w2 / se;
+    float4* ap = reinterpret_cast<float4*>(acc + ((long long)sy * W + sx) * KA);
+#pragma unroll
+    for (int q = 0; q < (K + 4) / 4; ++q) {
+      if (4 * q < KA) {
+        const float4 v = ap[q];
+        float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          constexpr int kmax = K - 1;
+          const int k = 4 * q + j;
+          const float pk = ws * z[k < K ? k : kmax];
+          if (k < Kreal) f[j] += pk;
+          else if (k == Kreal) f[j] += w2;
+        }
+        ap[q] = make_float4(f[0], f[1], f[2], f[3]);
+      }
+    }
+  }
+}
+
 // C in {8, 16, 32, 64} (64 / width_divisor channels) x padded class slots KP >= K
 #define HEAD_SWITCH_K(C_, K_, ...)                                                  \
   if (K_ <= 2) { constexpr int KK = 2; __VA_ARGS__; }                               \
@@ -1292,6 +1353,19 @@ void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_logits_kernel<CC, KK, false>), dim3(grid), dim3(256), 0, st,
                                          a, Wh, bh, logits, P, HW, bn4, K));
+}
+
+void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh, const int* origins,
+                               const float* win, float* acc, int B, int tile, int H, int W, int KA,
+                               int C, int K, const float* bn4, hipStream_t st) {
+  const long long P = (long long)B * tile * tile;
+  const int grid = (int)std::min<long long>((P + 255) / 256, 4096);
+  if (bn4 != nullptr)
+    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, true>), dim3(grid), dim3(256),
+                                         0, st, a, Wh, bh, origins, win, acc, P, tile, H, W, KA, bn4, K));
+  else
+    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, false>), dim3(grid), dim3(256),
+                                         0, st, a, Wh, bh, origins, win, acc, P, tile, H, W, KA, bn4, K));
 }
 
 }  // namespace ddlpc

@@ -277,7 +277,17 @@ void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, con
                           int ignore_index, hipStream_t st, int groups = 1);
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
+// whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the
+// scene accumulator acc [H][W][KA]; origins [B][2] = (y0, x0), win [tile] blend weights
+void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh, const int* origins,
+                               const float* win, float* acc, int B, int tile, int H, int W, int KA,
+                               int C, int K, const float* bn4, hipStream_t st);
 
+// ---------------------------------------------------------------- scene prediction (scene.hip)
+void window_gather_launch(const uint8_t* scene, const int* origins, int B, int H, int W, int in_ch,
+                          int tile, int cpad, bf16_t* x, hipStream_t st);
+void scene_finalize_launch(const float* acc, long long P, int K, int KA, const uint8_t* labels,
+                           int ignore_index, uint8_t* pred, int64_t* cm, hipStream_t st);
 
 // ---------------------------------------------------------------- optimizer / packing
 void adam_launch(float* p, const float* g, float* m, float* v, long long n, float b1, float b2,

@@ -1,4 +1,4 @@
-"""Command-line entry point: ``python -m ddlpc {train,validate,config}``.
+"""Command-line entry point: ``python -m ddlpc {train,validate,predict,config}``.
 
 The reference is started by hand on every PC (server first, then workers; rank from a
 hostname table, ref.py:223-251) and has no flags at all.  Here one command
@@ -10,8 +10,12 @@ MASTER_ADDR / MASTER_PORT come from the environment), e.g.
 
 Every ``TrainConfig`` / ``ModelConfig`` field is a ``--flag`` (``--config file.yaml`` first,
 flags override).  ``train`` prints the final reduced metrics as one JSON line on rank 0;
-``validate`` evaluates a checkpoint on the held-out split; ``config`` prints the resolved
-configuration (handy for writing a YAML to start from).
+``validate`` evaluates a checkpoint on the held-out split; ``predict`` segments whole scenes
+(a file or a directory of images, any size) by overlap-tile inference, e.g.
+
+    python -m ddlpc predict --checkpoint runs/x/ckpt_900.pt --input scenes/ --out-dir pred/
+
+and ``config`` prints the resolved configuration (handy for writing a YAML to start from).
 """
 from __future__ import annotations
 
@@ -22,6 +26,9 @@ import sys
 from typing import List, Optional
 
 from .config import add_config_args, config_from_args
+
+
+_PREDICT_ARGS = ("input", "out_dir", "pred_tile", "overlap", "blend", "window_batch", "save_proba")
 
 
 def _rank0() -> bool:
@@ -36,17 +43,35 @@ def main(argv: Optional[List[str]] = None) -> int:
     p_val = add_config_args(sub.add_parser("validate", help="evaluate on the held-out split"))
     p_val.add_argument("--checkpoint", default=None)
     p_val.add_argument("--device", default=None)
+    p_pred = add_config_args(sub.add_parser("predict", help="segment whole scenes (overlap-tile)"))
+    p_pred.add_argument("--checkpoint", required=True)
+    p_pred.add_argument("--input", required=True, help="an image, or a directory of images "
+                        "(+ optional .npy label maps)")
+    p_pred.add_argument("--out-dir", required=True)
+    p_pred.add_argument("--pred-tile", type=int, default=None, help="window size (default: --tile)")
+    p_pred.add_argument("--overlap", type=int, default=None, help="even, <= tile/2 (default: tile/4)")
+    p_pred.add_argument("--blend", choices=("core", "cosine"), default="cosine")
+    p_pred.add_argument("--window-batch", type=int, default=16)
+    p_pred.add_argument("--save-proba", action="store_true")
+    p_pred.add_argument("--device", default=None)
     add_config_args(sub.add_parser("config", help="print the resolved config as JSON"))
     args = ap.parse_args(argv)
     cmd = args.cmd
     device = getattr(args, "device", None)
     checkpoint = getattr(args, "checkpoint", None)
-    for k in ("cmd", "device", "checkpoint"):
+    pred_args = {k: getattr(args, k, None) for k in _PREDICT_ARGS}
+    for k in ("cmd", "device", "checkpoint") + _PREDICT_ARGS:
         if hasattr(args, k):
             delattr(args, k)
     cfg = config_from_args(args)
     if cmd == "config":
         print(json.dumps(cfg.to_dict(), indent=2))
+        return 0
+    if cmd == "predict":
+        from .infer import predict
+        metrics = predict(cfg, checkpoint, pred_args.pop("input"), **pred_args, device=device)
+        if _rank0():
+            print(json.dumps({"cmd": cmd, **metrics}))
         return 0
     from .train.trainer import train, validate
     if cmd == "train":
