@@ -82,9 +82,11 @@ int pick_bn(int Cout) {
 // (torch.ops.ddlpc.set_knob) or else the environment variable DDLPC_<NAME>, or else def.
 // Every name a kernel reads is listed in kKnobs; set_knob rejects any other name, so an A/B
 // (bench.py --ab, scripts/conv_micro.py --ab) can never silently time two identical
-// configurations.  An empty list = no experiment in progress.
+// configurations.
+//   CROP_LDS_T (default 1): crop_gather's transposing codes through LDS; 0 = the direct
+//   strided read, kept for scripts/crop_micro.py's A/B (docs/PERF.md)
 namespace {
-const char* const kKnobs[] = {""};
+const char* const kKnobs[] = {"CROP_LDS_T"};
 bool knob_registered(const std::string& name) {
   for (const char* k : kKnobs)
     if (k[0] != 0 && name == k) return true;
@@ -1562,6 +1564,76 @@ std::vector<at::Tensor> tile_gather(const at::Tensor& src, const at::Tensor& lab
   return {x, y};
 }
 
+// packed scenes (uint8 pixels [P, Cin], uint8 labels [P], int64 table [n, 3] of (offset, H, W))
+// -> tile x tile crops per params (scene, y0, x0, code), mirrored borders, one of the 8
+// symmetries of the square, optional per-sample (gain, bias): {x bf16 [B, T, T, cpad], y int64}
+std::vector<at::Tensor> crop_gather(const at::Tensor& scenes, const at::Tensor& labels,
+                                    const at::Tensor& table, const at::Tensor& params,
+                                    const c10::optional<at::Tensor>& color, int64_t tile,
+                                    int64_t cpad) {
+  CHECK_DEV(scenes); CHECK_CONTIG(scenes); CHECK_DEV(labels); CHECK_CONTIG(labels);
+  CHECK_DEV(table); CHECK_CONTIG(table); CHECK_DEV(params); CHECK_CONTIG(params);
+  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
+  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
+              "labels must be uint8 [pixels]");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
+              "table must be int64 [n, 3] (pixel offset, H, W)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
+              "params must be int32 [B, 4] (scene, y0, x0, code)");
+  const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0);
+  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  TORCH_CHECK(n < (1LL << 31), "too many scenes");
+  TORCH_CHECK(labels.device() == scenes.device() && table.device() == scenes.device() &&
+              params.device() == scenes.device(), "crop_gather: tensors on different devices");
+  const bool has_color = color.has_value() && color->defined();
+  if (has_color) {
+    CHECK_DEV(*color); CHECK_CONTIG(*color); CHECK_F32(*color);
+    TORCH_CHECK(color->dim() == 2 && color->size(0) == B && color->size(1) == 2 &&
+                color->device() == scenes.device(), "color must be fp32 [B, 2] (gain, bias)");
+  }
+  const int64_t nb = crop_gather_blocks((int)tile);
+  TORCH_CHECK(B * nb * nb < (1LL << 31), "crop_gather: batch too large");
+  c10::DeviceGuard guard(scenes.device());
+  at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
+  at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
+  if (B > 0)
+    crop_gather_launch(scenes.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
+                       (int)n, (long long)labels.size(0), params.data_ptr<int>(),
+                       has_color ? color->data_ptr<float>() : nullptr, (int)B, (int)in_ch, (int)tile,
+                       (int)cpad, knob("CROP_LDS_T", 1) != 0, bptr_mut(x), y.data_ptr<int64_t>(),
+                       cur_stream());
+  return {x, y};
+}
+
+// virtual sample numbers -> {params int32 [B, 4], color fp32 [B, 2]} (counter-based: data.hip)
+std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
+                                    int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
+                                    double bias_jitter) {
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(cum); CHECK_CONTIG(cum); CHECK_DEV(table); CHECK_CONTIG(table);
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
+              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
+  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
+              "cum must be int64 [n + 1]");
+  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device(),
+              "crop_params: tensors on different devices");
+  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  c10::DeviceGuard guard(idx.device());
+  const int64_t B = idx.numel();
+  TORCH_CHECK(B < (1LL << 31), "too many samples");
+  at::Tensor params = at::empty({B, 4}, idx.options().dtype(at::kInt));
+  at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
+  if (B > 0)
+    crop_params_launch(idx.data_ptr<int64_t>(), (int)B, cum.data_ptr<int64_t>(), table.data_ptr<int64_t>(),
+                       (int)table.size(0), (uint32_t)(seed & 0xffffffff), (int)tile, (int)mode,
+                       (float)gain_jitter, (float)bias_jitter, params.data_ptr<int>(),
+                       color.data_ptr<float>(), cur_stream());
+  return {params, color};
+}
+
 // ------------------------------------------------------------------------ scene prediction
 static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
   CHECK_DEV(origins); CHECK_CONTIG(origins);
@@ -1733,6 +1805,10 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("synth_tiles(Tensor idx, int seed, int classes, int in_ch, int tile, int dims, int grid, "
         "float k, Tensor palette, int cpad) -> Tensor[]");
   m.def("tile_gather(Tensor src, Tensor lab, Tensor idx, int cpad) -> Tensor[]");
+  m.def("crop_gather(Tensor scenes, Tensor labels, Tensor table, Tensor params, Tensor? color, "
+        "int tile, int cpad) -> Tensor[]");
+  m.def("crop_params(Tensor idx, Tensor cum, Tensor table, int seed, int tile, int mode, "
+        "float gain_jitter, float bias_jitter) -> Tensor[]");
   m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad) -> Tensor");
   // (the windows of one call must be pairwise disjoint: acc is updated without atomics)
   m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
@@ -1778,6 +1854,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("to_nhwc_bf16", &ddlpc::to_nhwc_bf16);
   m.impl("synth_tiles", &ddlpc::synth_tiles);
   m.impl("tile_gather", &ddlpc::tile_gather);
+  m.impl("crop_gather", &ddlpc::crop_gather);
+  m.impl("crop_params", &ddlpc::crop_params);
   m.impl("window_gather", &ddlpc::window_gather);
   m.impl("head_predict_accum", &ddlpc::head_predict_accum);
   m.impl("scene_finalize", &ddlpc::scene_finalize);

@@ -980,6 +980,123 @@ Tensor window_gather(const Tensor& scene, const Tensor& origins, int64_t tile, i
   return x;
 }
 
+// ------------------------------------------------------------------------ augmented crops
+// csrc/data.hip crop_gather_kernel / crop_params_kernel, bit for bit (every float operation
+// rounds on its own)
+std::vector<Tensor> crop_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+                                const Tensor& params, const optional<Tensor>& color, int64_t tile,
+                                int64_t cpad) {
+  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
+  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
+              "labels must be uint8 [pixels]");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
+              "table must be int64 [n, 3] (pixel offset, H, W)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
+              "params must be int32 [B, 4] (scene, y0, x0, code)");
+  const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0), P = labels.size(0);
+  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  const bool has_color = has(color);
+  Tensor cc;
+  if (has_color) {
+    TORCH_CHECK(color->scalar_type() == at::kFloat && color->dim() == 2 && color->size(0) == B &&
+                color->size(1) == 2, "color must be fp32 [B, 2] (gain, bias)");
+    cc = color->contiguous();
+  }
+  const Tensor sc = scenes.contiguous(), lc = labels.contiguous(), tc = table.contiguous(),
+               pc = params.contiguous();
+  const uint8_t* sp = sc.data_ptr<uint8_t>();
+  const uint8_t* lp = lc.data_ptr<uint8_t>();
+  const int64_t* tp = tc.data_ptr<int64_t>();
+  const int* pp = pc.data_ptr<int>();
+  const float* cp = has_color ? cc.data_ptr<float>() : nullptr;
+  Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
+  Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
+  int64_t* yp = y.data_ptr<int64_t>();
+  auto* xp = x.data_ptr<c10::BFloat16>();
+  at::parallel_for(0, B * tile, 16, [&](int64_t r0, int64_t r1) {
+    for (int64_t row = r0; row < r1; ++row) {
+      const int64_t b = row / tile, oy = row - b * tile;
+      const int64_t s = pp[4 * b], y0 = pp[4 * b + 1], x0 = pp[4 * b + 2];
+      const int code = pp[4 * b + 3] & 7;
+      const bool listed = s >= 0 && s < n;
+      const int64_t off = listed ? tp[3 * s] : 0, H = listed ? tp[3 * s + 1] : 1, W = listed ? tp[3 * s + 2] : 1;
+      const bool valid = listed && H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30) && off >= 0 &&
+                         off <= P && H * W <= P - off;
+      const float gain = has_color ? cp[2 * b] : 1.f, bias = has_color ? cp[2 * b + 1] : 0.f;
+      for (int64_t ox = 0; ox < tile; ++ox) {
+        const int64_t e = row * tile + ox;
+        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+        if (code & 2) a = tile - 1 - a;
+        if (code & 1) c = tile - 1 - c;
+        const int64_t q = valid ? off + reflect_index(y0 + a, H) * W + reflect_index(x0 + c, W) : 0;
+        yp[e] = valid ? (int64_t)lp[q] : (int64_t)-100;
+        for (int64_t ch = 0; ch < cpad; ++ch) {
+          float v = 0.f;
+          if (ch < in_ch && valid) {
+            v = (float)sp[q * in_ch + ch] / 255.0f;
+            if (has_color) {
+              volatile float m = v * gain;
+              volatile float t = m + bias;
+              v = std::fmin(std::fmax((float)t, 0.f), 1.f);
+            }
+          }
+          xp[e * cpad + ch] = c10::BFloat16(v);
+        }
+      }
+    }
+  });
+  return {x, y};
+}
+
+std::vector<Tensor> crop_params(const Tensor& idx, const Tensor& cum, const Tensor& table, int64_t seed,
+                                int64_t tile, int64_t mode, double gain_jitter, double bias_jitter) {
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
+              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
+  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
+              "cum must be int64 [n + 1]");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  const Tensor ix = idx.contiguous(), cc = cum.contiguous(), tc = table.contiguous();
+  const int64_t B = ix.numel(), n = table.size(0);
+  const int64_t* ip = ix.data_ptr<int64_t>();
+  const int64_t* cp = cc.data_ptr<int64_t>();
+  const int64_t* tp = tc.data_ptr<int64_t>();
+  Tensor params = at::empty({B, 4}, idx.options().dtype(at::kInt));
+  Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
+  int* pp = params.data_ptr<int>();
+  float* op = color.data_ptr<float>();
+  const uint32_t skey = mix32((uint32_t)(seed & 0xffffffff) ^ 0xC2B2AE35u);
+  const float gj = (float)gain_jitter, bj = (float)bias_jitter;
+  for (int64_t i = 0; i < B; ++i) {
+    const uint64_t s = (uint64_t)ip[i];
+    const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
+    uint32_t r[6];
+    for (int j = 0; j < 6; ++j) r[j] = mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u);
+    const uint64_t t = ((uint64_t)r[0] * (uint64_t)cp[n]) >> 32;
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((uint64_t)cp[mid] <= t) lo = mid; else hi = mid;
+    }
+    const int64_t H = tp[3 * lo + 1], W = tp[3 * lo + 2];
+    const uint64_t ny = (uint64_t)(H > tile ? H - tile : 0) + 1u, nx = (uint64_t)(W > tile ? W - tile : 0) + 1u;
+    pp[4 * i] = (int)lo;
+    pp[4 * i + 1] = (int)(((uint64_t)r[1] * ny) >> 32);
+    pp[4 * i + 2] = (int)(((uint64_t)r[2] * nx) >> 32);
+    pp[4 * i + 3] = mode == 0 ? 0 : (int)(r[3] & (mode == 1 ? 3u : 7u));
+    for (int k = 0; k < 2; ++k) {
+      volatile float u2 = 2.0f * u24(r[4 + k]);
+      volatile float d = u2 + -1.0f;
+      volatile float m = (k == 0 ? gj : bj) * d;
+      volatile float g = 1.0f + m;
+      op[2 * i + k] = k == 0 ? (float)g : (float)m;
+    }
+  }
+  return {params, color};
+}
+
 void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& origins,
                         const Tensor& win, Tensor& acc, const optional<Tensor>& bn4) {
   TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2) && a.scalar_type() == at::kBFloat16,
@@ -1097,6 +1214,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("synth_tiles", &synth_tiles);
   m.impl("tile_gather", &tile_gather);
   m.impl("window_gather", &window_gather);
+  m.impl("crop_gather", &crop_gather);
+  m.impl("crop_params", &crop_params);
   m.impl("head_predict_accum", &head_predict_accum);
   m.impl("scene_finalize", &scene_finalize);
 }

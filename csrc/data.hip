@@ -20,6 +20,25 @@
 //   * tile_gather_kernel: a real dataset uploaded ONCE to HBM as uint8 NHWC (+ uint8 label
 //     maps): gather the batch's sample indices, /255 (IEEE division, as the reference's
 //     numpy op), pad, bf16; labels widen to int64.
+//   * crop_params_kernel + crop_gather_kernel: training on whole scenes.  The scenes are
+//     uploaded ONCE, packed: uint8 pixels [total_pixels, in_ch], uint8 labels [total_pixels]
+//     and an int64 table [n, 3] of (pixel offset, H, W) rows (a contiguous tile stack is
+//     this packing with offset = n H W).  A batch is tile x tile random crops, augmented by
+//     one of the 8 symmetries of the square and a per-sample gain / bias, cut in one pass.
+//     Virtual sample s depends only on (seed, s), as the synthetic recipe (twin:
+//     data/scenes.py crop_params_reference):
+//       key   = mix(mix(mix(seed ^ 0xC2B2AE35) ^ lo32(s)) ^ mix(hi32(s) + 0x85EBCA6B))
+//       r_j   = mix(key + (j + 1) * 0x9E3779B9)                       j = 0..5
+//       scene = the k with cum[k] <= (r0 * cum[n]) >> 32 < cum[k + 1], cum = prefix sum of
+//               the scenes' valid-origin counts ny * nx, ny = max(H - tile, 0) + 1 (crops are
+//               uniform over all valid crops; cum[n] < 2^32)
+//       y0    = (r1 * ny) >> 32,  x0 = (r2 * nx) >> 32
+//       code  = 0 | r3 & 3 | r3 & 7                                   (none | flip | d4)
+//       gain  = 1 + gain_jitter * (2 u24(r4) - 1),  bias = bias_jitter * (2 u24(r5) - 1)
+//     crop_gather: output pixel (oy, ox) reads source pixel (y0 + a, x0 + b), mirrored into
+//     the scene (reflect_index): (a, b) = (oy, ox); code & 4: swap a, b; code & 2: a = tile -
+//     1 - a; code & 1: b = tile - 1 - b.  Value: v = u8 / 255, with colour clamp(round(v *
+//     gain) + bias, 0, 1), every op rounded on its own, then bf16.
 #include "common.h"
 #include "ops.h"
 
@@ -143,7 +162,165 @@ int data_grid(long long total) {
   return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 16384));
 }
 
+// ---- augmented random crops -------------------------------------------------------------
+// one thread per virtual sample number: see the recipe in the header
+__global__ __launch_bounds__(256) void crop_params_kernel(
+    const int64_t* __restrict__ idx, int B, const int64_t* __restrict__ cum,
+    const int64_t* __restrict__ table, int n, uint32_t seed, int tile, int mode, float gj, float bj,
+    int* __restrict__ params, float* __restrict__ color) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const uint64_t s = (uint64_t)idx[i];
+  const uint32_t skey = mix32(seed ^ 0xC2B2AE35u);
+  const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
+  uint32_t r[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) r[j] = mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u);
+  const uint64_t t = ((uint64_t)r[0] * (uint64_t)cum[n]) >> 32;
+  int lo = 0, hi = n;                        // the scene with cum[lo] <= t < cum[lo + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint64_t)cum[mid] <= t) lo = mid; else hi = mid;
+  }
+  const long long H = table[3 * lo + 1], W = table[3 * lo + 2];
+  const uint64_t ny = (uint64_t)(H > tile ? H - tile : 0) + 1u;
+  const uint64_t nx = (uint64_t)(W > tile ? W - tile : 0) + 1u;
+  params[4 * i] = lo;
+  params[4 * i + 1] = (int)(((uint64_t)r[1] * ny) >> 32);
+  params[4 * i + 2] = (int)(((uint64_t)r[2] * nx) >> 32);
+  params[4 * i + 3] = mode == 0 ? 0 : (int)(r[3] & (mode == 1 ? 3u : 7u));
+  color[2 * i] = __fadd_rn(1.0f, mul_rn(gj, __fadd_rn(mul_rn(2.0f, u24(r[4])), -1.0f)));
+  color[2 * i + 1] = mul_rn(bj, __fadd_rn(mul_rn(2.0f, u24(r[5])), -1.0f));
+}
+
+// reflect_index without the division for a coordinate already inside the scene (all of them,
+// for a crop that does not overhang)
+DDLPC_DEVICE int reflect_fast(int i, int n) {
+  return (unsigned)i < (unsigned)n ? i : reflect_index(i, n);
+}
+
+constexpr int kCropBS = 32;                  // output pixels per workgroup: kCropBS^2
+
+// One workgroup (256 threads) per kCropBS^2 block of one sample's output pixels; lanes run
+// along ox, so every output row segment is one 16-byte store per lane.
+//   * codes without bit 4: a lane's source pixel moves by +-1 column with ox — the source row
+//     is read forwards or backwards, coalesced; straight from HBM.
+//   * codes with bit 4 (transposing): source COLUMN = f(oy), source ROW = f(ox).  With
+//     LDS_T the block's source pixels are first read with lanes along the source row
+//     (coalesced) into LDS as raw bytes, s[ox][oy], and the output phase reads s transposed;
+//     rows padded to kCropBS + 1 entries: the transposed 8-byte read then touches 64 distinct
+//     banks per 32-lane half, the 4-byte label read 32.  Without LDS_T adjacent lanes read
+//     pixels W * in_ch bytes apart.
+// The per-sample code is uniform in a workgroup, so no branch below diverges inside a wave.
+template <bool LDS_T>
+__global__ __launch_bounds__(256) void crop_gather_kernel(
+    const uint8_t* __restrict__ src, const uint8_t* __restrict__ lab,
+    const int64_t* __restrict__ table, int n, long long total_px, const int* __restrict__ params,
+    const float* __restrict__ color, int nb, int in_ch, int tile, int cpad,
+    bf16_t* __restrict__ x, int64_t* __restrict__ y) {
+  __shared__ uint2 s_px[kCropBS][kCropBS + 1];
+  __shared__ uint32_t s_lab[kCropBS][kCropBS + 1];
+  const int blk = blockIdx.x;
+  const int b = blk / (nb * nb);
+  const int rem = blk - b * nb * nb;
+  const int by = rem / nb, bx = rem - by * nb;
+  const int lx = threadIdx.x & (kCropBS - 1), ly0 = threadIdx.x / kCropBS;
+  constexpr int kRows = 256 / kCropBS;       // block rows covered per pass
+  const int sc = params[4 * b];
+  const bool listed = sc >= 0 && sc < n;
+  const int oy0 = params[4 * b + 1], ox0 = params[4 * b + 2], code = params[4 * b + 3] & 7;
+  const long long off = listed ? table[3 * sc] : 0;
+  const long long Hl = listed ? table[3 * sc + 1] : 1, Wl = listed ? table[3 * sc + 2] : 1;
+  // a scene outside [0, n) reads nothing, nor does a table row that does not lie inside the
+  // pixel buffer (the table is device data: the host cannot check it without a read-back)
+  const bool valid = listed && Hl >= 1 && Wl >= 1 && Hl < (1 << 30) && Wl < (1 << 30) && off >= 0 &&
+                     off <= total_px && Hl * Wl <= total_px - off;
+  const int H = valid ? (int)Hl : 1, W = valid ? (int)Wl : 1;
+  const bool has_color = color != nullptr;
+  const float gain = has_color ? color[2 * b] : 1.f, bias = has_color ? color[2 * b + 1] : 0.f;
+  const bool staged = LDS_T && valid && (code & 4);
+  if (staged) {
+    // load role: r = ox - block origin (source row), lanes c = oy - block origin (source column)
+    for (int r = ly0; r < kCropBS; r += kRows) {
+      const int ox = bx * kCropBS + r, oy = by * kCropBS + lx;
+      if (ox < tile && oy < tile) {
+        const int a = (code & 2) ? tile - 1 - ox : ox;
+        const int c = (code & 1) ? tile - 1 - oy : oy;
+        const long long sp = off + (long long)reflect_fast(oy0 + a, H) * W + reflect_fast(ox0 + c, W);
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int ch = 0; ch < 8; ++ch)
+          if (ch < in_ch) w[ch >> 2] |= (uint32_t)src[sp * in_ch + ch] << (8 * (ch & 3));
+        s_px[r][lx] = make_uint2(w[0], w[1]);
+        s_lab[r][lx] = lab[sp];
+      }
+    }
+    __syncthreads();
+  }
+  for (int ly = ly0; ly < kCropBS; ly += kRows) {
+    const int oy = by * kCropBS + ly, ox = bx * kCropBS + lx;
+    if (oy >= tile || ox >= tile) continue;
+    const long long e = ((long long)b * tile + oy) * tile + ox;
+    uint32_t w[2] = {0u, 0u};
+    int64_t l = -100;
+    if (staged) {
+      const uint2 v = s_px[lx][ly];
+      w[0] = v.x; w[1] = v.y;
+      l = (int64_t)s_lab[lx][ly];
+    } else if (valid) {
+      int a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+      if (code & 2) a = tile - 1 - a;
+      if (code & 1) c = tile - 1 - c;
+      const long long sp = off + (long long)reflect_fast(oy0 + a, H) * W + reflect_fast(ox0 + c, W);
+#pragma unroll
+      for (int ch = 0; ch < 8; ++ch)
+        if (ch < in_ch) w[ch >> 2] |= (uint32_t)src[sp * in_ch + ch] << (8 * (ch & 3));
+      l = (int64_t)lab[sp];
+    }
+    y[e] = l;
+    float f[8];
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+      float v = 0.f;
+      if (ch < in_ch && valid) {
+        v = __fdiv_rn((float)((w[ch >> 2] >> (8 * (ch & 3))) & 0xffu), 255.0f);
+        if (has_color) v = fminf(fmaxf(__fadd_rn(mul_rn(v, gain), bias), 0.f), 1.f);
+      }
+      f[ch] = v;
+    }
+    if (cpad == 8) {
+      reinterpret_cast<uint4*>(x)[e] = pack8(f);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 8; ++ch)
+        if (ch < cpad) x[e * cpad + ch] = f2bf(f[ch]);
+    }
+  }
+}
+
 }  // namespace
+
+void crop_params_launch(const int64_t* idx, int B, const int64_t* cum, const int64_t* table, int n,
+                        uint32_t seed, int tile, int mode, float gain_jitter, float bias_jitter,
+                        int* params, float* color, hipStream_t st) {
+  hipLaunchKernelGGL(crop_params_kernel, dim3((B + 255) / 256), dim3(256), 0, st, idx, B, cum, table,
+                     n, seed, tile, mode, gain_jitter, bias_jitter, params, color);
+}
+
+int crop_gather_blocks(int tile) { return (tile + kCropBS - 1) / kCropBS; }
+
+void crop_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
+                        long long total_px, const int* params, const float* color, int B, int in_ch,
+                        int tile, int cpad, bool lds_transpose, bf16_t* x, int64_t* y, hipStream_t st) {
+  const int nb = crop_gather_blocks(tile);
+  const dim3 grid((unsigned)((long long)B * nb * nb));
+  if (lds_transpose)
+    hipLaunchKernelGGL(crop_gather_kernel<true>, grid, dim3(256), 0, st, src, lab, table, n, total_px,
+                       params, color, nb, in_ch, tile, cpad, x, y);
+  else
+    hipLaunchKernelGGL(crop_gather_kernel<false>, grid, dim3(256), 0, st, src, lab, table, n, total_px,
+                       params, color, nb, in_ch, tile, cpad, x, y);
+}
 
 void synth_tiles_launch(const int64_t* idx, int B, uint32_t seed, int classes, int in_ch, int tile,
                         int dims, int grid, float k, const float* palette, int cpad, bf16_t* x,

@@ -361,6 +361,13 @@ void synth_tiles_launch(const int64_t* idx, int B, uint32_t seed, int classes, i
 void tile_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* idx, int B,
                         long long S, int in_ch, int cpad, long long N, bf16_t* x, int64_t* y,
                         hipStream_t st);
+void crop_params_launch(const int64_t* idx, int B, const int64_t* cum, const int64_t* table, int n,
+                        uint32_t seed, int tile, int mode, float gain_jitter, float bias_jitter,
+                        int* params, float* color, hipStream_t st);
+int crop_gather_blocks(int tile);   // workgroups per output row / column of one sample
+void crop_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
+                        long long total_px, const int* params, const float* color, int B, int in_ch,
+                        int tile, int cpad, bool lds_transpose, bf16_t* x, int64_t* y, hipStream_t st);
 
 void bn_running_apply_launch(float* rm, float* rv, const float* slots, int K, int C, long long stride,
                              float momentum, int64_t* nbt, hipStream_t st);
@@ -370,7 +377,7 @@ void bn_running_apply_all_launch(const int64_t* entries, int L, int maxC, const 
 // ---------------------------------------------------------------- A/B switches (bindings.cpp)
 // knob("NAME", def): an in-process override (torch.ops.ddlpc.set_knob, for interleaved
 // same-process A/B runs) or else the environment variable DDLPC_NAME, or else def — for
-// experiments in progress only: no shipped kernel reads one
+// experiments in progress, and for a rejected path kept measurable (CROP_LDS_T, data.hip)
 int knob(const char* name, int def);
 
 // ---------------------------------------------------------------- comm proxy (reduce.hip)

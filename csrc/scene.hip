@@ -20,16 +20,6 @@ namespace ddlpc {
 
 namespace {
 
-// mirror index i into [0, n): period 2 (n - 1), edge pixel not repeated; a window may wrap
-// several times over a scene smaller than itself
-DDLPC_DEVICE int reflect_index(int i, int n) {
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  i %= p;
-  if (i < 0) i += p;
-  return i >= n ? p - i : i;
-}
-
 __global__ __launch_bounds__(256) void window_gather_kernel(
     const uint8_t* __restrict__ scene, const int* __restrict__ origins, int B, int H, int W,
     int in_ch, int tile, int cpad, bf16_t* __restrict__ x) {

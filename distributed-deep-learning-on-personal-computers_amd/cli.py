@@ -15,7 +15,9 @@ flags override).  ``train`` prints the final reduced metrics as one JSON line on
 
     python -m ddlpc predict --checkpoint runs/x/ckpt_900.pt --input scenes/ --out-dir pred/
 
-and ``config`` prints the resolved configuration (handy for writing a YAML to start from).
+``train --data scene_dir --data-dir scenes/ --augment d4`` trains on uncut scenes of unequal size
+(augmented random crops cut on the device, ``data/scenes.py``);
+``config`` prints the resolved configuration (handy for writing a YAML to start from).
 """
 from __future__ import annotations
 

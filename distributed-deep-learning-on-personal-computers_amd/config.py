@@ -24,7 +24,8 @@ GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax")
 CODEC_SCALES = ("global", "bucket", "tensor")
 REDUCE_OPS = ("mean", "sum", "reference")
 UP_MODES = ("conv_transpose", "bilinear")
-DATA_KINDS = ("synthetic", "vaihingen_dir")
+DATA_KINDS = ("synthetic", "vaihingen_dir", "scene_dir")
+AUGMENT_MODES = ("none", "flip", "d4")
 
 
 @dataclass
@@ -56,7 +57,8 @@ class ModelConfig:
 class TrainConfig:
     model: ModelConfig = field(default_factory=ModelConfig)
     # ---- data ----------------------------------------------------------------
-    data: str = "synthetic"              # synthetic | vaihingen_dir
+    data: str = "synthetic"              # synthetic | vaihingen_dir (pre-cut tiles of one size)
+                                         # | scene_dir (images of any size: random crops)
     data_dir: Optional[str] = None       # directory of image + .npy label pairs (ref.py:660-674)
     tile: int = 256                      # H = W (D too for dims=3); reference: 512 (ref.py:737)
     num_samples: int = 127               # synthetic dataset length (ref.py:750: 127 tiles/epoch)
@@ -65,6 +67,12 @@ class TrainConfig:
     shuffle: bool = True
     data_on_device: bool = True          # GPU: render / keep the dataset in HBM (K20)
     data_hbm_gb: Optional[float] = None  # HBM budget for a real dataset (None: half the free)
+    # augmented random crops, cut on the device (data/scenes.py; 2-D): always for scene_dir,
+    # for vaihingen_dir when augment or a jitter is set (each tile = a tile-sized scene)
+    crops_per_epoch: int = 0             # 0 = total scene area / tile^2, rounded up
+    augment: str = "none"                # none | flip (the 4 mirrorings) | d4 (+ transposes)
+    gain_jitter: float = 0.0             # per-sample gain 1 +- this (uniform) and bias +- this,
+    bias_jitter: float = 0.0             # x = clamp(x * gain + bias, 0, 1)
     # ---- optimisation ----------------------------------------------------------
     batch_per_gpu: int = 1               # batch_size, ref.py:686
     accum_steps: int = 1                 # frequency_sending_gradients, ref.py:685
@@ -142,6 +150,7 @@ class TrainConfig:
                                    ("wire_dtype", self.wire_dtype, ("fp32", "bf16")),
                                    ("bucket_plan", self.bucket_plan, ("readiness", "size")),
                                    ("data", self.data, DATA_KINDS),
+                                   ("augment", self.augment, AUGMENT_MODES),
                                    ("impl", self.impl, ("auto", "hip", "torch")),
                                    ("dtype", self.dtype, ("bf16", "fp32"))):
             if val not in allowed:
@@ -154,7 +163,23 @@ class TrainConfig:
                              "'auto' for fp32 compute")
         if self.accum_steps < 1 or self.batch_per_gpu < 1:
             raise ValueError("accum_steps and batch_per_gpu must be >= 1")
+        if self.crops_per_epoch < 0:
+            raise ValueError("crops_per_epoch must be >= 0")
+        for name in ("gain_jitter", "bias_jitter"):
+            if not 0.0 <= getattr(self, name) <= 1.0:
+                raise ValueError(f"{name} must be in [0, 1]")
+        if self.data == "synthetic" and (self.crops_per_epoch or self.augmented):
+            raise ValueError("crops_per_epoch, augment and the colour jitters need data=scene_dir or "
+                             "vaihingen_dir (the synthetic tiles are rendered, not cropped)")
+        if self.model.dims == 3 and (self.data == "scene_dir" or self.crops_per_epoch or self.augmented):
+            raise ValueError("scene_dir, crops_per_epoch, augment and the colour jitters are 2-D only "
+                             "(model.dims == 2)")
         return self
+
+    @property
+    def augmented(self) -> bool:
+        """Batches go through the augmenting crop kernels."""
+        return self.augment != "none" or self.gain_jitter != 0.0 or self.bias_jitter != 0.0
 
     # ---- (de)serialisation ---------------------------------------------------------
     def to_dict(self) -> Dict[str, Any]:

@@ -29,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from ..config import TrainConfig
-from ..data import ShardedSampler, SyntheticTiles, TileDataset
+from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset
 from ..models.unet import UNet
 from ..ops import _ext
 from ..ops.adam import FlatAdam
@@ -256,12 +256,29 @@ class Trainer:
         c = self.cfg
         cuda = self.device.type == "cuda"
         layout = "engine" if self.impl == "hip" else "nchw"
+        if c.data in ("vaihingen_dir", "scene_dir") and not c.data_dir:
+            raise ValueError(f"data={c.data} needs data_dir")
+        budget = None if c.data_hbm_gb is None else int(c.data_hbm_gb * 2**30)
+        if c.data == "scene_dir" or (c.data == "vaihingen_dir" and c.augmented):
+            # random augmented crops cut by the crop_params / crop_gather kernels; the held-out
+            # scenes (tiles) are served un-augmented through the same gather
+            crop = dict(crops_per_epoch=c.crops_per_epoch, augment=c.augment, seed=c.seed,
+                        gain_jitter=c.gain_jitter, bias_jitter=c.bias_jitter, layout=layout)
+            if c.data == "scene_dir":
+                tr, te = SceneCropDataset.from_dir(c.data_dir, c.tile, c.test_holdout, **crop)
+            else:
+                tiles, held = TileDataset.from_dir(c.data_dir, c.test_holdout)
+                crop["crops_per_epoch"] = c.crops_per_epoch or len(tiles)
+                tr = SceneCropDataset.from_tiles(tiles, c.tile, **crop)
+                te = None if held is None else SceneCropDataset.test_grid(
+                    [(x, y) for x, y in zip(held.x.numpy(), held.y.numpy())], c.tile, layout)
+            if cuda and c.data_on_device:
+                tr = tr.to_device(self.device, layout, budget)
+                te = te.to_device(self.device, layout, budget) if te is not None else None
+            return tr, te
         if c.data == "vaihingen_dir":
-            if not c.data_dir:
-                raise ValueError("data=vaihingen_dir needs data_dir")
             tr, te = TileDataset.from_dir(c.data_dir, c.test_holdout)
             if cuda and c.data_on_device:
-                budget = None if c.data_hbm_gb is None else int(c.data_hbm_gb * 2**30)
                 tr = tr.to_device(self.device, layout, budget)
                 te = te.to_device(self.device, layout, budget) if te is not None else None
             return tr, te
@@ -795,6 +812,8 @@ class Trainer:
         prefetch = getattr(self.train_set, "prefetch", None)     # host-streamed datasets
         while self.epoch < c.epochs:
             self.sampler.set_epoch(self.epoch)
+            if hasattr(self.train_set, "set_epoch"):      # random crops: a new stream per epoch
+                self.train_set.set_epoch(self.epoch)
             self.meter.reset()
             t_ep = time.perf_counter()
             pending: List[Tuple[torch.Tensor, torch.Tensor]] = []
