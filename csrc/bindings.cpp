@@ -78,6 +78,17 @@ int pick_bn(int Cout) {
 
 }  // namespace
 
+// ---- what the last conv / convT operator of this thread dispatched to (torch.ops.ddlpc.
+// last_path): "<operator>:<kernel variant>:<decisions that change the code that runs>", e.g.
+// "conv3_fwd:stream:cfg5:ks1", "conv3_wgrad:v3:bco128:ciw1", "convt_fwd:res"; the CPU kernels
+// (cpu_ref.cpp) report "cpu".  Host-side bookkeeping only: tests assert that a shape written
+// for one kernel variant still runs it after the launch heuristics are retuned.
+namespace {
+thread_local std::string g_last_path;
+}  // namespace
+void set_last_path(const std::string& path) { g_last_path = path; }
+std::string last_path() { return g_last_path; }
+
 // ---- A/B switches for experiments in progress: knob(name, def) = an in-process override
 // (torch.ops.ddlpc.set_knob) or else the environment variable DDLPC_<NAME>, or else def.
 // Every name a kernel reads is listed in kKnobs; set_knob rejects any other name, so an A/B
@@ -260,6 +271,7 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
       a.Y1 = bptr_mut(y1);
       a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
       a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
+      set_last_path("conv3_fwd:ds");
       conv3d_ds_launch(a, grid, smem, cur_stream());
       at::Tensor none = at::empty({0}, opts);
       return {y1, y2.defined() ? y2 : none, stats.defined() ? stats : none};
@@ -278,6 +290,8 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
       a.Y1 = bptr_mut(y1);
       a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
       a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
+      set_last_path("conv3_fwd:res:v" + std::to_string(variant) +
+                    (a.Co1 < a.Cout ? ":split" : "") + (a.bnb_y != nullptr ? ":bnb" : ""));
       conv3_res_launch(a, variant, grid, smem, cur_stream());
       at::Tensor none = at::empty({0}, opts);
       return {y1, y2.defined() ? y2 : none, stats.defined() ? stats : none};
@@ -372,6 +386,9 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
   a.Y1 = bptr_mut(y1);
   a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
   a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
+  set_last_path(std::string(g.dims == 3 ? "conv3_fwd:stream3d:cfg" : "conv3_fwd:stream:cfg") +
+                std::to_string(cfg) + ":ks" + std::to_string(a.ksplit) +
+                (a.bnb_y != nullptr ? ":bnb" : ""));
   conv3_fwd_launch(a, cfg, cur_stream());
   if (a.ksplit > 1) conv3_splitk_finalize_launch(a, fin_grid, cur_stream());
   at::Tensor none = at::empty({0}, opts);
@@ -519,6 +536,15 @@ at::Tensor conv3_wgrad(const at::Tensor& dy, const at::Tensor& x1,
   TORCH_CHECK(a.pscale2 == nullptr || v2, "X2 prologue needs the v2/v3 weight-gradient kernels "
               "(2-D or 3-D, W >= 16, C1 % 32 == 0)");
   TORCH_CHECK(a.groups <= 1 || (v3 && !img), "conv3_wgrad groups: the v3 kernel only (W >= 8, C1 % 32 == 0)");
+  {
+    const std::string d3 = g.dims == 3 ? ":3d" : "";
+    if (ds_grid >= 0) set_last_path("conv3_wgrad:ds");
+    else if (c32_grid >= 0) set_last_path(std::string("conv3_wgrad:c32") + (emit ? ":dyout" : ""));
+    else if (img) set_last_path("conv3_wgrad:img" + d3 + (a.dyy != nullptr ? ":dypro" : ""));
+    else if (v3) set_last_path("conv3_wgrad:v3:bco" + std::to_string(bco) + ":ciw" + std::to_string(a.ciw) + d3);
+    else if (v2) set_last_path("conv3_wgrad:v2" + d3 + (a.dyy != nullptr ? ":dypro" : ""));
+    else set_last_path("conv3_wgrad:v1" + d3);
+  }
   if (ds_grid >= 0) conv3d_wgrad_ds_launch(a, ds_grid, cur_stream());
   else if (c32_grid >= 0) conv3_wgrad_c32_launch(a, c32_grid, cur_stream());
   else if (img) conv3_wgrad_img_launch(a, bco, cur_stream());
@@ -573,6 +599,7 @@ std::vector<at::Tensor> conv3_bwd32(const at::Tensor& dy, const at::Tensor& y, c
   at::Tensor bnpart = at::empty({grid, 2, 32}, fopts);
   at::Tensor wpart = at::empty({(int64_t)grid * 32 * 9 * 32}, fopts);
   a.dA = bptr_mut(dA); a.bnpart = bnpart.data_ptr<float>(); a.wpart = wpart.data_ptr<float>();
+  set_last_path(G > 1 ? "conv3_bwd32:groups" : "conv3_bwd32");
   conv3_bwd32_launch(a, grid, cur_stream());
   const bool into = dw_out.has_value() && dw_out->defined();
   if (into) {
@@ -932,7 +959,9 @@ at::Tensor convt_fwd(const at::Tensor& x, const at::Tensor& wt, const c10::optio
   TORCH_CHECK((int64_t)a.M * (g.dims == 2 ? 4 : 8) < (int64_t)INT32_MAX, "convT: too many pixels for 32-bit pixel indices");
   at::Tensor out = at::empty(shape_with_c(g, (int)cout, 2), x.options());
   a.C = out.data_ptr();
-  if (!convt_res_launch(a, num_cus(), cur_stream())) gemm_launch(a, cur_stream());
+  const bool res = convt_res_launch(a, num_cus(), cur_stream());
+  if (!res) gemm_launch(a, cur_stream());
+  set_last_path(res ? "convt_fwd:res" : "convt_fwd:gemm");
   return out;
 }
 
@@ -975,7 +1004,9 @@ std::vector<at::Tensor> convt_dgrad(const at::Tensor& dout, const at::Tensor& wd
     bnpart = at::empty({(int64_t)grid, 2, (int64_t)cin}, dout.options().dtype(at::kFloat));
     a.bnpart = bnpart.data_ptr<float>();
   }
-  if (res_rows == 0 || !convt_res_launch(a, num_cus(), cur_stream())) gemm_launch(a, cur_stream());
+  const bool res = res_rows != 0 && convt_res_launch(a, num_cus(), cur_stream());
+  if (!res) gemm_launch(a, cur_stream());
+  set_last_path(res ? "convt_dgrad:res" : "convt_dgrad:gemm");
   return {dx, bnpart};
 }
 
@@ -1043,6 +1074,7 @@ std::vector<at::Tensor> convt_bwd_fused(const at::Tensor& x, const at::Tensor& d
     const bool has_bn = bn4.has_value() && bn4->defined();
     auto r = convt_dgrad(dout, wd, x.size(3), has_bn ? c10::optional<at::Tensor>(x) : c10::nullopt, bn4);
     auto w = convt_wgrad(x, dout, dw_out, db_out, colsum_rows, bn4);
+    set_last_path("convt_bwd_fused:separate");
     return {r[0], r[1], w[0], w[1]};
   }
   TORCH_CHECK(wd.numel() == 64 * 256, "convt_bwd_fused: packed dgrad weights must be [64][256]");
@@ -1065,6 +1097,7 @@ std::vector<at::Tensor> convt_bwd_fused(const at::Tensor& x, const at::Tensor& d
   a.partial = part.data_ptr<float>();
   at::Tensor bnpart = at::empty({a.bn4 != nullptr ? (int64_t)a.splits : 0, 2, 64}, fopts);
   if (a.bn4 != nullptr) a.bnpart = bnpart.data_ptr<float>();
+  set_last_path("convt_bwd_fused:fused");
   convt_bwd_fused_launch(a, cur_stream());
   at::Tensor dW = into ? *dw_out : at::empty({64, 64, 2, 2}, fopts);
   const long long NW = 64LL * 256;
@@ -1120,6 +1153,7 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
   auto fopts = x.options().dtype(at::kFloat);
   at::Tensor part = at::empty({(int64_t)splits * a.M * a.N}, fopts);
   a.partial = part.data_ptr<float>();
+  set_last_path(a.wg2 ? "convt_wgrad:wg2" : "convt_wgrad:wg1");
   gemm_launch(a, cur_stream());
   std::vector<int64_t> ws = {g.C, go.C, 2, 2};
   if (g.dims == 3) ws.push_back(2);
@@ -1745,6 +1779,7 @@ void comm_proxy(const at::Tensor& g, int64_t blocks, int64_t passes) {
 TORCH_LIBRARY(ddlpc, m) {
   m.def("set_cu_reserve(int k) -> int", &ddlpc::set_cu_reserve);
   m.def("set_knob(str name, int value) -> int", &ddlpc::set_knob);
+  m.def("last_path() -> str", &ddlpc::last_path);
   m.def("comm_proxy(Tensor(a!) g, int blocks, int passes) -> ()");
   m.def("conv3_fwd(Tensor x1, Tensor? x2, Tensor w, Tensor? bias, Tensor? pscale, Tensor? pshift, "
         "int cout, int co1, bool stats, Tensor? pscale2=None, Tensor? pshift2=None, Tensor? bnb_y=None, "

@@ -20,7 +20,12 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
+
+namespace ddlpc {
+void set_last_path(const std::string& path);    // bindings.cpp: torch.ops.ddlpc.last_path
+}
 
 namespace ddlpc_cpu {
 
@@ -221,6 +226,7 @@ std::vector<Tensor> conv3_fwd(const Tensor& x1, const optional<Tensor>& x2, cons
                               const optional<Tensor>& pshift, int64_t cout, int64_t co1, bool want_stats,
                               const optional<Tensor>& pscale2, const optional<Tensor>& pshift2,
                               const optional<Tensor>& bnb_y, const optional<Tensor>& bnb_s4, int64_t groups) {
+  ddlpc::set_last_path("cpu");
   const int dims = sdims(x1);
   const int64_t G = groups > 1 ? groups : 1;
   TORCH_CHECK(x1.size(0) % G == 0, "conv3_fwd: groups must divide the batch");
@@ -247,6 +253,7 @@ Tensor conv3_wgrad(const Tensor& dy, const Tensor& x1, const optional<Tensor>& x
                    const optional<Tensor>& pshift2, const optional<Tensor>& dy_y,
                    const optional<Tensor>& dy_s4, const optional<Tensor>& dy_coefs, int64_t cin_real,
                    int64_t groups, const optional<Tensor>& dy_out) {
+  ddlpc::set_last_path("cpu");
   (void)cin_real;                       // (the GPU's image-layer kernel choice; same result)
   const int dims = sdims(x1);
   const int64_t G = groups > 1 ? groups : 1;
@@ -272,6 +279,7 @@ Tensor conv3_wgrad(const Tensor& dy, const Tensor& x1, const optional<Tensor>& x
 
 std::vector<Tensor> conv3_bwd32(const Tensor& dy, const Tensor& y, const Tensor& s4, const Tensor& wd,
                                 const optional<Tensor>& dw_out, int64_t groups) {
+  ddlpc::set_last_path("cpu");
   const int64_t G = groups > 1 ? groups : 1;
   const int64_t C = y.size(-1);
   const Tensor yf = f32(y);
@@ -516,6 +524,7 @@ Tensor convt_input(const Tensor& x, const optional<Tensor>& bn4) {
 
 Tensor convt_fwd(const Tensor& x, const Tensor& wt, const optional<Tensor>& bias, int64_t cout,
                  const optional<Tensor>& bn4) {
+  ddlpc::set_last_path("cpu");
   const int64_t C = x.size(-1);
   const Tensor xin = convt_input(x, bn4).reshape({-1, C});
   const Tensor cols = at::matmul(xin, f32(wt).reshape({-1, C}).t());
@@ -526,6 +535,7 @@ Tensor convt_fwd(const Tensor& x, const Tensor& wt, const optional<Tensor>& bias
 
 std::vector<Tensor> convt_dgrad(const Tensor& dout, const Tensor& wd, int64_t cin, const optional<Tensor>& bny,
                                 const optional<Tensor>& bn4) {
+  ddlpc::set_last_path("cpu");
   const Tensor cols = shuffle_down(f32(dout));
   std::vector<int64_t> xs = dout.sizes().vec();
   for (size_t i = 1; i + 1 < xs.size(); ++i) xs[i] /= 2;
@@ -547,6 +557,7 @@ Tensor convt_bias(const Tensor& dout, const optional<Tensor>& colsum_rows) {
 std::vector<Tensor> convt_wgrad(const Tensor& x, const Tensor& dout, const optional<Tensor>& dw_out,
                                 const optional<Tensor>& db_out, const optional<Tensor>& colsum_rows,
                                 const optional<Tensor>& bn4) {
+  ddlpc::set_last_path("cpu");
   const int dims = sdims(x);
   const int64_t C = x.size(-1), co = dout.size(-1), S = dims == 2 ? 4 : 8;
   const Tensor xin = convt_input(x, bn4).reshape({-1, C});
@@ -566,6 +577,7 @@ std::vector<Tensor> convt_wgrad(const Tensor& x, const Tensor& dout, const optio
 std::vector<Tensor> convt_bwd_fused(const Tensor& x, const Tensor& dout, const Tensor& wd,
                                     const optional<Tensor>& dw_out, const optional<Tensor>& db_out,
                                     const optional<Tensor>& colsum_rows, const optional<Tensor>& bn4) {
+  ddlpc::set_last_path("cpu");
   auto r = convt_dgrad(dout, wd, x.size(-1), has(bn4) ? optional<Tensor>(x) : c10::nullopt, bn4);
   auto w = convt_wgrad(x, dout, dw_out, db_out, colsum_rows, bn4);
   return {r[0], r[1], w[0], w[1]};

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <string>
 
 #include "common.h"
 
@@ -379,6 +380,11 @@ void bn_running_apply_all_launch(const int64_t* entries, int L, int maxC, const 
 // same-process A/B runs) or else the environment variable DDLPC_NAME, or else def — for
 // experiments in progress, and for a rejected path kept measurable (CROP_LDS_T, data.hip)
 int knob(const char* name, int def);
+
+// ---------------------------------------------------------------- dispatch report (bindings.cpp)
+// the kernel variant the calling thread's last conv / convT operator dispatched to
+// (torch.ops.ddlpc.last_path; the CPU kernels report "cpu")
+void set_last_path(const std::string& path);
 
 // ---------------------------------------------------------------- comm proxy (reduce.hip)
 void comm_proxy_launch(float* g, long long n, int blocks, int passes, hipStream_t st);

@@ -251,12 +251,13 @@ def test_bn_window_on_cpu_matches_micro_batches():
 def test_every_operator_has_cpu_and_gpu_kernels():
     """One op namespace, two kernels: every ``ddlpc::`` tensor operator registers a CUDA
     (gfx950) and a CPU kernel.  Exceptions: ``comm_proxy`` (a single-GPU stand-in for an RCCL
-    collective) and the two host-only planner settings (``set_cu_reserve``, ``set_knob``)."""
+    collective) and the host-only planner settings and report (``set_cu_reserve``, ``set_knob``,
+    ``last_path``)."""
     from ddlpc.ops import _ext
     _ext.load()
     names = sorted(n for n in torch._C._dispatch_get_all_op_names() if n.startswith("ddlpc::"))
     assert len(names) >= 40
-    host_only = {"ddlpc::set_cu_reserve", "ddlpc::set_knob"}
+    host_only = {"ddlpc::set_cu_reserve", "ddlpc::set_knob", "ddlpc::last_path"}
     for n in names:
         if n in host_only:
             continue
