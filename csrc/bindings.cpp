@@ -78,9 +78,10 @@ int pick_bn(int Cout) {
 
 }  // namespace
 
-// ---- what the last conv / convT operator of this thread dispatched to (torch.ops.ddlpc.
+// ---- what the last conv / convT / head operator of this thread dispatched to (torch.ops.ddlpc.
 // last_path): "<operator>:<kernel variant>:<decisions that change the code that runs>", e.g.
-// "conv3_fwd:stream:cfg5:ks1", "conv3_wgrad:v3:bco128:ciw1", "convt_fwd:res"; the CPU kernels
+// "conv3_fwd:stream:cfg5:ks1", "conv3_wgrad:v3:bco128:ciw1", "convt_fwd:res",
+// "head_ce_bwd:head32:defer:stats"; the CPU kernels
 // (cpu_ref.cpp) report "cpu".  Host-side bookkeeping only: tests assert that a shape written
 // for one kernel variant still runs it after the launch heuristics are retuned.
 namespace {
@@ -1171,6 +1172,10 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
 }
 
 // ------------------------------------------------------------------------ head + CE
+// the kernel family of the head's backward-side launches (head_ce.hip: every C = 32 head with
+// a supported class count runs the MFMA head32 kernels, the other widths the channel-split ones)
+static const char* head_variant(int C) { return C == 32 ? "head32" : "split"; }
+
 at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                        const at::Tensor& labels, int64_t ignore_index,
                        const c10::optional<at::Tensor>& bn4) {
@@ -1188,6 +1193,7 @@ at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
   head_ce_fwd_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                      partial.data_ptr<float>(), out3.data_ptr<float>(), bn4_ptr(bn4, C), nb, P, C, K,
                      (int)ignore_index, cur_stream());
+  set_last_path(std::string("head_ce_fwd:split") + (bn4_ptr(bn4, C) != nullptr ? ":defer" : ""));
   return out3;
 }
 
@@ -1215,6 +1221,8 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
                      fptr_opt(gscale), out3.data_ptr<float>(), 0, store_da ? bptr_mut(dA) : nullptr,
                      part.data_ptr<float>(), nb, P, C, K, (int)ignore_index, pbn,
                      pbn != nullptr ? bnpart.data_ptr<float>() : nullptr, cur_stream());
+  set_last_path(std::string("head_ce_bwd:") + head_variant(C) + (pbn != nullptr ? ":defer" : "") +
+                (store_da ? "" : ":stats"));
   const bool into = dw_out.has_value() && dw_out->defined();
   at::Tensor sums = reduce_rows(part, nb, K * C + K);   // rows are [dW (K*C) | db (K)]
   if (into) {
@@ -1273,8 +1281,9 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
     at::Tensor dY = at::empty_like(a);
     head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                          fptr_opt(gscale), out3.data_ptr<float>(), bn4.data_ptr<float>(),
-                         coefs.data_ptr<float>(), bptr_mut(dY), P, C, K, (int)ignore_index, cur_stream(),
-                         (int)groups);
+                         coefs.data_ptr<float>(), bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(),
+                         cur_stream(), (int)groups);
+    set_last_path("head_ce_bn_bwd:head32:groups");
     return {dY, dgamma, dbeta};
   }
   const float* pbn = bn4_ptr(bn4, C);
@@ -1302,7 +1311,8 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
   at::Tensor dY = at::empty_like(a);
   head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                        fptr_opt(gscale), out3.data_ptr<float>(), pbn, coefs.data_ptr<float>(),
-                       bptr_mut(dY), P, C, K, (int)ignore_index, cur_stream());
+                       bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream());
+  set_last_path(std::string("head_ce_bn_bwd:") + head_variant(C));
   return {dY, dgamma, dbeta};
 }
 
@@ -1342,6 +1352,7 @@ std::vector<at::Tensor> head_ce_fwd_stats(const at::Tensor& a, const at::Tensor&
                            pbn, wrows.data_ptr<float>(), brows.data_ptr<float>(), lrows.data_ptr<float>(),
                            out3.data_ptr<float>(), nb, P, C, K, (int)ignore_index, cur_stream(),
                            groups > 1 ? (int)groups : 1);
+  set_last_path(std::string("head_ce_fwd_stats:") + head_variant(C) + (groups > 1 ? ":groups" : ""));
   return {out3, wrows, brows};
 }
 
@@ -1419,6 +1430,7 @@ at::Tensor head_logits(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
   at::Tensor out = at::empty(os, a.options().dtype(at::kFloat));
   head_logits_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), out.data_ptr<float>(),
                      (long long)g.N * HW, HW, C, K, bn4_ptr(bn4, C), cur_stream());
+  set_last_path(std::string("head_logits") + (bn4_ptr(bn4, C) != nullptr ? ":defer" : ""));
   return out;
 }
 

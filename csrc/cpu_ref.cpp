@@ -598,6 +598,7 @@ struct HeadFwd {
 HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                      int64_t ignore_index, const optional<Tensor>& bn4, int64_t G) {
   const int64_t K = Wh.size(0);
+  ddlpc::set_last_path("cpu");
   HeadFwd h;
   h.A = head_act(a, bn4, G);
   h.logits = at::matmul(h.A, f32(Wh).reshape({K, -1}).t()) + f32(bh).reshape({K});
@@ -674,7 +675,8 @@ std::vector<Tensor> head_ce_fwd_stats(const Tensor& a, const Tensor& Wh, const T
   const int64_t K = Wh.size(0), C = a.size(-1);
   const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G);
   const Tensor dl = head_dlogits(h, 1.0);                   // unit gradient scale
-  const Tensor dAf = rbf(at::matmul(dl, f32(Wh).reshape({K, C}))).reshape(a.sizes());
+  // (the unrounded dA, as the GPU kernels' unit-scale pass: nothing is stored here)
+  const Tensor dAf = at::matmul(dl, f32(Wh).reshape({K, C})).reshape(a.sizes());
   const Tensor wrows = at::cat({at::matmul(dl.t(), h.A).reshape({-1}), dl.sum(0)}).reshape({1, K * C + K});
   return {h.out3, wrows, bnb_rows(dAf, f32(a), bn4, G)};
 }
@@ -705,6 +707,7 @@ void meter_add(Tensor& buf, const Tensor& loss, const Tensor& correct, double pi
 
 Tensor head_logits(const Tensor& a, const Tensor& Wh, const Tensor& bh, const optional<Tensor>& bn4) {
   const int64_t K = Wh.size(0);
+  ddlpc::set_last_path("cpu");
   const Tensor A = head_act(a, bn4, 1);
   const Tensor l = at::matmul(A, f32(Wh).reshape({K, -1}).t()) + f32(bh).reshape({K});
   std::vector<int64_t> s = a.sizes().vec();

@@ -264,9 +264,10 @@ void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const
                         int ignore_index, const float* bn4, float* bnpart, hipStream_t st);
 // two-pass backward with the deferred BatchNorm of the last decoder block: dA == nullptr in
 // head_ce_bwd_launch runs the stats pass (dWh, dbh, BN partials); this second pass
-// recomputes dA and writes that BatchNorm's dY (coefs = [k | m1 | m2] x C)
+// recomputes dA and writes that BatchNorm's dY (coefs = [k | m1 | m2] x C); its C = 32 grid
+// is persistent and sized from num_cus like its siblings'
 // training forward with the deferred BN: loss rows -> out3 (ce_finalize) plus the backward
-// statistics at a unit gradient scale (head_ce_bwd_kernel LOSS variant)
+// statistics at a unit gradient scale (the LOSS variant of head32_kernel / head_ce_bwd_kernel)
 void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
                               const int64_t* labels, const float* bn4, float* dW_partial,
                               float* bnpart, float* loss_partial, float* out3, int nblocks,
@@ -275,7 +276,7 @@ void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
 void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                           const float* gscale, const float* stats3, const float* bn4,
                           const float* coefs, bf16_t* dY, long long P, int C, int K,
-                          int ignore_index, hipStream_t st, int groups = 1);
+                          int ignore_index, int num_cus, hipStream_t st, int groups = 1);
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
 // whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the
@@ -382,7 +383,7 @@ void bn_running_apply_all_launch(const int64_t* entries, int L, int maxC, const 
 int knob(const char* name, int def);
 
 // ---------------------------------------------------------------- dispatch report (bindings.cpp)
-// the kernel variant the calling thread's last conv / convT operator dispatched to
+// the kernel variant the calling thread's last conv / convT / head operator dispatched to
 // (torch.ops.ddlpc.last_path; the CPU kernels report "cpu")
 void set_last_path(const std::string& path);
 
