@@ -1176,9 +1176,22 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
 // a supported class count runs the MFMA head32 kernels, the other widths the channel-split ones)
 static const char* head_variant(int C) { return C == 32 ? "head32" : "split"; }
 
+// class_weight (optional): fp32 [K] on a's device — cross_entropy(weight=): a valid pixel
+// carries w[label], out3[2] is the weight sum of the valid pixels (the count without weights)
+// and loss and gradients are normalised by it; hits stay unweighted; a zero sum gives loss 0
+// and zero gradients (PyTorch: NaN).  The passes of one backward must be given the same tensor.
+static const float* class_weight_ptr(const c10::optional<at::Tensor>& cw, const at::Tensor& a, int K) {
+  if (!cw.has_value() || !cw->defined()) return nullptr;
+  CHECK_F32(*cw); CHECK_CONTIG(*cw);
+  TORCH_CHECK(cw->dim() == 1 && cw->numel() == K && cw->device() == a.device(),
+              "class_weight must be fp32 [K] on the activation's device");
+  return cw->data_ptr<float>();
+}
+
 at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                        const at::Tensor& labels, int64_t ignore_index,
-                       const c10::optional<at::Tensor>& bn4) {
+                       const c10::optional<at::Tensor>& bn4,
+                       const c10::optional<at::Tensor>& class_weight) {
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a); CHECK_F32(Wh); CHECK_CONTIG(Wh);
   TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous(), "labels must be int64");
   c10::DeviceGuard guard(a.device());
@@ -1192,7 +1205,7 @@ at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
   at::Tensor out3 = at::empty({3}, fopts);
   head_ce_fwd_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                      partial.data_ptr<float>(), out3.data_ptr<float>(), bn4_ptr(bn4, C), nb, P, C, K,
-                     (int)ignore_index, cur_stream());
+                     (int)ignore_index, cur_stream(), class_weight_ptr(class_weight, a, K));
   set_last_path(std::string("head_ce_fwd:split") + (bn4_ptr(bn4, C) != nullptr ? ":defer" : ""));
   return out3;
 }
@@ -1202,7 +1215,8 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
                                     const c10::optional<at::Tensor>& gscale, int64_t ignore_index,
                                     const c10::optional<at::Tensor>& dw_out,
                                     const c10::optional<at::Tensor>& db_out,
-                                    const c10::optional<at::Tensor>& bn4, bool store_da) {
+                                    const c10::optional<at::Tensor>& bn4, bool store_da,
+                                    const c10::optional<at::Tensor>& class_weight) {
   CHECK_DEV(a); CHECK_CONTIG(a);
   c10::DeviceGuard guard(a.device());
   const int C = (int)a.size(-1), K = (int)Wh.size(0);
@@ -1220,7 +1234,8 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
   head_ce_bwd_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                      fptr_opt(gscale), out3.data_ptr<float>(), 0, store_da ? bptr_mut(dA) : nullptr,
                      part.data_ptr<float>(), nb, P, C, K, (int)ignore_index, pbn,
-                     pbn != nullptr ? bnpart.data_ptr<float>() : nullptr, cur_stream());
+                     pbn != nullptr ? bnpart.data_ptr<float>() : nullptr, cur_stream(),
+                     class_weight_ptr(class_weight, a, K));
   set_last_path(std::string("head_ce_bwd:") + head_variant(C) + (pbn != nullptr ? ":defer" : "") +
                 (store_da ? "" : ":stats"));
   const bool into = dw_out.has_value() && dw_out->defined();
@@ -1252,12 +1267,14 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
                                        const at::Tensor& gamma,
                                        const c10::optional<at::Tensor>& dgamma_out,
                                        const c10::optional<at::Tensor>& dbeta_out,
-                                       const c10::optional<at::Tensor>& pscale, int64_t groups) {
+                                       const c10::optional<at::Tensor>& pscale, int64_t groups,
+                                       const c10::optional<at::Tensor>& class_weight) {
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
   // pscale: device factor on the partial rows (rows from the fused forward at unit scale)
   const float* ps = fptr_opt(pscale);
   c10::DeviceGuard guard(a.device());
   const int C = (int)a.size(-1), K = (int)Wh.size(0);
+  const float* pcw = class_weight_ptr(class_weight, a, K);
   if (groups > 1) {
     // BN groups (a batched window): bn4 [groups][4][C], partial rows group-major (the fused
     // forward's head_ce_fwd_stats with groups), per-group coefficients
@@ -1282,7 +1299,7 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
     head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                          fptr_opt(gscale), out3.data_ptr<float>(), bn4.data_ptr<float>(),
                          coefs.data_ptr<float>(), bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(),
-                         cur_stream(), (int)groups);
+                         cur_stream(), (int)groups, pcw);
     set_last_path("head_ce_bn_bwd:head32:groups");
     return {dY, dgamma, dbeta};
   }
@@ -1311,7 +1328,7 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
   at::Tensor dY = at::empty_like(a);
   head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                        fptr_opt(gscale), out3.data_ptr<float>(), pbn, coefs.data_ptr<float>(),
-                       bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream());
+                       bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream(), 1, pcw);
   set_last_path(std::string("head_ce_bn_bwd:") + head_variant(C));
   return {dY, dgamma, dbeta};
 }
@@ -1323,7 +1340,8 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
 std::vector<at::Tensor> head_ce_fwd_stats(const at::Tensor& a, const at::Tensor& Wh,
                                           const at::Tensor& bh, const at::Tensor& labels,
                                           int64_t ignore_index, const at::Tensor& bn4,
-                                          int64_t groups) {
+                                          int64_t groups,
+                                          const c10::optional<at::Tensor>& class_weight) {
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a); CHECK_CONTIG(labels);
   TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
   c10::DeviceGuard guard(a.device());
@@ -1351,7 +1369,7 @@ std::vector<at::Tensor> head_ce_fwd_stats(const at::Tensor& a, const at::Tensor&
   head_ce_fwd_stats_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                            pbn, wrows.data_ptr<float>(), brows.data_ptr<float>(), lrows.data_ptr<float>(),
                            out3.data_ptr<float>(), nb, P, C, K, (int)ignore_index, cur_stream(),
-                           groups > 1 ? (int)groups : 1);
+                           groups > 1 ? (int)groups : 1, class_weight_ptr(class_weight, a, K));
   set_last_path(std::string("head_ce_fwd_stats:") + head_variant(C) + (groups > 1 ? ":groups" : ""));
   return {out3, wrows, brows};
 }
@@ -1824,15 +1842,17 @@ TORCH_LIBRARY(ddlpc, m) {
         "Tensor? colsum_rows=None, Tensor? bn4=None) -> Tensor[]");
   m.def("convt_bwd_fused(Tensor x, Tensor dout, Tensor wd, Tensor(a!)? dw_out=None, "
         "Tensor(b!)? db_out=None, Tensor? colsum_rows=None, Tensor? bn4=None) -> Tensor[]");
-  m.def("head_ce_fwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, Tensor? bn4=None) -> Tensor");
+  m.def("head_ce_fwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, Tensor? bn4=None, "
+        "Tensor? class_weight=None) -> Tensor");
   m.def("head_ce_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
         "int ignore_index, Tensor(a!)? dw_out=None, Tensor(b!)? db_out=None, Tensor? bn4=None, "
-        "bool store_da=True) -> Tensor[]");
+        "bool store_da=True, Tensor? class_weight=None) -> Tensor[]");
   m.def("head_ce_bn_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
         "int ignore_index, Tensor bn4, Tensor partial, Tensor gamma, Tensor(a!)? dgamma_out=None, "
-        "Tensor(b!)? dbeta_out=None, Tensor? pscale=None, int groups=0) -> Tensor[]");
+        "Tensor(b!)? dbeta_out=None, Tensor? pscale=None, int groups=0, "
+        "Tensor? class_weight=None) -> Tensor[]");
   m.def("head_ce_fwd_stats(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, "
-        "Tensor bn4, int groups=0) -> Tensor[]");
+        "Tensor bn4, int groups=0, Tensor? class_weight=None) -> Tensor[]");
   m.def("head_wgrad_from_rows(Tensor rows, Tensor scale, int K, int C, Tensor(a!)? dw_out=None, "
         "Tensor(b!)? db_out=None) -> Tensor[]");
   m.def("meter_add(Tensor(a!) buf, Tensor loss, Tensor correct, float pixels, float count=1.) -> ()");

@@ -592,11 +592,15 @@ Tensor head_act(const Tensor& a, const optional<Tensor>& bn4, int64_t G) {
   return bn_act(f32(a), s4row(*bn4, G, C, 2), s4row(*bn4, G, C, 3), G).reshape({-1, C});
 }
 
+// class weights (cross_entropy(weight=)): pw = w[label] per valid pixel — 0 for a label
+// outside [0, K) — multiplies the pixel's loss term and dlogits, and sum pw replaces the
+// valid-pixel count (out3[2]); hits stay unweighted.  Without weights nothing is multiplied.
 struct HeadFwd {
-  Tensor A, logits, valid, lab, out3;
+  Tensor A, logits, valid, lab, out3, pw;
 };
 HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
-                     int64_t ignore_index, const optional<Tensor>& bn4, int64_t G) {
+                     int64_t ignore_index, const optional<Tensor>& bn4, int64_t G,
+                     const optional<Tensor>& cw = c10::nullopt) {
   const int64_t K = Wh.size(0);
   ddlpc::set_last_path("cpu");
   HeadFwd h;
@@ -607,8 +611,19 @@ HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const 
   h.lab = at::where(h.valid, lab, at::zeros_like(lab));
   const Tensor lse = at::logsumexp(h.logits, 1);
   const Tensor picked = h.logits.gather(1, h.lab.unsqueeze(1)).squeeze(1);
-  const Tensor ce = at::where(h.valid, lse - picked, at::zeros_like(lse)).to(at::kDouble);
-  const double count = h.valid.sum().item<double>();
+  Tensor ce = at::where(h.valid, lse - picked, at::zeros_like(lse)).to(at::kDouble);
+  double count = h.valid.sum().item<double>();
+  if (has(cw)) {
+    TORCH_CHECK(cw->scalar_type() == at::kFloat && cw->dim() == 1 && cw->numel() == K,
+                "class_weight must be fp32 [K] on the activation's device");
+    // (the table is indexed by in-range labels only; h.lab is already 0 on ignored pixels)
+    const Tensor in = h.valid & (lab >= 0) & (lab < K);
+    const Tensor idx = at::where(in, lab, at::zeros_like(lab));
+    h.pw = at::where(in, cw->index_select(0, idx), at::zeros_like(lse));
+    h.lab = idx;
+    ce = at::where(in, (lse - picked) * h.pw, at::zeros_like(lse)).to(at::kDouble);
+    count = h.pw.to(at::kDouble).sum().item<double>();
+  }
   const double correct = (h.logits.argmax(1) == lab).sum().item<double>();
   const double loss = count > 0 ? ce.sum().item<double>() / count : 0.0;
   h.out3 = at::tensor({(float)loss, (float)correct, (float)count}, a.options().dtype(at::kFloat));
@@ -618,6 +633,8 @@ HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const 
 Tensor head_dlogits(const HeadFwd& h, double scale) {
   Tensor p = at::softmax(h.logits, 1);
   p = p - at::one_hot(h.lab, h.logits.size(1)).to(at::kFloat);
+  if (h.pw.defined())     // (softmax - onehot) * (scale * w): the GPU kernels' operand order
+    return at::where(h.valid.unsqueeze(1), p * (h.pw * scale).unsqueeze(1), at::zeros_like(p));
   return at::where(h.valid.unsqueeze(1), p * scale, at::zeros_like(p));
 }
 double head_scale(const Tensor& out3, const optional<Tensor>& gs) {
@@ -627,17 +644,18 @@ double head_scale(const Tensor& out3, const optional<Tensor>& gs) {
 void add_into(const optional<Tensor>& dst, const Tensor& v) { add_to(*dst, v); }
 
 Tensor head_ce_fwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
-                   int64_t ignore_index, const optional<Tensor>& bn4) {
-  return head_forward(a, Wh, bh, labels, ignore_index, bn4, 1).out3;
+                   int64_t ignore_index, const optional<Tensor>& bn4, const optional<Tensor>& class_weight) {
+  return head_forward(a, Wh, bh, labels, ignore_index, bn4, 1, class_weight).out3;
 }
 
 std::vector<Tensor> head_ce_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                                 const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
                                 const optional<Tensor>& dw_out, const optional<Tensor>& db_out,
-                                const optional<Tensor>& bn4, bool store_da) {
+                                const optional<Tensor>& bn4, bool store_da,
+                                const optional<Tensor>& class_weight) {
   TORCH_CHECK(store_da || has(bn4), "head_ce_bwd: store_da=False needs the deferred BN (bn4)");
   const int64_t K = Wh.size(0), C = a.size(-1);
-  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, 1);
+  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, 1, class_weight);
   const Tensor dl = head_dlogits(h, head_scale(out3, gscale));
   const Tensor dAf = at::matmul(dl, f32(Wh).reshape({K, C}));
   const Tensor dA = store_da ? bf(dAf.reshape(a.sizes())) : at::empty({0}, a.options());
@@ -655,10 +673,11 @@ std::vector<Tensor> head_ce_bn_bwd(const Tensor& a, const Tensor& Wh, const Tens
                                    const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
                                    const Tensor& bn4, const Tensor& partial, const Tensor& gamma,
                                    const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
-                                   const optional<Tensor>& pscale, int64_t groups) {
+                                   const optional<Tensor>& pscale, int64_t groups,
+                                   const optional<Tensor>& class_weight) {
   const int64_t G = groups > 1 ? groups : 1;
   const int64_t K = Wh.size(0), C = a.size(-1);
-  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G);
+  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G, class_weight);
   const Tensor dl = head_dlogits(h, head_scale(out3, gscale));
   const Tensor dAf = rbf(at::matmul(dl, f32(Wh).reshape({K, C}))).reshape(a.sizes());
   const BnBwd t = bn_terms(dAf, f32(a), bn4, G, 1.0);
@@ -670,10 +689,11 @@ std::vector<Tensor> head_ce_bn_bwd(const Tensor& a, const Tensor& Wh, const Tens
 }
 
 std::vector<Tensor> head_ce_fwd_stats(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
-                                      int64_t ignore_index, const Tensor& bn4, int64_t groups) {
+                                      int64_t ignore_index, const Tensor& bn4, int64_t groups,
+                                      const optional<Tensor>& class_weight) {
   const int64_t G = groups > 1 ? groups : 1;
   const int64_t K = Wh.size(0), C = a.size(-1);
-  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G);
+  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G, class_weight);
   const Tensor dl = head_dlogits(h, 1.0);                   // unit gradient scale
   // (the unrounded dA, as the GPU kernels' unit-scale pass: nothing is stored here)
   const Tensor dAf = at::matmul(dl, f32(Wh).reshape({K, C})).reshape(a.sizes());

@@ -14,6 +14,14 @@
 // dA store) and head_bn_apply_kernel, which recomputes dA and writes the BN's dY directly —
 // y + labels are read twice, but dA never round-trips through HBM and the separate BN-apply
 // pass over (dA, y) disappears (256^2 x 128: 5.1 -> 3.2 tensor-sized HBM transfers).
+//
+// Class weights (cross_entropy(weight=w), optional): a valid pixel carries w[label] into its
+// loss term and into dlogits, and wherever the unweighted code uses the valid-pixel count it
+// uses sum w[label] instead (out3[2]; ce_finalize and the gradient scale keep their
+// arithmetic).  Hits stay unweighted.  The K weights sit in LDS; a label indexes the table only
+// after it was found inside it (class_w).  Without weights every factor is exactly 1: the
+// channel-split kernels then multiply by a table of ones, the C = 32 kernels are instantiated
+// without the factor (WT = false) — the same bits either way.
 #include "common.h"
 #include "ops.h"
 
@@ -58,6 +66,23 @@ DDLPC_DEVICE void load_head(const float* Wh, const float* bh, int K, float* sW, 
   if (threadIdx.x < KP) sb[threadIdx.x] = (int)threadIdx.x < K ? bh[threadIdx.x] : -INFINITY;
 }
 
+// stage the class weights as KP slots: w[k] and 0 in the padded slots; all ones without weights
+template <int KP>
+DDLPC_DEVICE void load_cw(const float* cw, int K, float* scw) {
+  if (threadIdx.x < KP)
+    scw[threadIdx.x] = cw == nullptr ? 1.f : ((int)threadIdx.x < K ? cw[threadIdx.x] : 0.f);
+}
+
+// the weight of a label.  Only a label inside the table indexes it: an ignored label (-100,
+// 255, ...) or any other value outside [0, KP) selects slot 0 BEFORE the read and takes `wout`
+// (0 with weights; 1 without, where such a pixel counts as it always did)
+template <int KP, typename L>
+DDLPC_DEVICE float class_w(const float* scw, L lab, float wout) {
+  const bool in = lab >= 0 && lab < KP;
+  const float w = scw[in ? (int)lab : 0];
+  return in ? w : wout;
+}
+
 // stage != nullptr: also store the (bf16) activation row to LDS for the weight-gradient pass
 template <int C, int K, bool DEFER>
 DDLPC_DEVICE void logits_of(const bf16_t* ap, const float* sW, const float* sb, const float* sBN,
@@ -93,10 +118,12 @@ template <int C, int K, bool DEFER>
 __global__ __launch_bounds__(256) void head_ce_fwd_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, float* __restrict__ partial, long long P,
-    int ignore_index, const float* __restrict__ bn4, int Kreal) {
+    int ignore_index, const float* __restrict__ bn4, int Kreal, const float* __restrict__ cw) {
   __shared__ __attribute__((aligned(16))) float sBNm[4 * C];
-  __shared__ float sW[K * C], sb[K];
+  __shared__ float sW[K * C], sb[K], scw[K];
   load_head<C, K>(Wh, bh, Kreal, sW, sb);
+  load_cw<K>(cw, Kreal, scw);
+  const float wout = cw != nullptr ? 0.f : 1.f;
   const float* sBN = DEFER ? load_bn<C>(bn4, sBNm, false) : nullptr;
   __syncthreads();
   float loss = 0.f, correct = 0.f, count = 0.f;
@@ -117,9 +144,10 @@ __global__ __launch_bounds__(256) void head_ce_fwd_kernel(
     float zy = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) zy = (k == y) ? z[k] : zy;
+    const float wy = class_w<K>(scw, y, wout);
     if (y != ignore_index) {
-      loss += lse - zy;
-      count += 1.f;
+      loss += (lse - zy) * wy;
+      count += wy;
     }
     correct += (am == y) ? 1.f : 0.f;
   }
@@ -137,7 +165,8 @@ __global__ __launch_bounds__(256) void head_ce_fwd_kernel(
   }
 }
 
-// out[0] = sum loss / count, out[1] = correct, out[2] = count
+// out[0] = sum loss / count, out[1] = correct, out[2] = count (with class weights: the sum of
+// the valid pixels' weights, and the loss terms carry them)
 __global__ void ce_finalize_kernel(const float* __restrict__ partial, int nb, float* out) {
   double s[3] = {0, 0, 0};
   for (int i = threadIdx.x; i < nb; i += blockDim.x)
@@ -267,7 +296,7 @@ __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, bf16_t* __restrict__ dA, float* __restrict__ dWp,
     long long P, int ignore_index, const float* __restrict__ bn4, float* __restrict__ bnpart,
-    int Kreal, float* __restrict__ lossp = nullptr) {
+    int Kreal, float* __restrict__ lossp, const float* __restrict__ cw) {
   static_assert(STORE || DEFER, "the stats-only pass exists for the deferred BatchNorm");
   static_assert(!LOSS || (DEFER && !STORE), "the fused forward is the deferred stats pass");
   constexpr int G = C / 8;                          // lanes per pixel
@@ -277,9 +306,12 @@ __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
   __shared__ float sred[4][G][NACC];
   __shared__ __attribute__((aligned(16))) float sW[K * C];      // Wh, padded classes zero
   __shared__ __attribute__((aligned(16))) float sXh[2 * C];     // invstd | -mean*invstd
+  __shared__ float scw[K];                                       // class weights (ones without)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cg = lane % G, c8 = cg * 8;
   for (int i = tid; i < K * C; i += 256) sW[i] = i < Kreal * C ? Wh[i] : 0.f;
+  load_cw<K>(cw, Kreal, scw);
+  const float wout = cw != nullptr ? 0.f : 1.f;
   if (DEFER)
     for (int i = tid; i < C; i += 256) { sXh[i] = bn4[C + i]; sXh[C + i] = -bn4[i] * bn4[C + i]; }
   // registers: bias (padded classes -inf) and the deferred BN's scale / shift (the ReLU
@@ -324,11 +356,12 @@ __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
     float y8[8], f[8], d[K], o8[8], lse, zy;
     int am;
     uint4 pk;
-    head_pixel_x<C, K, DEFER>(a_cur, lab, sW + opaque_zero() + c8, bk, sc, sh, gs, ignore_index,
+    const float wy = class_w<K>(scw, lab, wout);     // (x 1 without weights: the same bits)
+    head_pixel_x<C, K, DEFER>(a_cur, lab, sW + opaque_zero() + c8, bk, sc, sh, gs * wy, ignore_index,
                               y8, f, d, pk, o8, lse, zy, am);
     if (STORE) *reinterpret_cast<uint4*>(dA + px * C + c8) = pk;
     if (LOSS && cg == 0) {
-      if (lab != ignore_index) { acc[LA] += lse - zy; acc[LA + 2] += 1.f; }
+      if (lab != ignore_index) { acc[LA] += (lse - zy) * wy; acc[LA + 2] += wy; }
       acc[LA + 1] += am == lab ? 1.f : 0.f;
     }
     {
@@ -420,14 +453,17 @@ __global__ __launch_bounds__(256) void head_bn_apply_kernel(
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, const float* __restrict__ bn4,
     const float* __restrict__ coefs, bf16_t* __restrict__ dY, long long P, int ignore_index,
-    int Kreal) {
+    int Kreal, const float* __restrict__ cw) {
   constexpr int G = C / 8;
   constexpr int PPB = 256 / G;
   constexpr int U = 4;                               // pixels per lane in flight
   __shared__ __attribute__((aligned(16))) float sW[K * C];
+  __shared__ float scw[K];                           // class weights (ones without)
   const int tid = threadIdx.x, lane = tid & 63;
   const int cg = lane % G, c8 = cg * 8;
   for (int i = tid; i < K * C; i += 256) sW[i] = i < Kreal * C ? Wh[i] : 0.f;
+  load_cw<K>(cw, Kreal, scw);
+  const float wout = cw != nullptr ? 0.f : 1.f;
   float bk[K], sc[8], sh[8], is[8], nm[8], k1[8], m1[8], m2[8];
 #pragma unroll
   for (int k = 0; k < K; ++k) bk[k] = k < Kreal ? bh[k] : -INFINITY;
@@ -458,8 +494,9 @@ __global__ __launch_bounds__(256) void head_bn_apply_kernel(
       if (px >= P) break;                            // uniform over the G lanes of a pixel
       float y8[8], f[8], d[K];
       uint4 pk;
-      head_pixel<C, K, true>(av[r], lab[r], sW + opaque_zero() + c8, bk, sc, sh, gs,
-                             ignore_index, y8, f, d, pk);
+      // (the same gs * w as the stats pass: dA is recomputed bit for bit)
+      head_pixel<C, K, true>(av[r], lab[r], sW + opaque_zero() + c8, bk, sc, sh,
+                             gs * class_w<K>(scw, lab[r], wout), ignore_index, y8, f, d, pk);
       float rr[8], o[8];
       unpack8(pk, rr);
 #pragma unroll
@@ -566,8 +603,12 @@ DDLPC_DEVICE Head32W head32_weights(const float* __restrict__ Wh, const float* _
 // its label and validity -> the activation f (BN + ReLU when DEFER, bf16-rounded), the 4
 // dlogits d (classes 4g..4g+3, scaled by gs; zero for ignored / tail pixels), dA before
 // rounding (o8, the lane's 8 channels) and rounded (pk); LOSS extras: lse, the label's
-// logit, the arg-max class (valid on every lane of the pixel)
-template <bool DEFER, bool LOSS>
+// logit, the arg-max class (valid on every lane of the pixel).  gs carries the pixel's class
+// weight when there are weights.  WT only keeps the weighted kernels' instantiation apart: this
+// function is internal, and the unweighted fused forward passes the constant gs = 1, which the
+// compiler propagates into an instantiation whose every caller does (measured: with a shared
+// instantiation that kernel came out 22 instructions longer and 2.7 % slower)
+template <bool DEFER, bool LOSS, bool WT>
 DDLPC_DEVICE void head32_step(const uint4 yv, const int lab, const bool valid, const Head32W* __restrict__ wl,
                               const float (&sc)[8], const float (&sh)[8], float gs, int ignore_index,
                               int g, float (&y8)[8], uint4& fb, float (&d)[4], uint2& bh2, uint2& bl2,
@@ -656,14 +697,16 @@ struct Head32Ld {
 // The C = 32 counterpart of head_ce_bwd_kernel<32, K, DEFER, STORE, LOSS> (same outputs, same
 // row layouts): stats of the backward (dWh, dbh; with DEFER the deferred BatchNorm's backward
 // partials), the dA store (STORE), and with LOSS the training forward's loss / hits / count at
-// a unit gradient scale.
-template <bool DEFER, bool STORE, bool LOSS>
+// a unit gradient scale.  WT: class weights (cw [K], staged as 16 slots, the padded ones 0) —
+// the pixel's weight multiplies gs (hence every dlogit) and the loss / count terms.
+template <bool DEFER, bool STORE, bool LOSS, bool WT>
 __global__ __launch_bounds__(256, 4) void head32_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, bf16_t* __restrict__ dA, float* __restrict__ dWp,
     long long P, int ignore_index, const float* __restrict__ bn4, float* __restrict__ bnpart,
-    int Kreal, float* __restrict__ lossp, int groups, long long gsteps) {
+    int Kreal, float* __restrict__ lossp, int groups, long long gsteps,
+    const float* __restrict__ cw) {
   static_assert(!LOSS || (DEFER && !STORE), "the fused forward is the deferred stats pass");
   constexpr int C = 32;
   // BN groups (a batched window, groups > 1): the deferred BatchNorm has per-group statistics
@@ -679,9 +722,11 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
   __shared__ float sred[4][4][24];                 // [wave][row g][db 4 | bn 16 | loss 3]
   __shared__ __attribute__((aligned(16))) float sK[4][C];   // scale | shift | invstd | -mean*invstd
   __shared__ Head32W sW[64];                       // the lanes' constant MFMA operands
+  __shared__ float sCW[MAXK];                      // class weights (WT)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: scalar step indices)
   const int n = lane & 15, g = lane >> 4;
   if (tid < 64) sW[tid] = head32_weights(Wh, bh, Kreal, lane);
+  if (WT) load_cw<MAXK>(cw, Kreal, sCW);
   if (DEFER && tid < C) {
     sK[0][tid] = bn4[2 * C + tid];
     sK[1][tid] = bn4[3 * C + tid];
@@ -742,7 +787,12 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
       int am = 0;
       uint4 pk, fb;
       uint2 bh2, bl2;
-      head32_step<DEFER, LOSS>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh, gs, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
+      float wy = 1.f, gsw = gs;                      // the pixel's class weight, gs * weight
+      if (WT) {
+        wy = class_w<MAXK>(sCW, lab, 0.f);
+        gsw = gs * wy;
+      }
+      head32_step<DEFER, LOSS, WT>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh, gsw, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
                                lse, zy, am);
       if (STORE && valid) *reinterpret_cast<uint4*>(dA + px * C + 8 * g) = pk;
       // dWh via the LDS transpose: act row (the lane's 8 channels; zero for tail pixels),
@@ -763,8 +813,13 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
       if (LOSS) {                                    // (branch-free: row g = 0 counts a pixel)
         const bool cnt_px = g == 0 && valid;
         const bool lv = cnt_px && lab != ignore_index;
-        ls[0] += lv ? lse - zy : 0.f;
-        ls[2] += lv ? 1.f : 0.f;
+        if (WT) {
+          ls[0] += lv ? (lse - zy) * wy : 0.f;
+          ls[2] += lv ? wy : 0.f;
+        } else {
+          ls[0] += lv ? lse - zy : 0.f;
+          ls[2] += lv ? 1.f : 0.f;
+        }
         ls[1] += (cnt_px && am == lab) ? 1.f : 0.f;
       }
       if (DEFER) {
@@ -846,17 +901,19 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
 
 // The C = 32 counterpart of head_bn_apply_kernel: dA recomputed exactly as head32_kernel
 // stores it, the deferred BatchNorm's backward applied in registers (bn_bwd2_kernel's apply
-// arithmetic), dY stored.  A HEAD32_DA-deep load pipeline.
+// arithmetic), dY stored.  A HEAD32_DA-deep load pipeline.  WT: as head32_kernel.
+template <bool WT>
 __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, const float* __restrict__ bn4,
     const float* __restrict__ coefs, bf16_t* __restrict__ dY, long long P, int ignore_index,
-    int Kreal, int groups, long long gsteps) {
+    int Kreal, int groups, long long gsteps, const float* __restrict__ cw) {
   constexpr int C = 32;
   // scale | shift | invstd | -mean*invstd | k | m1 | m2 (the BN backward coefficients)
   __shared__ __attribute__((aligned(16))) float sK[7][C];
   __shared__ Head32W sW[64];                       // the lanes' constant MFMA operands
+  __shared__ float sCW[MAXK];                      // class weights (WT)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: scalar step indices)
   const int n = lane & 15, g = lane >> 4;
   // BN groups: group-major workgroups as head32_kernel (bn4 [groups][4][C], coefs [groups][3][C])
@@ -865,6 +922,7 @@ __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
   bn4 += (long long)grp * 4 * C;
   coefs += (long long)grp * 3 * C;
   if (tid < 64) sW[tid] = head32_weights(Wh, bh, Kreal, lane);
+  if (WT) load_cw<MAXK>(cw, Kreal, sCW);
   if (tid < C) {
     sK[0][tid] = bn4[2 * C + tid]; sK[1][tid] = bn4[3 * C + tid];
     sK[2][tid] = bn4[C + tid]; sK[3][tid] = -bn4[tid] * bn4[C + tid];
@@ -907,7 +965,8 @@ __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
       int am;
       uint4 pk, fb;
       uint2 bh2, bl2;
-      head32_step<true, false>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh, gs, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
+      head32_step<true, false, WT>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh,
+                               WT ? gs * class_w<MAXK>(sCW, lab, 0.f) : gs, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
                                lse, zy, am);
       float rr[8], o[8], is[8], nm[8], k1[8], m1[8], m2[8];
       unpack8(pk, rr);
@@ -1027,6 +1086,13 @@ __global__ __launch_bounds__(256) void head_predict_accum_kernel(
     return true;                                                                    \
   }()
 
+// the C = 32 kernels with (WT = true) and without the class-weight factor
+#define HEAD32_WT(cw_, ...)                                  \
+  do {                                                       \
+    if ((cw_) != nullptr) { constexpr bool WT = true; __VA_ARGS__; } \
+    else { constexpr bool WT = false; __VA_ARGS__; }         \
+  } while (0)
+
 }  // namespace
 
 bool head_supported(int C, int K) {
@@ -1035,13 +1101,13 @@ bool head_supported(int C, int K) {
 
 void head_ce_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         float* partial, float* out3, const float* bn4, int nblocks, long long P,
-                        int C, int K, int ignore_index, hipStream_t st) {
+                        int C, int K, int ignore_index, hipStream_t st, const float* cw) {
   if (bn4 != nullptr)
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_fwd_kernel<CC, KK, true>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K));
+                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K, cw));
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_fwd_kernel<CC, KK, false>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K));
+                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K, cw));
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, out3);
 }
 
@@ -1060,9 +1126,11 @@ int head32_grid(long long P, int per_cu, int num_cus) {
   return (int)std::max<long long>(1, std::min<long long>(steps4, (long long)per_cu * num_cus));
 }
 int head32_bwd_per_cu() {
-  static int n = std::min({head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, true, false>)),
-                           head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, false, false>)),
-                           head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<false, true, false>))});
+  // (the unweighted instantiations size every grid: the weighted ones run under the same
+  // launch bounds on the same grid, so the reduction order does not depend on the weights)
+  static int n = std::min({head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, true, false, false>)),
+                           head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, false, false, false>)),
+                           head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<false, true, false, false>))});
   return n;
 }
 }  // namespace
@@ -1089,38 +1157,38 @@ int head_ce_bwd_blocks(int C, int K, bool /*defer*/, long long P, int num_cus) {
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         const float* gscale, const float* stats3, int /*unused*/, bf16_t* dA,
                         float* dW_partial, int nblocks, long long P, int C, int K,
-                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st) {
+                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st,
+                        const float* cw) {
   if (C == 32 && K <= MAXK) {
-    if (bn4 != nullptr && dA == nullptr)
-      hipLaunchKernelGGL((head32_kernel<true, false, false>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh,
-                         labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, 1, 0LL);
-    else if (bn4 != nullptr)
-      hipLaunchKernelGGL((head32_kernel<true, true, false>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh,
-                         labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, 1, 0LL);
-    else
-      hipLaunchKernelGGL((head32_kernel<false, true, false>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh,
-                         labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, 1, 0LL);
+#define HEAD32_BWD(D_, S_)                                                                          \
+  HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<D_, S_, false, WT>), dim3(nblocks), dim3(256), 0, st, a, Wh, \
+                                   bh, labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4,   \
+                                   bnpart, K, nullptr, 1, 0LL, cw))
+    if (bn4 != nullptr && dA == nullptr) HEAD32_BWD(true, false);
+    else if (bn4 != nullptr) HEAD32_BWD(true, true);
+    else HEAD32_BWD(false, true);
+#undef HEAD32_BWD
     return;
   }
   if (bn4 != nullptr && dA == nullptr)               // stats pass of the two-pass backward
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true, false>), dim3(nblocks), dim3(256), 0,
                                          st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K));
+                                         ignore_index, bn4, bnpart, K, nullptr, cw));
   else if (bn4 != nullptr)
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true>), dim3(nblocks), dim3(256), 0,
                                          st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K));
+                                         ignore_index, bn4, bnpart, K, nullptr, cw));
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, false>), dim3(nblocks), dim3(256), 0,
                                          st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K));
+                                         ignore_index, bn4, bnpart, K, nullptr, cw));
 }
 
 // the fused forward + statistics pass: head32_kernel<.., LOSS> for C = 32, else the
 // channel-split head_ce_bwd_kernel<.., LOSS> on head_ce_bwd_blocks' grid
 int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups) {
   if (C == 32 && K <= MAXK) {
-    static const int n = head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, false, true>));
+    static const int n = head32_per_cu(reinterpret_cast<const void*>(&head32_kernel<true, false, true, false>));
     const int nb = head32_grid(P, n, num_cus);
     return groups > 1 ? groups * std::max(1, nb / groups) : nb;   // (groups x Rb, group-major)
   }
@@ -1130,15 +1198,17 @@ int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups) {
 void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
                               const int64_t* labels, const float* bn4, float* dW_partial,
                               float* bnpart, float* loss_partial, float* out3, int nblocks,
-                              long long P, int C, int K, int ignore_index, hipStream_t st, int groups) {
+                              long long P, int C, int K, int ignore_index, hipStream_t st, int groups,
+                              const float* cw) {
   if (C == 32 && K <= MAXK)
-    hipLaunchKernelGGL((head32_kernel<true, false, true>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, labels,
-                       nullptr, nullptr, nullptr, dW_partial, P, ignore_index, bn4, bnpart, K, loss_partial,
-                       groups, groups > 1 ? P / groups / 16 : 0LL);
+    HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<true, false, true, WT>), dim3(nblocks), dim3(256), 0, st, a,
+                                     Wh, bh, labels, nullptr, nullptr, nullptr, dW_partial, P, ignore_index,
+                                     bn4, bnpart, K, loss_partial, groups,
+                                     groups > 1 ? P / groups / 16 : 0LL, cw));
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true, false, true>), dim3(nblocks),
                                          dim3(256), 0, st, a, Wh, bh, labels, nullptr, nullptr, nullptr,
-                                         dW_partial, P, ignore_index, bn4, bnpart, K, loss_partial));
+                                         dW_partial, P, ignore_index, bn4, bnpart, K, loss_partial, cw));
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, loss_partial, nblocks, out3);
 }
 
@@ -1151,20 +1221,20 @@ int head_bn_apply_blocks(long long P, int C) {
 void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                           const float* gscale, const float* stats3, const float* bn4,
                           const float* coefs, bf16_t* dY, long long P, int C, int K,
-                          int ignore_index, int num_cus, hipStream_t st, int groups) {
+                          int ignore_index, int num_cus, hipStream_t st, int groups, const float* cw) {
   if (C == 32 && K <= MAXK) {
-    static const int per_cu = head32_per_cu(reinterpret_cast<const void*>(&head32_apply_kernel));
+    static const int per_cu = head32_per_cu(reinterpret_cast<const void*>(&head32_apply_kernel<false>));
     const int nb = head32_grid(P, per_cu, num_cus);
     const int grid = groups > 1 ? groups * std::max(1, nb / groups) : nb;
-    hipLaunchKernelGGL(head32_apply_kernel, dim3(grid), dim3(256), 0, st, a, Wh, bh,
-                       labels, gscale, stats3, bn4, coefs, dY, P, ignore_index, K, groups,
-                       groups > 1 ? P / groups / 16 : 0LL);
+    HEAD32_WT(cw, hipLaunchKernelGGL((head32_apply_kernel<WT>), dim3(grid), dim3(256), 0, st, a, Wh, bh,
+                                     labels, gscale, stats3, bn4, coefs, dY, P, ignore_index, K, groups,
+                                     groups > 1 ? P / groups / 16 : 0LL, cw));
     return;
   }
   const int nb = head_bn_apply_blocks(P, C);
   HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_bn_apply_kernel<CC, KK>), dim3(nb), dim3(256), 0, st,
                                        a, Wh, bh, labels, gscale, stats3, bn4, coefs, dY, P,
-                                       ignore_index, K));
+                                       ignore_index, K, cw));
 }
 
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits,

@@ -246,11 +246,13 @@ void bn_group_finalize_rows_launch(const float* partial, int nb, int groups, lon
 
 // ---------------------------------------------------------------- head + cross-entropy
 bool head_supported(int C, int K);
+// cw (optional, [K] fp32): class weights of the loss — a valid pixel carries cw[label] and the
+// weight sum replaces the valid-pixel count (out3[2]); every pass of one backward takes the same
 // bn4 (optional, [mean | invstd | scale | shift] x C): the input holds a PRE-BatchNorm
 // conv output whose BN + ReLU is applied on load (deferred activation)
 void head_ce_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         float* partial, float* out3, const float* bn4, int nblocks, long long P,
-                        int C, int K, int ignore_index, hipStream_t st);
+                        int C, int K, int ignore_index, hipStream_t st, const float* cw = nullptr);
 // bnpart (with bn4): [nblocks][2][C] BatchNorm-backward partial rows of the stored dA;
 // nblocks from head_ce_bwd_blocks (one persistent wave of workgroups)
 int head_ce_bwd_blocks(int C, int K, bool defer, long long P, int num_cus);
@@ -261,7 +263,8 @@ int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups = 1
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         const float* gscale, const float* stats3, int unused, bf16_t* dA,
                         float* dW_partial, int nblocks, long long P, int C, int K,
-                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st);
+                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st,
+                        const float* cw = nullptr);
 // two-pass backward with the deferred BatchNorm of the last decoder block: dA == nullptr in
 // head_ce_bwd_launch runs the stats pass (dWh, dbh, BN partials); this second pass
 // recomputes dA and writes that BatchNorm's dY (coefs = [k | m1 | m2] x C); its C = 32 grid
@@ -272,11 +275,12 @@ void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
                               const int64_t* labels, const float* bn4, float* dW_partial,
                               float* bnpart, float* loss_partial, float* out3, int nblocks,
                               long long P, int C, int K, int ignore_index, hipStream_t st,
-                              int groups = 1);
+                              int groups = 1, const float* cw = nullptr);
 void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                           const float* gscale, const float* stats3, const float* bn4,
                           const float* coefs, bf16_t* dY, long long P, int C, int K,
-                          int ignore_index, int num_cus, hipStream_t st, int groups = 1);
+                          int ignore_index, int num_cus, hipStream_t st, int groups = 1,
+                          const float* cw = nullptr);
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
 // whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the

@@ -17,6 +17,9 @@ flags override).  ``train`` prints the final reduced metrics as one JSON line on
 
 ``train --data scene_dir --data-dir scenes/ --augment d4`` trains on uncut scenes of unequal size
 (augmented random crops cut on the device, ``data/scenes.py``);
+``--class-weights 1,1,1,1,4,4`` (one number per class) or ``--class-weights median_freq`` (from
+the training split's labels) trains with ``CrossEntropyLoss(weight=...)``, fused into the head
+kernels — the validation loss stays unweighted, the per-class IoU shows the effect;
 ``config`` prints the resolved configuration (handy for writing a YAML to start from).
 """
 from __future__ import annotations

@@ -18,7 +18,8 @@ import dataclasses
 import json
 import os
 from dataclasses import dataclass, field, fields
-from typing import Any, Dict, Optional
+import math
+from typing import Any, Dict, List, Optional, Sequence, Union
 
 GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax")
 CODEC_SCALES = ("global", "bucket", "tensor")
@@ -26,6 +27,42 @@ REDUCE_OPS = ("mean", "sum", "reference")
 UP_MODES = ("conv_transpose", "bilinear")
 DATA_KINDS = ("synthetic", "vaihingen_dir", "scene_dir")
 AUGMENT_MODES = ("none", "flip", "d4")
+CLASS_WEIGHT_MODES = ("median_freq",)
+
+
+def parse_class_weights(spec: Union[None, str, Sequence[float]], classes: int):
+    """``TrainConfig.class_weights`` -> ``None``, ``"median_freq"`` or a list of ``classes``
+    floats.  A list (a comma string, or a YAML / JSON list) must hold one non-negative finite
+    number per class, not all zero."""
+    if spec is None or (isinstance(spec, str) and spec.strip() in ("", "none", "None")):
+        return None
+    if isinstance(spec, str) and spec.strip() in CLASS_WEIGHT_MODES:
+        return spec.strip()
+    try:
+        vals = [float(v) for v in (spec.split(",") if isinstance(spec, str) else spec)]
+    except (TypeError, ValueError):
+        raise ValueError(f"class_weights={spec!r}: a comma list of {classes} numbers or one of "
+                         f"{CLASS_WEIGHT_MODES}") from None
+    if len(vals) != classes:
+        raise ValueError(f"class_weights: {len(vals)} values for out_classes={classes}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in vals):
+        raise ValueError("class_weights must be non-negative finite numbers")
+    if not any(v > 0.0 for v in vals):
+        raise ValueError("class_weights must not all be zero")
+    return vals
+
+
+def median_freq_weights(counts) -> List[float]:
+    """Median-frequency balancing from per-class pixel counts ``n_k`` (float64 arithmetic):
+    ``f_k = n_k / sum n``, ``w_k = median{f_j : n_j > 0} / f_k``; a class that never occurs
+    gets 1.0."""
+    import numpy as np
+    n = np.asarray(counts, dtype=np.float64)
+    if n.sum() <= 0:
+        raise ValueError("class_weights=median_freq: the training split has no labelled pixels")
+    f = n / n.sum()
+    med = np.median(f[n > 0])
+    return [float(med / fk) if nk > 0 else 1.0 for fk, nk in zip(f, n)]
 
 
 @dataclass
@@ -73,6 +110,10 @@ class TrainConfig:
     augment: str = "none"                # none | flip (the 4 mirrorings) | d4 (+ transposes)
     gain_jitter: float = 0.0             # per-sample gain 1 +- this (uniform) and bias +- this,
     bias_jitter: float = 0.0             # x = clamp(x * gain + bias, 0, 1)
+    # CrossEntropyLoss(weight=...) of the training loss (validation stays unweighted):
+    # None | "w0,w1,..." (out_classes non-negative numbers, not all zero; a YAML list too)
+    # | "median_freq" (from the training split's label histogram; real data only)
+    class_weights: Optional[str] = None
     # ---- optimisation ----------------------------------------------------------
     batch_per_gpu: int = 1               # batch_size, ref.py:686
     accum_steps: int = 1                 # frequency_sending_gradients, ref.py:685
@@ -168,6 +209,14 @@ class TrainConfig:
         for name in ("gain_jitter", "bias_jitter"):
             if not 0.0 <= getattr(self, name) <= 1.0:
                 raise ValueError(f"{name} must be in [0, 1]")
+        if isinstance(self.class_weights, (list, tuple)):      # a YAML / JSON list
+            self.class_weights = ",".join(repr(float(v)) for v in self.class_weights)
+        cw = parse_class_weights(self.class_weights, self.model.out_classes)
+        if cw is None:
+            self.class_weights = None
+        elif cw == "median_freq" and self.data == "synthetic":
+            raise ValueError("class_weights=median_freq needs data=scene_dir or vaihingen_dir (the "
+                             "histogram of the training split's label files)")
         if self.data == "synthetic" and (self.crops_per_epoch or self.augmented):
             raise ValueError("crops_per_epoch, augment and the colour jitters need data=scene_dir or "
                              "vaihingen_dir (the synthetic tiles are rendered, not cropped)")

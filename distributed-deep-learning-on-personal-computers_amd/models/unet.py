@@ -159,14 +159,20 @@ class UNet(nn.Module):
             x = blk(x, s)
         return self.conv_last(x)
 
-    def loss_and_correct(self, x, y, ignore_index: int = -100):
+    def loss_and_correct(self, x, y, ignore_index: int = -100, class_weight=None):
         """Mean cross-entropy (nn.CrossEntropyLoss defaults, ref.py:703) and the number of
         correctly classified pixels (ref.py:775).  The HIP path fuses the 1x1 head,
-        softmax, CE, its gradient and the arg-max into one kernel (logits never hit HBM)."""
+        softmax, CE, its gradient and the arg-max into one kernel (logits never hit HBM).
+
+        ``class_weight`` (fp32 ``[out_classes]``, on the input's device) is
+        ``CrossEntropyLoss(weight=...)``: the loss is ``sum w[y_p] ce_p / sum w[y_p]`` over the
+        valid pixels; the hit count stays unweighted.  Where the weight sum is 0 (every pixel
+        ignored, or every valid label of weight 0) the engine gives loss 0 and zero gradients;
+        this stock path gives PyTorch's NaN."""
         if self._engine is not None:
-            return self._engine.loss_and_correct(x, y)
+            return self._engine.loss_and_correct(x, y, ignore_index, class_weight)
         logits = self.forward_torch(x)
-        loss = F.cross_entropy(logits.float(), y, ignore_index=ignore_index)
+        loss = F.cross_entropy(logits.float(), y, weight=class_weight, ignore_index=ignore_index)
         correct = (logits.detach().argmax(1) == y).sum()
         return loss, correct
 

@@ -297,7 +297,8 @@ class _DoubleConvFn(torch.autograd.Function):
         # ---- second conv: per-group BN2 + ReLU (+ unpool + skip sum) backward
         if head is not None:
             dy2, dg2, dbe2 = F.head_ce_bn_bwd(*hargs, bn2.weight.grad if direct else None,
-                                              bn2.bias.grad if direct else None, hps, G)
+                                              bn2.bias.grad if direct else None, hps, G,
+                                              getattr(da2, "_ddlpc_head_cw", None))
         else:
             dy2, dg2, dbe2 = F.bn_group_backward(da2, dpool, y2, s2, g2, G,
                                                  bn2.weight.grad if direct else None,
@@ -397,6 +398,8 @@ class _DoubleConvFn(torch.autograd.Function):
             y2 = F.conv3_fwd(y1, None, blk.pack2.fwd, ctx.b2, s1[2], s1[3], blk.pack2.cout, 0, False)[0]
         # BN-backward partial sums already reduced by the consumer's kernel (deferred BN)
         part2 = getattr(da2, "_ddlpc_bn_partial", None) if ctx.defer else None
+        # (the class weights of the loss: the second pass must see the first pass's)
+        hcw = getattr(da2, "_ddlpc_head_cw", None) if head is not None else None
         bn1, bn2 = blk.bn1.bn, blk.bn2.bn
         direct = eng.direct_grads
         p1, p2 = blk.pack1, blk.pack2
@@ -408,7 +411,7 @@ class _DoubleConvFn(torch.autograd.Function):
         if direct:
             if head is not None:
                 dy2, _, _ = F.head_ce_bn_bwd(*head, s2, part2, g2, bn2.weight.grad, bn2.bias.grad,
-                                             getattr(da2, "_ddlpc_bn_pscale", None))
+                                             getattr(da2, "_ddlpc_bn_pscale", None), 0, hcw)
             else:
                 dy2, _, _ = F.bn_backward(da2, dpool, y2, s2, g2, None, bn2.weight.grad,
                                           bn2.bias.grad, part2)
@@ -424,7 +427,7 @@ class _DoubleConvFn(torch.autograd.Function):
         else:
             if head is not None:
                 dy2, dg2, dbe2 = F.head_ce_bn_bwd(*head, s2, part2, g2, None, None,
-                                                  getattr(da2, "_ddlpc_bn_pscale", None))
+                                                  getattr(da2, "_ddlpc_bn_pscale", None), 0, hcw)
             else:
                 dy2, dg2, dbe2 = F.bn_backward(da2, dpool, y2, s2, g2, None, None, None, part2)
             if bwd32:
@@ -584,7 +587,7 @@ class _BilinearFn(torch.autograd.Function):
 class _HeadCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, wh, bh, labels, ignore_index: int, engine,
-                bn: Optional[torch.Tensor] = None):
+                bn: Optional[torch.Tensor] = None, cw: Optional[torch.Tensor] = None):
         # training with the deferred BN: the forward also runs the backward's statistics
         # pass (unit gradient scale) — one read of the activation and labels for both
         ctx.rows = None
@@ -595,14 +598,17 @@ class _HeadCEFn(torch.autograd.Function):
         groups = bn.shape[0] if (bn is not None and bn.dim() == 3) else 0
         if (bn is not None and engine.head_apply and engine.head_fused_fwd
                 and any(ctx.needs_input_grad[:3])):
-            out3, wrows, brows = _ops().head_ce_fwd_stats(a, wh, bh, labels, ignore_index, bn, groups)
+            out3, wrows, brows = _ops().head_ce_fwd_stats(a, wh, bh, labels, ignore_index, bn, groups, cw)
             ctx.rows = (wrows, brows)
         else:
             assert groups == 0, "grouped head statistics need the fused training forward"
-            out3 = _ops().head_ce_fwd(a, wh, bh, labels, ignore_index, bn)
+            out3 = _ops().head_ce_fwd(a, wh, bh, labels, ignore_index, bn, cw)
         ctx.save_for_backward(a, wh, bh, labels, out3, bn if bn is not None else torch.empty(0))
         ctx.has_bn = bn is not None
         ctx.ignore_index = ignore_index
+        # class weights of the loss (out3[2] is their sum over the valid pixels): a persistent
+        # tensor of the caller's, not saved for backward — every backward pass reads it again
+        ctx.cw = cw
         ctx.engine = engine
         loss = out3[0]
         correct = out3[1]
@@ -615,6 +621,7 @@ class _HeadCEFn(torch.autograd.Function):
         bn = bn if ctx.has_bn else None
         gs = dloss.reshape(1).float().contiguous() if dloss is not None else None
         eng = ctx.engine
+        cw = ctx.cw
         # two-pass backward with the deferred BatchNorm: this pass reduces dWh, dbh and the
         # BN partials without storing dA; the block's backward then runs head_ce_bn_bwd,
         # which recomputes dA and applies the BatchNorm backward in registers (no dA
@@ -635,26 +642,28 @@ class _HeadCEFn(torch.autograd.Function):
                 dw, db = _ops().head_wgrad_from_rows(wrows, scale, K, C)
             da = eng.zero_scalar(a).expand(a.shape)
             da._ddlpc_head = (a, wh, bh, labels, out3, gs, ctx.ignore_index)
+            da._ddlpc_head_cw = cw
             da._ddlpc_bn_partial = brows
             da._ddlpc_bn_pscale = scale
-            return da, dw, db, None, None, None, None
+            return da, dw, db, None, None, None, None, None
         if eng.direct_grads:
             head = eng.head
             da, _, _, part = _ops().head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index,
-                                                head.weight.grad, head.bias.grad, bn, not two_pass)
+                                                head.weight.grad, head.bias.grad, bn, not two_pass, cw)
             with eng.wgrad_stream():
                 eng.ready(head.weight, head.bias)
             dw = db = None
         else:
             da, dw, db, part = _ops().head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index,
-                                                  None, None, bn, not two_pass)
+                                                  None, None, bn, not two_pass, cw)
         if two_pass:
             # stand-in gradient of the right shape (no storage); the consumer recognises it
             da = eng.zero_scalar(a).expand(a.shape)
             da._ddlpc_head = (a, wh, bh, labels, out3, gs, ctx.ignore_index)
+            da._ddlpc_head_cw = cw
         if bn is not None:
             da._ddlpc_bn_partial = part
-        return da, dw, db, None, None, None, None
+        return da, dw, db, None, None, None, None, None
 
 
 class _Block:
@@ -1122,8 +1131,13 @@ class UNetEngine:
         a, s = self.features(x, defer_last=True)
         return _ops().head_logits(a, wh.detach().contiguous(), bh.detach(), s)
 
-    def loss_and_correct(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int = -100):
-        """-> (mean cross-entropy over the batch's pixels, correct-pixel count).  With
+    def loss_and_correct(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int = -100,
+                         class_weight: Optional[torch.Tensor] = None):
+        """-> (mean cross-entropy over the batch's pixels, correct-pixel count).
+        ``class_weight`` (fp32 ``[K]`` on x's device, kept alive by the caller until the
+        backward has run): ``cross_entropy(weight=)`` — loss and gradients are normalised by the
+        weight sum of the valid pixels instead of their count, the hit count is unweighted, and
+        a zero weight sum gives loss 0 and zero gradients (PyTorch: NaN).  With
         ``bn_groups`` = G >= 1 (training) the batch is G equal micro-batches with their own
         BatchNorm statistics; the running statistics are updated once per micro-batch, in
         order, after the forward (bit-for-bit the update sequence of G forwards)."""
@@ -1134,7 +1148,13 @@ class UNetEngine:
             self.bn_defer_prepare(1, G)
         a, s = self.features(x, defer_last=True)
         wh, bh = self._head_params()
-        out = _HeadCEFn.apply(a, wh, bh, y.contiguous(), ignore_index, self, s)
+        cw = None
+        if class_weight is not None:
+            if (class_weight.dtype != torch.float32 or class_weight.dim() != 1
+                    or class_weight.shape[0] != wh.shape[0] or class_weight.device != a.device):
+                raise ValueError(f"class_weight must be fp32 [{wh.shape[0]}] on {a.device}")
+            cw = class_weight.detach().contiguous()
+        out = _HeadCEFn.apply(a, wh, bh, y.contiguous(), ignore_index, self, s, cw)
         if G >= 1:
             self.bn_defer_apply(G)
         return out

@@ -41,7 +41,8 @@ def set_rng_state(st: Dict[str, Any]):
 
 def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, epoch: int = 0,
                     step: int = 0, micro_step: int = 0, config: Optional[dict] = None,
-                    extra: Optional[dict] = None, epoch_step: int = 0):
+                    extra: Optional[dict] = None, epoch_step: int = 0,
+                    class_weights: Optional[list] = None):
     os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
     sd = {k: v.detach().cpu() if torch.is_tensor(v) else v
           for k, v in model.state_dict().items()}
@@ -55,6 +56,10 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, epoch: in
         blob["optimizer"] = osd
     if extra:
         blob["extra"] = extra
+    if class_weights is not None:
+        # the resolved class weights of the training loss (config.class_weights may say
+        # "median_freq": the numbers depend on the training split)
+        blob["class_weights"] = [float(v) for v in class_weights]
     tmp = path + ".tmp"
     torch.save(blob, tmp)
     os.replace(tmp, path)

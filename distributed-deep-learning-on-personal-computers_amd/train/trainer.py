@@ -25,10 +25,11 @@ import os
 import time
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
-from ..config import TrainConfig
+from ..config import TrainConfig, median_freq_weights, parse_class_weights
 from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset
 from ..models.unet import UNet
 from ..ops import _ext
@@ -130,7 +131,17 @@ class Trainer:
         self._static = None
         self.epoch = 0
         self.epoch_step = 0              # optimizer steps done in the current epoch
+        self._train_label_counts = None
         self.train_set, self.test_set = self._build_data()
+        # class weights of the training loss, resolved once: the list as configured, or
+        # median-frequency balancing from the training split's label histogram (counted on
+        # the host before the upload).  Every rank reads the same files, so every rank
+        # resolves the same weights (no exchange; a checkpoint records the resolved list)
+        self.class_weights = self._resolve_class_weights()
+        self.class_weight = None if self.class_weights is None else torch.tensor(
+            self.class_weights, dtype=torch.float32, device=self.device)
+        if self.class_weights is not None:
+            self.logger.log({"class_weights": [float(v) for v in self.class_weight.tolist()]})
         self.sampler = ShardedSampler(len(self.train_set), self.rank, self.world,
                                       shard=cfg.shard_data, shuffle=cfg.shuffle, seed=cfg.seed)
         if cfg.resume:
@@ -250,6 +261,21 @@ class Trainer:
             self.model._engine.pack_weights()
 
     # ------------------------------------------------------------------ data
+    def _count_labels(self, labels: torch.Tensor):
+        """Label histogram of the training split (host uint8 labels; values outside
+        [0, out_classes) are not counted) — only when class_weights=median_freq asks for it."""
+        if self.cfg.class_weights == "median_freq":
+            k = self.cfg.model.out_classes
+            self._train_label_counts = np.bincount(labels.numpy().reshape(-1), minlength=256)[:k]
+
+    def _resolve_class_weights(self) -> Optional[List[float]]:
+        k = self.cfg.model.out_classes
+        cw = parse_class_weights(self.cfg.class_weights, k)
+        if cw == "median_freq":
+            # float64 on the host, then fp32 (the kernels' and F.cross_entropy's weight dtype)
+            cw = np.asarray(median_freq_weights(self._train_label_counts)).astype(np.float32).tolist()
+        return cw
+
     def _build_data(self):
         """Datasets that produce device batches directly on a GPU: the
         synthetic generator renders in HBM, a real dataset is uploaded once as uint8."""
@@ -272,12 +298,14 @@ class Trainer:
                 tr = SceneCropDataset.from_tiles(tiles, c.tile, **crop)
                 te = None if held is None else SceneCropDataset.test_grid(
                     [(x, y) for x, y in zip(held.x.numpy(), held.y.numpy())], c.tile, layout)
+            self._count_labels(tr.labels)
             if cuda and c.data_on_device:
                 tr = tr.to_device(self.device, layout, budget)
                 te = te.to_device(self.device, layout, budget) if te is not None else None
             return tr, te
         if c.data == "vaihingen_dir":
             tr, te = TileDataset.from_dir(c.data_dir, c.test_holdout)
+            self._count_labels(tr.y)
             if cuda and c.data_on_device:
                 tr = tr.to_device(self.device, layout, budget)
                 te = te.to_device(self.device, layout, budget) if te is not None else None
@@ -307,7 +335,7 @@ class Trainer:
         ctx = (torch.autocast("cuda", dtype=torch.bfloat16) if self.autocast
                else contextlib.nullcontext())
         with ctx:
-            loss, correct = self.model.loss_and_correct(x, y)
+            loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
         if sync and self.reducer is not None:
             self.reducer.mark_backward_start()
         loss.backward()
@@ -385,7 +413,7 @@ class Trainer:
         self.micro_count += n
 
     def _ms_body(self, k: int, x, y):
-        loss, correct = self.model.loss_and_correct(x, y)
+        loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
         loss.backward()
         self._ms_meters[k].add(loss, correct, y.numel())
 
@@ -518,7 +546,7 @@ class Trainer:
         x, y = self._static[0], self._static[1]
         if self.reducer is not None:
             self.reducer.prepare(sync=False)        # "acc": never a collective in a graph
-        loss, correct = self.model.loss_and_correct(x, y)
+        loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
         loss.backward()
         self.meter.add(loss, correct, y.numel())
         if kind == "last":                          # single GPU: the optimizer step too
@@ -706,7 +734,7 @@ class Trainer:
                 self.reducer.prepare(sync=ci == len(chunks) - 1)
             eng.bn_groups = len(ch) if len(ch) > 1 else 0
             try:
-                loss, correct = self.model.loss_and_correct(x, y)
+                loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
                 if self.reducer is not None and ci == len(chunks) - 1:
                     self.reducer.mark_backward_start()
                 (loss * float(len(ch)) if len(ch) > 1 else loss).backward()
@@ -889,7 +917,11 @@ class Trainer:
     @torch.no_grad()
     def validate(self, dataset=None, batch: Optional[int] = None) -> Dict[str, float]:
         """Held-out loss, pixel accuracy and per-class IoU (the reference never evaluates its
-        30-tile test split, ref.py:672-673), sharded over ranks and all-reduced."""
+        30-tile test split, ref.py:672-673), sharded over ranks and all-reduced.
+
+        ``val_loss`` is always the UNWEIGHTED mean cross-entropy, whatever ``class_weights``
+        the training loss uses: that is the figure that stays comparable between runs.  The
+        effect of class weights shows in the per-class IoU (``val_iou``)."""
         ds = dataset if dataset is not None else self.test_set
         if ds is None or len(ds) == 0:
             return {}
@@ -932,7 +964,8 @@ class Trainer:
         if self.rank == 0:
             save_checkpoint(path, self.model, self.optimizer, epoch=self.epoch,
                             step=self.step_count, micro_step=self.micro_count,
-                            config=self.cfg.to_dict(), epoch_step=self.epoch_step)
+                            config=self.cfg.to_dict(), epoch_step=self.epoch_step,
+                            class_weights=self.class_weights)
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
         return path
