@@ -97,8 +97,10 @@ std::string last_path() { return g_last_path; }
 // configurations.
 //   CROP_LDS_T (default 1): crop_gather's transposing codes through LDS; 0 = the direct
 //   strided read, kept for scripts/crop_micro.py's A/B (docs/PERF.md)
+//   WINDOW_LDS_T (default 1): the same choice for window_gather's transposing codes
+//   (scripts/predict_micro.py --tta, docs/PERF.md)
 namespace {
-const char* const kKnobs[] = {"CROP_LDS_T"};
+const char* const kKnobs[] = {"CROP_LDS_T", "WINDOW_LDS_T"};
 bool knob_registered(const std::string& name) {
   for (const char* k : kKnobs)
     if (k[0] != 0 && name == k) return true;
@@ -1706,9 +1708,57 @@ static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
   TORCH_CHECK(origins.device() == like.device(), "origins must be on the scene's device");
 }
 
-// HBM-resident uint8 scene [H, W, Cin] -> bf16 windows [B, tile, tile, cpad], mirrored borders
+// test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
+// in 0..7) -> S (0 without codes) and the codes packed 3 bits each, code j at bits 3 j.  The
+// values are checked on the host and reach the kernels as a launch argument: the list is read
+// back with one small blocking copy, once per tensor — the last checked list of a thread is
+// remembered (the tensor itself, so its memory cannot be handed out again, and its version
+// counter, which every in-place write moves), and a predictor that passes the same codes tensor
+// to every call pays the copy and the stall of the launch queue once per scene, not per pass
+namespace {
+struct CodesSeen {
+  at::Tensor t;
+  int64_t S = 0;
+  uint32_t version = 0, packed = 0;
+};
+}  // namespace
+static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& like, uint32_t* packed) {
+  *packed = 0u;
+  if (!codes.has_value() || !codes->defined()) return 0;
+  TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
+  TORCH_CHECK(codes->device() == like.device(), "codes must be on the device of the other tensors");
+  const int64_t S = codes->size(0);
+  TORCH_CHECK(S >= 1 && S <= 8, "codes: 1 <= S <= 8");
+  // (never freed: a device tensor must not be destroyed while the process exits)
+  thread_local CodesSeen* seen_last = new CodesSeen();
+  const bool versioned = !codes->is_inference();
+  if (versioned && seen_last->t.defined() && seen_last->t.is_same(*codes) && seen_last->S == S &&
+      seen_last->version == codes->_version()) {
+    *packed = seen_last->packed;
+    return (int)S;
+  }
+  const at::Tensor host = codes->contiguous().cpu();
+  const int* c = host.data_ptr<int>();
+  uint32_t seen = 0u;
+  for (int64_t j = 0; j < S; ++j) {
+    TORCH_CHECK(c[j] >= 0 && c[j] <= 7, "codes: values must lie in 0..7");
+    TORCH_CHECK(!(seen & (1u << c[j])), "codes: values must be distinct");
+    seen |= 1u << c[j];
+    *packed |= (uint32_t)c[j] << (3 * j);
+  }
+  if (versioned) {
+    seen_last->t = *codes;
+    seen_last->S = S;
+    seen_last->version = codes->_version();
+    seen_last->packed = *packed;
+  }
+  return (int)S;
+}
+
+// HBM-resident uint8 scene [H, W, Cin] -> bf16 windows [B, tile, tile, cpad], mirrored borders;
+// with codes [S]: [B * S, tile, tile, cpad], row b * S + j = window b under symmetry codes[j]
 at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int64_t tile,
-                         int64_t cpad) {
+                         int64_t cpad, const c10::optional<at::Tensor>& codes) {
   CHECK_DEV(scene); CHECK_CONTIG(scene);
   TORCH_CHECK(scene.scalar_type() == at::kByte && scene.dim() == 3, "scene must be uint8 [H, W, Cin]");
   check_origins(origins, scene);
@@ -1719,6 +1769,18 @@ at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int
   c10::DeviceGuard guard(scene.device());
   const int64_t B = origins.size(0);
   TORCH_CHECK(B < (1 << 30), "too many windows");
+  uint32_t packed = 0u;
+  const int S = pack_codes(codes, scene, &packed);
+  if (S > 0) {
+    const int64_t nb = window_gather_blocks((int)tile);
+    TORCH_CHECK(B * S * nb * nb < (1LL << 31), "window_gather: batch too large");
+    at::Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
+    if (B > 0)
+      window_gather_codes_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, S, packed,
+                                 (int)H, (int)W, (int)in_ch, (int)tile, (int)cpad,
+                                 knob("WINDOW_LDS_T", 1) != 0, bptr_mut(x), cur_stream());
+    return x;
+  }
   at::Tensor x = at::empty({B, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
   if (B > 0)
     window_gather_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, (int)H, (int)W,
@@ -1731,10 +1793,13 @@ at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int
 // the kernel accumulates with plain read-modify-write, no atomics
 void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                         const at::Tensor& origins, const at::Tensor& win, at::Tensor& acc,
-                        const c10::optional<at::Tensor>& bn4) {
+                        const c10::optional<at::Tensor>& bn4, const c10::optional<at::Tensor>& codes) {
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
   TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2), "a must be [B, tile, tile, C]");
-  const int64_t B = a.size(0), tile = a.size(1);
+  uint32_t packed = 0u;
+  const int S = pack_codes(codes, a, &packed);
+  TORCH_CHECK(S == 0 || a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
+  const int64_t B = S > 0 ? a.size(0) / S : a.size(0), tile = a.size(1);
   const int C = (int)a.size(3);
   CHECK_DEV(Wh); CHECK_F32(Wh); CHECK_CONTIG(Wh); CHECK_DEV(bh); CHECK_F32(bh); CHECK_CONTIG(bh);
   TORCH_CHECK(Wh.dim() == 2 && Wh.size(1) == C && bh.numel() == Wh.size(0), "Wh [K, C] / bh [K]");
@@ -1755,6 +1820,14 @@ void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Ten
   c10::DeviceGuard guard(a.device());
   const float* pbn = bn4_ptr(bn4, C);
   if (B == 0) return;
+  if (S > 0) {
+    TORCH_CHECK(B * S < (1 << 30), "scene / window size out of range");
+    head_predict_accum_codes_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(),
+                                    origins.data_ptr<int>(), win.data_ptr<float>(), acc.data_ptr<float>(),
+                                    (int)B, S, packed, (int)tile, (int)acc.size(0), (int)acc.size(1),
+                                    (int)acc.size(2), C, K, pbn, cur_stream());
+    return;
+  }
   head_predict_accum_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), origins.data_ptr<int>(),
                             win.data_ptr<float>(), acc.data_ptr<float>(), (int)B, (int)tile,
                             (int)acc.size(0), (int)acc.size(1), (int)acc.size(2), C, K, pbn, cur_stream());
@@ -1876,10 +1949,10 @@ TORCH_LIBRARY(ddlpc, m) {
         "int tile, int cpad) -> Tensor[]");
   m.def("crop_params(Tensor idx, Tensor cum, Tensor table, int seed, int tile, int mode, "
         "float gain_jitter, float bias_jitter) -> Tensor[]");
-  m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad) -> Tensor");
+  m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad, Tensor? codes=None) -> Tensor");
   // (the windows of one call must be pairwise disjoint: acc is updated without atomics)
   m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
-        "Tensor? bn4=None) -> ()");
+        "Tensor? bn4=None, Tensor? codes=None) -> ()");
   m.def("scene_finalize(Tensor acc, int K, Tensor? labels=None, int ignore_index=-100) -> Tensor[]");
 }
 

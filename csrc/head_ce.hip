@@ -1015,7 +1015,8 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const bf16_t* __restri
 // != 0 adds w2 * softmax_k to channel k < K and w2 to channel K; channels above K keep their
 // bits, every other pixel is not touched.  The windows of one launch are pairwise disjoint
 // (the colour plan), so a scene pixel belongs to at most one thread: plain read-modify-write,
-// no atomics, the same bits on every run.
+// no atomics, the same bits on every run.  (With symmetry codes — test-time augmentation —
+// head_predict_accum_codes_kernel below blends the S views of a window in the same pass.)
 template <int C, int K, bool DEFER>
 __global__ __launch_bounds__(256) void head_predict_accum_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
@@ -1061,6 +1062,130 @@ __global__ __launch_bounds__(256) void head_predict_accum_kernel(
           const float pk = ws * z[k < K ? k : kmax];
           if (k < Kreal) f[j] += pk;
           else if (k == Kreal) f[j] += w2;
+        }
+        ap[q] = make_float4(f[0], f[1], f[2], f[3]);
+      }
+    }
+  }
+}
+
+// Test-time augmentation: a [B * S][tile][tile][C] holds S views of every window, window-major,
+// view j of a window predicted under symmetry code j of `codes` (3 bits per code, code j at
+// bits 3 j; the convention of crop_gather / window_gather: network-side pixel (oy, ox) is
+// window-frame pixel (wa, wb) = (oy, ox); code & 4: swap; code & 2: wa = tile - 1 - wa;
+// code & 1: wb = tile - 1 - wb).  One thread owns one WINDOW-FRAME pixel (wa, wb) of one
+// window: it reads its S activations through the inverse map, computes the S softmaxes
+// (e_jk = exp(logit - max), se_j their sum), sums the views before the last in ascending j
+// (r_k = sum_{j < S - 1} (w2 / S) / se_j * e_jk, an fma chain from -0) and does ONE
+// read-modify-write of the scene pixel: acc[.., k] = fma((w2 / S) / se_last, e_last,k,
+// acc[.., k] + r_k), acc[.., K] += w2 — the accumulator traffic of one view, not of S.  The
+// S views of a window belong to one thread and the windows of a launch are disjoint: no
+// atomics, the same bits on every run.  Lanes run along wb: the accumulator and the
+// non-transposing views are read along rows; a transposing view is read with a stride of one
+// activation row between lanes, whole 2 C-byte pixels each.  A thread works through its S
+// views one after the other, so each view's pixel is requested 64 bytes at a time before its
+// first use (with logits_of's one 16-byte load in flight the kernel ran at 0.82 of S
+// single-view launches instead of 0.57, docs/PERF.md).
+// S = 1, code 0 gives the bits of head_predict_accum_kernel: w2 / 1 = w2, x + -0 = x, and the
+// last view is added with the fused multiply-add that kernel's `f += ws * z` compiles to.
+template <int C, int K, bool DEFER>
+__global__ __launch_bounds__(256) void head_predict_accum_codes_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int* __restrict__ origins, const float* __restrict__ win, float* __restrict__ acc,
+    long long P, int S, uint32_t codes, int tile, int H, int W, int KA,
+    const float* __restrict__ bn4, int Kreal) {
+  __shared__ __attribute__((aligned(16))) float sBNm[4 * C];
+  __shared__ float sW[K * C], sb[K];
+  load_head<C, K>(Wh, bh, Kreal, sW, sb);
+  const float* sBN = DEFER ? load_bn<C>(bn4, sBNm, false) : nullptr;
+  __syncthreads();
+  const int T2 = tile * tile;
+  const float fS = (float)S;
+#pragma unroll 1
+  for (long long px = blockIdx.x * (long long)blockDim.x + threadIdx.x; px < P;
+       px += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(px / T2);
+    const int p = (int)(px - (long long)b * T2);
+    const int wa = p / tile, wb = p - wa * tile;
+    const int sy = origins[2 * b] + wa, sx = origins[2 * b + 1] + wb;
+    const float w2 = win[wa] * win[wb];
+    if (sy < 0 || sy >= H || sx < 0 || sx >= W || w2 == 0.f) continue;
+    const float wS = w2 / fS;
+    float z[K], ws;
+    // view j -> z = exp(logit - max), ws = (w2 / S) / sum(z)
+    auto view = [&](int j) {
+      const int code = (int)((codes >> (3 * j)) & 7u);
+      const int ia = (code & 2) ? tile - 1 - wa : wa;
+      const int ib = (code & 1) ? tile - 1 - wb : wb;
+      const int oy = (code & 4) ? ib : ia, ox = (code & 4) ? ia : ib;
+      const long long q = (((long long)b * S + j) * tile + oy) * tile + ox;
+      // up to 32 channels (64 bytes) of the pixel are requested before their first use: four
+      // loads in flight per thread instead of logits_of's one (the same sums in the same
+      // order); C = 64 takes two such steps, which keeps the unrolled body and its registers
+      // those of C = 32
+      constexpr int CH = C < 32 ? C : 32;
+      const uint4* rp = reinterpret_cast<const uint4*>(a + q * C);
+      const int oz = opaque_zero();
+      const float* vW = sW + oz;
+      const float* vb = sb + oz;
+#pragma unroll
+      for (int k = 0; k < K; ++k) z[k] = vb[k];
+#pragma unroll 1
+      for (int c0 = 0; c0 < C; c0 += CH) {
+        uint4 row[CH / 8];
+#pragma unroll
+        for (int i = 0; i < CH / 8; ++i) row[i] = rp[c0 / 8 + i];
+#pragma unroll
+        for (int i = 0; i < CH / 8; ++i) {
+          const int c8 = c0 + 8 * i;
+          float f[8];
+          unpack8(row[i], f);
+          if (DEFER) {
+            const float* vn = sBN + opaque_zero();
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) f[jj] = fmaxf(fmaf(f[jj], vn[c8 + jj], vn[C + c8 + jj]), 0.f);
+            unpack8(pack8(f), f);
+          }
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) z[k] = fmaf(f[jj], vW[k * C + c8 + jj], z[k]);
+        }
+      }
+      float m = z[0];
+#pragma unroll
+      for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
+      float se = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        z[k] = __expf(z[k] - m);
+        se += z[k];
+      }
+      ws = wS / se;
+    };
+    float r[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) r[k] = -0.f;
+#pragma unroll 1
+    for (int j = 0; j + 1 < S; ++j) {
+      view(j);
+#pragma unroll
+      for (int k = 0; k < K; ++k) r[k] = fmaf(ws, z[k], r[k]);
+    }
+    view(S - 1);
+    float4* ap = reinterpret_cast<float4*>(acc + ((long long)sy * W + sx) * KA);
+#pragma unroll
+    for (int q = 0; q < (K + 4) / 4; ++q) {
+      if (4 * q < KA) {
+        const float4 v = ap[q];
+        float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          constexpr int kmax = K - 1;
+          const int k = 4 * q + jj;
+          const int kk = k < K ? k : kmax;
+          if (k < Kreal) f[jj] = fmaf(ws, z[kk], __fadd_rn(f[jj], r[kk]));
+          else if (k == Kreal) f[jj] = __fadd_rn(f[jj], w2);
         }
         ap[q] = make_float4(f[0], f[1], f[2], f[3]);
       }
@@ -1259,6 +1384,22 @@ void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, false>), dim3(grid), dim3(256),
                                          0, st, a, Wh, bh, origins, win, acc, P, tile, H, W, KA, bn4, K));
+}
+
+void head_predict_accum_codes_launch(const bf16_t* a, const float* Wh, const float* bh,
+                                     const int* origins, const float* win, float* acc, int B, int S,
+                                     uint32_t codes, int tile, int H, int W, int KA, int C, int K,
+                                     const float* bn4, hipStream_t st) {
+  const long long P = (long long)B * tile * tile;        // threads: window-frame pixels
+  const int grid = (int)std::min<long long>((P + 255) / 256, 4096);
+  if (bn4 != nullptr)
+    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_codes_kernel<CC, KK, true>), dim3(grid),
+                                         dim3(256), 0, st, a, Wh, bh, origins, win, acc, P, S, codes,
+                                         tile, H, W, KA, bn4, K));
+  else
+    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_codes_kernel<CC, KK, false>), dim3(grid),
+                                         dim3(256), 0, st, a, Wh, bh, origins, win, acc, P, S, codes,
+                                         tile, H, W, KA, bn4, K));
 }
 
 }  // namespace ddlpc

@@ -288,10 +288,20 @@ void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float
 void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh, const int* origins,
                                const float* win, float* acc, int B, int tile, int H, int W, int KA,
                                int C, int K, const float* bn4, hipStream_t st);
+// test-time augmentation: a [B * S][tile][tile][C], window-major views under the symmetry
+// codes packed 3 bits each in `codes` (code j at bits 3 j); one read-modify-write per pixel
+void head_predict_accum_codes_launch(const bf16_t* a, const float* Wh, const float* bh,
+                                     const int* origins, const float* win, float* acc, int B, int S,
+                                     uint32_t codes, int tile, int H, int W, int KA, int C, int K,
+                                     const float* bn4, hipStream_t st);
 
 // ---------------------------------------------------------------- scene prediction (scene.hip)
 void window_gather_launch(const uint8_t* scene, const int* origins, int B, int H, int W, int in_ch,
                           int tile, int cpad, bf16_t* x, hipStream_t st);
+int window_gather_blocks(int tile);   // workgroups per output row / column of one view
+void window_gather_codes_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
+                                int H, int W, int in_ch, int tile, int cpad, bool lds_transpose,
+                                bf16_t* x, hipStream_t st);
 void scene_finalize_launch(const float* acc, long long P, int K, int KA, const uint8_t* labels,
                            int ignore_index, uint8_t* pred, int64_t* cm, hipStream_t st);
 

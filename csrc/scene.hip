@@ -9,6 +9,9 @@
 //     edge pixel not repeated) is cut out directly in the first conv's input layout —
 //     channel-last bf16, /255 by IEEE division as tile_gather_kernel, channels zero-padded to
 //     cpad (8 = one 16-byte store per pixel).
+//   * window_gather_codes_kernel: the same cut under a list of symmetry codes (test-time
+//     augmentation): S views per window, window-major, the values of window_gather_kernel
+//     read through crop_gather's index map.
 //   * scene_finalize_kernel: accumulator [H, W, KA] -> uint8 class map (arg-max over the K
 //     class channels, lowest class on ties) and, with labels, the K x K confusion matrix:
 //     counted per workgroup in LDS, then added to HBM with integer atomics (integer sums do
@@ -42,6 +45,88 @@ __global__ __launch_bounds__(256) void window_gather_kernel(
 #pragma unroll
       for (int c = 0; c < 8; ++c)
         if (c < cpad) x[e * cpad + c] = f2bf(f[c]);
+    }
+  }
+}
+
+// Test-time augmentation: window b under symmetry code c (the convention of crop_gather,
+// data.hip: network-side pixel (oy, ox) reads window-frame pixel (a, b) = (oy, ox); c & 4:
+// swap a, b; c & 2: a = tile - 1 - a; c & 1: b = tile - 1 - b; scene pixel (y0 + a, x0 + b),
+// mirrored).  Output [B * S, tile, tile, cpad], window-major: row b * S + j is window b under
+// code j of `codes` (3 bits per code, code j at bits 3 j; a kernel argument, no device read).
+// One workgroup per kWinBS^2 block of one view's output pixels, lanes along ox: every output
+// row segment is one 16-byte store per lane.  Codes without bit 4 read the scene row forwards
+// or backwards (coalesced).  Transposing codes: scene COLUMN = f(oy), scene ROW = f(ox); with
+// LDS_T the block's scene pixels are read with lanes along the scene row into LDS as raw
+// bytes, s[ox][oy] (rows padded to kWinBS + 1: the transposed 8-byte read is conflict-free
+// per 32-lane half), and the output phase reads s transposed; without it adjacent lanes read
+// scene pixels W * in_ch bytes apart (the A/B of scripts/predict_micro.py, docs/PERF.md).
+// The code is uniform in a workgroup: no branch below diverges inside a wave.
+constexpr int kWinBS = 32;
+
+DDLPC_DEVICE int reflect_in(int i, int n) {
+  return (unsigned)i < (unsigned)n ? i : reflect_index(i, n);
+}
+
+template <bool LDS_T>
+__global__ __launch_bounds__(256) void window_gather_codes_kernel(
+    const uint8_t* __restrict__ scene, const int* __restrict__ origins, int S, uint32_t codes, int H,
+    int W, int nb, int in_ch, int tile, int cpad, bf16_t* __restrict__ x) {
+  __shared__ uint2 s_px[kWinBS][kWinBS + 1];
+  const int blk = blockIdx.x;
+  const int v = blk / (nb * nb);             // view = b * S + j
+  const int rem = blk - v * nb * nb;
+  const int by = rem / nb, bx = rem - by * nb;
+  const int b = v / S, j = v - b * S;
+  const int code = (int)((codes >> (3 * j)) & 7u);
+  const int y0 = origins[2 * b], x0 = origins[2 * b + 1];
+  const int lx = threadIdx.x & (kWinBS - 1), ly0 = threadIdx.x / kWinBS;
+  constexpr int kRows = 256 / kWinBS;
+  auto load = [&](int sy, int sx) {
+    const uint8_t* sp = scene + ((long long)sy * W + sx) * in_ch;
+    uint32_t w0 = 0u, w1 = 0u;
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch)
+      if (ch < in_ch) (ch < 4 ? w0 : w1) |= (uint32_t)sp[ch] << (8 * (ch & 3));
+    return make_uint2(w0, w1);
+  };
+  const bool staged = LDS_T && (code & 4);
+  if (staged) {
+    // load role: r = ox - block origin (scene row), lanes along oy - block origin (scene column)
+    for (int r = ly0; r < kWinBS; r += kRows) {
+      const int ox = bx * kWinBS + r, oy = by * kWinBS + lx;
+      if (ox < tile && oy < tile) {
+        const int a = (code & 2) ? tile - 1 - ox : ox;
+        const int c = (code & 1) ? tile - 1 - oy : oy;
+        s_px[r][lx] = load(reflect_in(y0 + a, H), reflect_in(x0 + c, W));
+      }
+    }
+    __syncthreads();
+  }
+  for (int ly = ly0; ly < kWinBS; ly += kRows) {
+    const int oy = by * kWinBS + ly, ox = bx * kWinBS + lx;
+    if (oy >= tile || ox >= tile) continue;
+    uint2 px;
+    if (staged) {
+      px = s_px[lx][ly];
+    } else {
+      int a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+      if (code & 2) a = tile - 1 - a;
+      if (code & 1) c = tile - 1 - c;
+      px = load(reflect_in(y0 + a, H), reflect_in(x0 + c, W));
+    }
+    const uint32_t w[2] = {px.x, px.y};
+    float f[8];
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch)
+      f[ch] = ch < in_ch ? __fdiv_rn((float)((w[ch >> 2] >> (8 * (ch & 3))) & 0xffu), 255.0f) : 0.f;
+    const long long e = ((long long)v * tile + oy) * tile + ox;
+    if (cpad == 8) {
+      reinterpret_cast<uint4*>(x)[e] = pack8(f);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 8; ++ch)
+        if (ch < cpad) x[e * cpad + ch] = f2bf(f[ch]);
     }
   }
 }
@@ -94,6 +179,25 @@ void window_gather_launch(const uint8_t* scene, const int* origins, int B, int H
                           int tile, int cpad, bf16_t* x, hipStream_t st) {
   hipLaunchKernelGGL(window_gather_kernel, dim3(scene_grid((long long)B * tile * tile)), dim3(256),
                      0, st, scene, origins, B, H, W, in_ch, tile, cpad, x);
+}
+
+int window_gather_blocks(int tile) { return (tile + kWinBS - 1) / kWinBS; }
+
+void window_gather_codes_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
+                                int H, int W, int in_ch, int tile, int cpad, bool lds_transpose,
+                                bf16_t* x, hipStream_t st) {
+  const int nb = window_gather_blocks(tile);
+  const dim3 grid((unsigned)((long long)B * S * nb * nb));
+  // a list without a transposing code never stages: the direct kernel runs the same
+  // instructions without the LDS allocation (3% faster, docs/PERF.md)
+  bool transposing = false;
+  for (int j = 0; j < S; ++j) transposing |= ((codes >> (3 * j)) & 4u) != 0;
+  if (lds_transpose && transposing)
+    hipLaunchKernelGGL(window_gather_codes_kernel<true>, grid, dim3(256), 0, st, scene, origins, S,
+                       codes, H, W, nb, in_ch, tile, cpad, x);
+  else
+    hipLaunchKernelGGL(window_gather_codes_kernel<false>, grid, dim3(256), 0, st, scene, origins, S,
+                       codes, H, W, nb, in_ch, tile, cpad, x);
 }
 
 void scene_finalize_launch(const float* acc, long long P, int K, int KA, const uint8_t* labels,

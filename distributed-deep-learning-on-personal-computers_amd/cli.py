@@ -15,6 +15,9 @@ flags override).  ``train`` prints the final reduced metrics as one JSON line on
 
     python -m ddlpc predict --checkpoint runs/x/ckpt_900.pt --input scenes/ --out-dir pred/
 
+(``--tta d4`` averages every window over the eight symmetries of the square, the test-time
+counterpart of ``train --augment d4``.)
+
 ``train --data scene_dir --data-dir scenes/ --augment d4`` trains on uncut scenes of unequal size
 (augmented random crops cut on the device, ``data/scenes.py``);
 ``--class-weights 1,1,1,1,4,4`` (one number per class) or ``--class-weights median_freq`` (from
@@ -33,7 +36,8 @@ from typing import List, Optional
 from .config import add_config_args, config_from_args
 
 
-_PREDICT_ARGS = ("input", "out_dir", "pred_tile", "overlap", "blend", "window_batch", "save_proba")
+_PREDICT_ARGS = ("input", "out_dir", "pred_tile", "overlap", "blend", "window_batch", "save_proba",
+                 "tta")
 
 
 def _rank0() -> bool:
@@ -58,6 +62,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     p_pred.add_argument("--blend", choices=("core", "cosine"), default="cosine")
     p_pred.add_argument("--window-batch", type=int, default=16)
     p_pred.add_argument("--save-proba", action="store_true")
+    p_pred.add_argument("--tta", choices=("none", "flip", "d4"), default="none",
+                        help="test-time augmentation: average every window over 4 / 8 symmetries")
     p_pred.add_argument("--device", default=None)
     add_config_args(sub.add_parser("config", help="print the resolved config as JSON"))
     args = ap.parse_args(argv)

@@ -20,6 +20,11 @@ blended.
   the logits never reach HBM; without it (stock fp32 modules, ``fused=False``) the same
   result is composed from ``model(x)``, ``torch.softmax`` and slice-adds.
   ``scene_finalize`` turns the accumulator into the class map and the confusion matrix.
+* Test-time augmentation (``tta="flip" | "d4"``): every window is predicted under 4 / 8
+  symmetries of the square (the codes of ``crop_gather``, ``symmetry_maps``), the class
+  probabilities are mapped back and averaged.  ``window_gather`` cuts the S views of a
+  window and ``head_predict_accum`` un-maps, sums and blends them with ONE read-modify-write
+  of the accumulator per window pixel.
 * ``predict`` is the entry point behind ``python -m ddlpc predict``.
 """
 from __future__ import annotations
@@ -35,6 +40,7 @@ import numpy as np
 import torch
 
 BLENDS = ("core", "cosine")
+TTA_CODES = {"none": (0,), "flip": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
 
 
 # ---------------------------------------------------------------------- plan and weights
@@ -90,6 +96,26 @@ def blend_weights(tile: int, overlap: int, blend: str = "cosine") -> torch.Tenso
     return torch.from_numpy(w.astype(np.float32))
 
 
+def symmetry_maps(tile: int, code: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Flat index maps of symmetry ``code`` (0..7, the convention of ``crop_gather``):
+    network-side pixel ``(oy, ox)`` is window-frame pixel ``(a, b) = (oy, ox)``; ``code & 4``:
+    swap ``a``, ``b``; ``code & 2``: ``a = tile - 1 - a``; ``code & 1``: ``b = tile - 1 - b``.
+    -> ``(fwd, inv)``, int64 ``[tile * tile]``: ``view.flat[q] = window.flat[fwd[q]]`` and
+    ``window.flat[n] = view.flat[inv[n]]``."""
+    if not 0 <= code <= 7:
+        raise ValueError(f"symmetry code must be in 0..7, got {code}")
+    oy, ox = torch.meshgrid(torch.arange(tile), torch.arange(tile), indexing="ij")
+    a, b = (ox, oy) if code & 4 else (oy, ox)
+    if code & 2:
+        a = tile - 1 - a
+    if code & 1:
+        b = tile - 1 - b
+    fwd = (a * tile + b).reshape(-1)
+    inv = torch.empty_like(fwd)
+    inv[fwd] = torch.arange(tile * tile)
+    return fwd, inv
+
+
 def acc_channels(classes: int) -> int:
     """Channels of the scene accumulator: the classes and the weight sum, padded to whole
     float4s (a pixel is 16-byte aligned)."""
@@ -103,10 +129,16 @@ class ScenePredictor:
     ``fused`` (default: whether the model has the operator engine attached) selects the
     one-kernel head + softmax + blend; ``fused=False`` is the unfused composition through
     ``model(x)`` (the test oracle, and the path of the stock modules).  ``autocast`` (an
-    attribute, default off) runs the stock modules under bf16 autocast."""
+    attribute, default off) runs the stock modules under bf16 autocast.
+
+    ``tta`` (``"none"``, ``"flip"``: symmetry codes 0..3, ``"d4"``: codes 0..7) averages the
+    class probabilities of every window over S symmetries.  ``window_batch`` stays the number
+    of network inputs per forward: a pass takes ``max(1, window_batch // S)`` windows.
+    ``windows`` counts the windows of the last scene, ``inputs`` its network inputs
+    (``windows * S``)."""
 
     def __init__(self, model, tile: int, overlap: Optional[int] = None, blend: str = "cosine",
-                 window_batch: int = 16, fused: Optional[bool] = None):
+                 window_batch: int = 16, fused: Optional[bool] = None, tta: str = "none"):
         if getattr(model, "dims", 2) != 2:
             raise ValueError("scene prediction supports 2-D models only")
         overlap = (tile // 4) & ~1 if overlap is None else int(overlap)
@@ -115,6 +147,8 @@ class ScenePredictor:
             raise ValueError(f"tile {tile} must be a multiple of 2**depth = {2 ** model.depth}")
         if window_batch < 1:
             raise ValueError("window_batch must be >= 1")
+        if tta not in TTA_CODES:
+            raise ValueError(f"tta must be one of {tuple(TTA_CODES)}, got {tta!r}")
         engine = getattr(model, "_engine", None)
         if fused is None:
             fused = engine is not None
@@ -130,7 +164,12 @@ class ScenePredictor:
         self.classes = int(model.conv_last.out_channels)
         self.in_channels = int(model.cfg.in_channels)
         self.win = blend_weights(tile, overlap, blend)
+        self.tta = tta
+        self.codes = TTA_CODES[tta]
         self.windows = 0                           # windows of the last scene
+        self.inputs = 0                            # network inputs of the last scene
+        self._codes: Dict[str, torch.Tensor] = {}
+        self._maps: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._plans: Dict[Tuple[int, int, str], list] = {}
 
     @property
@@ -168,12 +207,16 @@ class ScenePredictor:
         was_training = model.training
         model.eval()
         try:
-            self.windows = 0
+            self.windows = self.inputs = 0
+            if self.tta != "none":
+                self._accumulate_tta(sc, win, w2, acc)
+                return acc
             for host, origins in self._plan(H, W, dev):        # colour groups, in order
                 for i in range(0, len(host), self.window_batch):
                     o = origins[i:i + self.window_batch]
                     x = engine_input(F.window_gather(sc, o, self.tile, 8), self.in_channels)
                     self.windows += int(o.shape[0])
+                    self.inputs += int(o.shape[0])
                     if self.fused:
                         eng = model._engine
                         a, s = eng.features(x, defer_last=True)
@@ -186,16 +229,67 @@ class ScenePredictor:
             model.train(was_training)
         return acc
 
-    def _accumulate_unfused(self, x, origins, w2, acc):
-        model, K, t = self.model, self.classes, self.tile
-        H, W = acc.shape[0], acc.shape[1]
+    def _accumulate_tta(self, sc, win, w2, acc):
+        """The passes of a scene under ``self.codes``: ``max(1, window_batch // S)`` windows of
+        one colour per forward, S views each (window-major)."""
+        from .data.datasets import engine_input
+        F, model, t = self.ops, self.model, self.tile
+        dev = sc.device
+        S = len(self.codes)
+        per = max(1, self.window_batch // S)
+        if self.fused:
+            key = str(dev)
+            if key not in self._codes:
+                self._codes[key] = torch.tensor(self.codes, dtype=torch.int32, device=dev)
+            codes = self._codes[key]
+        else:
+            fwd, inv = self._symmetry_maps(dev)
+        for host, origins in self._plan(int(sc.shape[0]), int(sc.shape[1]), dev):
+            for i in range(0, len(host), per):
+                o = origins[i:i + per]
+                B = int(o.shape[0])
+                self.windows += B
+                self.inputs += B * S
+                if self.fused:
+                    x = engine_input(F.window_gather(sc, o, t, 8, codes), self.in_channels)
+                    eng = model._engine
+                    a, s = eng.features(x, defer_last=True)
+                    wh, bh = eng._head_params()
+                    F.head_predict_accum(a, wh.detach().contiguous(), bh.detach().contiguous(),
+                                         o, win, acc, s, codes)
+                else:
+                    # the views through the index maps, the probabilities mapped back and averaged
+                    xw = F.window_gather(sc, o, t, 8).reshape(B, t * t, 8)
+                    xv = xw[:, fwd].reshape(B * S, t, t, 8)          # fwd [S, t * t]: window-major
+                    p = self._proba(engine_input(xv, self.in_channels))       # [B * S, K, t, t]
+                    p = p.reshape(B, S, self.classes, t * t)
+                    mean = p.gather(3, inv[None, :, None, :].expand_as(p)).sum(1) / S
+                    self._slice_add(mean.reshape(B, self.classes, t, t) * w2, host[i:i + per], w2, acc)
+
+    def _symmetry_maps(self, dev):
+        key = str(dev)
+        if key not in self._maps:
+            maps = [symmetry_maps(self.tile, c) for c in self.codes]
+            self._maps[key] = (torch.stack([m[0] for m in maps]).to(dev),
+                               torch.stack([m[1] for m in maps]).to(dev))
+        return self._maps[key]
+
+    def _proba(self, x) -> torch.Tensor:
+        model = self.model
         if model._engine is None:
             x = x.to(next(model.parameters()).dtype)
         ctx = (torch.autocast(x.device.type, dtype=torch.bfloat16) if self.autocast
                else contextlib.nullcontext())
         with ctx:
             logits = model(x)
-        p = torch.softmax(logits.float(), dim=1) * w2            # [B, K, t, t]
+        return torch.softmax(logits.float(), dim=1)
+
+    def _accumulate_unfused(self, x, origins, w2, acc):
+        self._slice_add(self._proba(x) * w2, origins, w2, acc)  # [B, K, t, t]
+
+    def _slice_add(self, p, origins, w2, acc):
+        K, t = self.classes, self.tile
+        H, W = acc.shape[0], acc.shape[1]
         for b, (y0, x0) in enumerate(origins):
             ys, xs = max(0, -y0), max(0, -x0)
             ye, xe = min(t, H - y0), min(t, W - x0)
@@ -266,12 +360,14 @@ def list_scenes(inputs: str) -> Tuple[List[str], Optional[List[str]]]:
 
 def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[str] = None,
             pred_tile: Optional[int] = None, overlap: Optional[int] = None, blend: str = "cosine",
-            window_batch: int = 16, save_proba: bool = False) -> Dict[str, object]:
+            window_batch: int = 16, save_proba: bool = False, tta: str = "none") -> Dict[str, object]:
     """Predict every scene of ``inputs`` with the checkpoint's model.  Writes per scene
     ``<stem>.png`` (class indices), ``<stem>_color.png`` (Vaihingen palette, 6 classes) and
     optionally ``<stem>_proba.npy`` (fp16 ``[K, H, W]``), appends one line per scene to
-    ``out_dir/predict.jsonl`` and returns the summary.  Under ``torchrun`` scenes are sharded
-    ``i % world == rank``; only the confusion matrix (and the pixel count) is all-reduced."""
+    ``out_dir/predict.jsonl`` and returns the summary.  ``tta`` (``none``, ``flip``, ``d4``)
+    averages every window over the symmetries of the square (test-time augmentation).  Under
+    ``torchrun`` scenes are sharded ``i % world == rank``; only the confusion matrix (and the
+    pixel count) is all-reduced."""
     import torch.distributed as dist
     from PIL import Image
 
@@ -295,7 +391,7 @@ def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[st
         model.to_hip()
     elif dev.type == "cuda":
         model.to(memory_format=torch.channels_last)
-    sp = ScenePredictor(model, pred_tile or cfg.tile, overlap, blend, window_batch)
+    sp = ScenePredictor(model, pred_tile or cfg.tile, overlap, blend, window_batch, tta=tta)
     sp.autocast = dev.type == "cuda" and impl == "torch" and cfg.dtype == "bf16"
     K = sp.classes
     images, labels = list_scenes(inputs)
@@ -313,7 +409,7 @@ def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[st
             ms = (time.perf_counter() - t0) * 1e3
             H, W = int(pred.shape[0]), int(pred.shape[1])
             rec = {"name": os.path.basename(images[i]), "H": H, "W": W, "windows": sp.windows,
-                   "ms": ms}
+                   "ms": ms, "tta": tta}
             if cm is not None:
                 m = metrics_of(cm)
                 rec.update(pixel_acc=m["pixel_acc"], iou=m["iou"])
