@@ -1226,7 +1226,7 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
   TORCH_CHECK(head_supported(C, K), "head kernel: unsupported (C, K)");
   TORCH_CHECK(store_da || pbn != nullptr, "head_ce_bwd: store_da=False needs the deferred BN (bn4)");
   const long long P = a.numel() / C;
-  const int nb = head_ce_bwd_blocks(C, K, pbn != nullptr, P, num_cus());
+  const int nb = head_ce_bwd_blocks(C, K, P, num_cus());
   auto fopts = a.options().dtype(at::kFloat);
   // store_da=False: the stats pass of the two-pass backward (head_ce_bn_bwd writes dY)
   at::Tensor dA = store_da ? at::empty_like(a) : at::empty({0}, a.options());
@@ -1234,7 +1234,7 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
   // deferred BatchNorm input: the kernel also emits that BN's backward partial rows
   at::Tensor bnpart = pbn != nullptr ? at::empty({nb, 2, C}, fopts) : at::empty({0}, fopts);
   head_ce_bwd_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
-                     fptr_opt(gscale), out3.data_ptr<float>(), 0, store_da ? bptr_mut(dA) : nullptr,
+                     fptr_opt(gscale), out3.data_ptr<float>(), store_da ? bptr_mut(dA) : nullptr,
                      part.data_ptr<float>(), nb, P, C, K, (int)ignore_index, pbn,
                      pbn != nullptr ? bnpart.data_ptr<float>() : nullptr, cur_stream(),
                      class_weight_ptr(class_weight, a, K));
@@ -1709,7 +1709,8 @@ static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
 }
 
 // test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
-// in 0..7) -> S (0 without codes) and the codes packed 3 bits each, code j at bits 3 j.  The
+// in 0..7) -> S and the codes packed 3 bits each, code j at bits 3 j (without codes: S = 1, code
+// 0 — the plain window — with no device read).  The
 // values are checked on the host and reach the kernels as a launch argument: the list is read
 // back with one small blocking copy, once per tensor — the last checked list of a thread is
 // remembered (the tensor itself, so its memory cannot be handed out again, and its version
@@ -1724,7 +1725,7 @@ struct CodesSeen {
 }  // namespace
 static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& like, uint32_t* packed) {
   *packed = 0u;
-  if (!codes.has_value() || !codes->defined()) return 0;
+  if (!codes.has_value() || !codes->defined()) return 1;
   TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
   TORCH_CHECK(codes->device() == like.device(), "codes must be on the device of the other tensors");
   const int64_t S = codes->size(0);
@@ -1771,20 +1772,13 @@ at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int
   TORCH_CHECK(B < (1 << 30), "too many windows");
   uint32_t packed = 0u;
   const int S = pack_codes(codes, scene, &packed);
-  if (S > 0) {
-    const int64_t nb = window_gather_blocks((int)tile);
-    TORCH_CHECK(B * S * nb * nb < (1LL << 31), "window_gather: batch too large");
-    at::Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
-    if (B > 0)
-      window_gather_codes_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, S, packed,
-                                 (int)H, (int)W, (int)in_ch, (int)tile, (int)cpad,
-                                 knob("WINDOW_LDS_T", 1) != 0, bptr_mut(x), cur_stream());
-    return x;
-  }
-  at::Tensor x = at::empty({B, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
+  const int64_t nb = window_gather_blocks((int)tile);
+  TORCH_CHECK(B * S * nb * nb < (1LL << 31), "window_gather: batch too large");
+  at::Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
   if (B > 0)
-    window_gather_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, (int)H, (int)W,
-                         (int)in_ch, (int)tile, (int)cpad, bptr_mut(x), cur_stream());
+    window_gather_launch(scene.data_ptr<uint8_t>(), origins.data_ptr<int>(), (int)B, S, packed, (int)H,
+                         (int)W, (int)in_ch, (int)tile, (int)cpad, knob("WINDOW_LDS_T", 1) != 0,
+                         bptr_mut(x), cur_stream());
   return x;
 }
 
@@ -1798,8 +1792,8 @@ void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Ten
   TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2), "a must be [B, tile, tile, C]");
   uint32_t packed = 0u;
   const int S = pack_codes(codes, a, &packed);
-  TORCH_CHECK(S == 0 || a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
-  const int64_t B = S > 0 ? a.size(0) / S : a.size(0), tile = a.size(1);
+  TORCH_CHECK(a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
+  const int64_t B = a.size(0) / S, tile = a.size(1);
   const int C = (int)a.size(3);
   CHECK_DEV(Wh); CHECK_F32(Wh); CHECK_CONTIG(Wh); CHECK_DEV(bh); CHECK_F32(bh); CHECK_CONTIG(bh);
   TORCH_CHECK(Wh.dim() == 2 && Wh.size(1) == C && bh.numel() == Wh.size(0), "Wh [K, C] / bh [K]");
@@ -1820,16 +1814,9 @@ void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Ten
   c10::DeviceGuard guard(a.device());
   const float* pbn = bn4_ptr(bn4, C);
   if (B == 0) return;
-  if (S > 0) {
-    TORCH_CHECK(B * S < (1 << 30), "scene / window size out of range");
-    head_predict_accum_codes_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(),
-                                    origins.data_ptr<int>(), win.data_ptr<float>(), acc.data_ptr<float>(),
-                                    (int)B, S, packed, (int)tile, (int)acc.size(0), (int)acc.size(1),
-                                    (int)acc.size(2), C, K, pbn, cur_stream());
-    return;
-  }
+  TORCH_CHECK(B * S < (1 << 30), "scene / window size out of range");
   head_predict_accum_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), origins.data_ptr<int>(),
-                            win.data_ptr<float>(), acc.data_ptr<float>(), (int)B, (int)tile,
+                            win.data_ptr<float>(), acc.data_ptr<float>(), (int)B, S, packed, (int)tile,
                             (int)acc.size(0), (int)acc.size(1), (int)acc.size(2), C, K, pbn, cur_stream());
 }
 

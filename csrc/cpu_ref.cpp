@@ -991,10 +991,10 @@ int64_t reflect_index(int64_t i, int64_t n) {
 }
 
 // test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
-// in 0..7; the convention of crop_gather) -> the list, empty without codes
+// in 0..7; the convention of crop_gather) -> the list, {0} (the plain window) without codes
 std::vector<int> codes_of(const optional<Tensor>& codes) {
   std::vector<int> out;
-  if (!has(codes)) return out;
+  if (!has(codes)) return {0};
   TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
   TORCH_CHECK(codes->device().is_cpu(), "codes must be on the device of the other tensors");
   const int64_t S = codes->size(0);
@@ -1023,37 +1023,22 @@ Tensor window_gather(const Tensor& scene, const Tensor& origins, int64_t tile, i
   const uint8_t* sp = sc.data_ptr<uint8_t>();
   const int* op = oc.data_ptr<int>();
   const std::vector<int> cs = codes_of(codes);
-  if (!cs.empty()) {
-    const int64_t S = (int64_t)cs.size();
-    Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
-    auto* xp = x.data_ptr<c10::BFloat16>();
-    for (int64_t v = 0; v < B * S; ++v) {
-      const int64_t b = v / S;
-      const int code = cs[v - b * S];
-      for (int64_t oy = 0; oy < tile; ++oy)
-        for (int64_t ox = 0; ox < tile; ++ox) {
-          int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
-          if (code & 2) a = tile - 1 - a;
-          if (code & 1) c = tile - 1 - c;
-          const uint8_t* q = sp + (reflect_index(op[2 * b] + a, H) * W + reflect_index(op[2 * b + 1] + c, W)) * in_ch;
-          c10::BFloat16* o = xp + ((v * tile + oy) * tile + ox) * cpad;
-          for (int64_t ch = 0; ch < cpad; ++ch) o[ch] = c10::BFloat16(ch < in_ch ? (float)q[ch] / 255.0f : 0.f);
-        }
-    }
-    return x;
-  }
-  Tensor x = at::empty({B, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
+  const int64_t S = (int64_t)cs.size();
+  Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
   auto* xp = x.data_ptr<c10::BFloat16>();
-  for (int64_t b = 0; b < B; ++b)
-    for (int64_t wy = 0; wy < tile; ++wy) {
-      const int64_t sy = reflect_index(op[2 * b] + wy, H);
-      for (int64_t wx = 0; wx < tile; ++wx) {
-        const int64_t sx = reflect_index(op[2 * b + 1] + wx, W);
-        const uint8_t* q = sp + (sy * W + sx) * in_ch;
-        c10::BFloat16* o = xp + ((b * tile + wy) * tile + wx) * cpad;
-        for (int64_t c = 0; c < cpad; ++c) o[c] = c10::BFloat16(c < in_ch ? (float)q[c] / 255.0f : 0.f);
+  for (int64_t v = 0; v < B * S; ++v) {
+    const int64_t b = v / S;
+    const int code = cs[v - b * S];
+    for (int64_t oy = 0; oy < tile; ++oy)
+      for (int64_t ox = 0; ox < tile; ++ox) {
+        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+        if (code & 2) a = tile - 1 - a;
+        if (code & 1) c = tile - 1 - c;
+        const uint8_t* q = sp + (reflect_index(op[2 * b] + a, H) * W + reflect_index(op[2 * b + 1] + c, W)) * in_ch;
+        c10::BFloat16* o = xp + ((v * tile + oy) * tile + ox) * cpad;
+        for (int64_t ch = 0; ch < cpad; ++ch) o[ch] = c10::BFloat16(ch < in_ch ? (float)q[ch] / 255.0f : 0.f);
       }
-    }
+  }
   return x;
 }
 
@@ -1181,8 +1166,8 @@ void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, con
               "a must be bf16 [B, tile, tile, C]");
   const std::vector<int> cs = codes_of(codes);
   const int64_t S = (int64_t)cs.size();
-  TORCH_CHECK(S == 0 || a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
-  const int64_t B = S > 0 ? a.size(0) / S : a.size(0), tile = a.size(1), K = Wh.size(0);
+  TORCH_CHECK(a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
+  const int64_t B = a.size(0) / S, tile = a.size(1), K = Wh.size(0);
   TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(0) == B &&
               origins.size(1) == 2, "origins must be int32 [B, 2] (y0, x0)");
   TORCH_CHECK(win.scalar_type() == at::kFloat && win.dim() == 1 && win.size(0) == tile,
@@ -1200,57 +1185,34 @@ void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, con
   const int* op = oc.data_ptr<int>();
   const float* wp = wc.data_ptr<float>();
   float* ap = acc.data_ptr<float>();
-  if (S > 0) {
-    // one update per window-frame pixel (wa, wb): the S views through the inverse index map,
-    // their softmaxes summed in ascending j, acc += (w2 / S) * sum
-    const float fS = (float)S;
-    for (int64_t b = 0; b < B; ++b)
-      for (int64_t wa = 0; wa < tile; ++wa) {
-        const int64_t sy = op[2 * b] + wa;
-        if (sy < 0 || sy >= H) continue;
-        for (int64_t wb = 0; wb < tile; ++wb) {
-          const int64_t sx = op[2 * b + 1] + wb;
-          const float w2 = wp[wa] * wp[wb];
-          if (sx < 0 || sx >= W || w2 == 0.f) continue;
-          float sum[16];
-          for (int64_t j = 0; j < S; ++j) {
-            const int code = cs[j];
-            const int64_t ia = (code & 2) ? tile - 1 - wa : wa, ib = (code & 1) ? tile - 1 - wb : wb;
-            const int64_t oy = (code & 4) ? ib : ia, ox = (code & 4) ? ia : ib;
-            const float* z = lp + (((b * S + j) * tile + oy) * tile + ox) * K;
-            float m = z[0], e[16], se = 0.f;
-            for (int64_t k = 1; k < K; ++k) m = std::max(m, z[k]);
-            for (int64_t k = 0; k < K; ++k) {
-              e[k] = std::exp(z[k] - m);
-              se += e[k];
-            }
-            for (int64_t k = 0; k < K; ++k) sum[k] = j == 0 ? e[k] / se : sum[k] + e[k] / se;
-          }
-          const float wS = w2 / fS;
-          float* o = ap + (sy * W + sx) * KA;
-          for (int64_t k = 0; k < K; ++k) o[k] += wS * sum[k];
-          o[K] += w2;
-        }
-      }
-    return;
-  }
+  // one update per window-frame pixel (wa, wb): the S views through the inverse index map,
+  // their softmaxes summed in ascending j, acc += (w2 / S) * sum
+  const float fS = (float)S;
   for (int64_t b = 0; b < B; ++b)
-    for (int64_t wy = 0; wy < tile; ++wy) {
-      const int64_t sy = op[2 * b] + wy;
+    for (int64_t wa = 0; wa < tile; ++wa) {
+      const int64_t sy = op[2 * b] + wa;
       if (sy < 0 || sy >= H) continue;
-      for (int64_t wx = 0; wx < tile; ++wx) {
-        const int64_t sx = op[2 * b + 1] + wx;
-        const float w2 = wp[wy] * wp[wx];
+      for (int64_t wb = 0; wb < tile; ++wb) {
+        const int64_t sx = op[2 * b + 1] + wb;
+        const float w2 = wp[wa] * wp[wb];
         if (sx < 0 || sx >= W || w2 == 0.f) continue;
-        const float* z = lp + ((b * tile + wy) * tile + wx) * K;
-        float m = z[0], e[16], se = 0.f;
-        for (int64_t k = 1; k < K; ++k) m = std::max(m, z[k]);
-        for (int64_t k = 0; k < K; ++k) {
-          e[k] = std::exp(z[k] - m);
-          se += e[k];
+        float sum[16];
+        for (int64_t j = 0; j < S; ++j) {
+          const int code = cs[j];
+          const int64_t ia = (code & 2) ? tile - 1 - wa : wa, ib = (code & 1) ? tile - 1 - wb : wb;
+          const int64_t oy = (code & 4) ? ib : ia, ox = (code & 4) ? ia : ib;
+          const float* z = lp + (((b * S + j) * tile + oy) * tile + ox) * K;
+          float m = z[0], e[16], se = 0.f;
+          for (int64_t k = 1; k < K; ++k) m = std::max(m, z[k]);
+          for (int64_t k = 0; k < K; ++k) {
+            e[k] = std::exp(z[k] - m);
+            se += e[k];
+          }
+          for (int64_t k = 0; k < K; ++k) sum[k] = j == 0 ? e[k] / se : sum[k] + e[k] / se;
         }
+        const float wS = w2 / fS;
         float* o = ap + (sy * W + sx) * KA;
-        for (int64_t k = 0; k < K; ++k) o[k] += w2 * (e[k] / se);
+        for (int64_t k = 0; k < K; ++k) o[k] += wS * sum[k];
         o[K] += w2;
       }
     }

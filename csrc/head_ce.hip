@@ -45,9 +45,9 @@ constexpr int MAXC = 64, MAXK = 16;
 // scale [C] | shift [C] in LDS) the tensor holds the block's PRE-BN conv output y and the
 // activation relu(y*scale + shift) is formed here, rounded to bf16 exactly as a
 // materialised activation would be — the last decoder block never writes it to HBM.
+// (the first form takes the 16 bytes already loaded)
 template <int C, bool DEFER>
-DDLPC_DEVICE void act8(const bf16_t* ap, int c8, const float* sBN, float (&f)[8]) {
-  const uint4 v = *reinterpret_cast<const uint4*>(ap + c8);
+DDLPC_DEVICE void act8(const uint4 v, int c8, const float* sBN, float (&f)[8]) {
   unpack8(v, f);
   if (DEFER) {
     // opaque LDS offset: the compiler would otherwise hoist all 2*C constants out of the
@@ -57,6 +57,10 @@ DDLPC_DEVICE void act8(const bf16_t* ap, int c8, const float* sBN, float (&f)[8]
     for (int j = 0; j < 8; ++j) f[j] = fmaxf(fmaf(f[j], vb[c8 + j], vb[C + c8 + j]), 0.f);
     unpack8(pack8(f), f);
   }
+}
+template <int C, bool DEFER>
+DDLPC_DEVICE void act8(const bf16_t* ap, int c8, const float* sBN, float (&f)[8]) {
+  act8<C, DEFER>(*reinterpret_cast<const uint4*>(ap + c8), c8, sBN, f);
 }
 
 // stage Wh [K][C] / bh [K] into LDS as KP padded rows
@@ -1012,84 +1016,30 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const bf16_t* __restri
 // (KA = 4 ceil((K + 1) / 4): one pixel = KA / 4 aligned float4s) in one pass — the logits
 // never reach HBM.  Window b covers scene rows origins[b][0] .. + tile, columns
 // origins[b][1] .. + tile; a window pixel inside the scene with weight w2 = win[y] * win[x]
-// != 0 adds w2 * softmax_k to channel k < K and w2 to channel K; channels above K keep their
-// bits, every other pixel is not touched.  The windows of one launch are pairwise disjoint
-// (the colour plan), so a scene pixel belongs to at most one thread: plain read-modify-write,
-// no atomics, the same bits on every run.  (With symmetry codes — test-time augmentation —
-// head_predict_accum_codes_kernel below blends the S views of a window in the same pass.)
-template <int C, int K, bool DEFER>
-__global__ __launch_bounds__(256) void head_predict_accum_kernel(
-    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
-    const int* __restrict__ origins, const float* __restrict__ win, float* __restrict__ acc,
-    long long P, int tile, int H, int W, int KA, const float* __restrict__ bn4, int Kreal) {
-  __shared__ __attribute__((aligned(16))) float sBNm[4 * C];
-  __shared__ float sW[K * C], sb[K];
-  load_head<C, K>(Wh, bh, Kreal, sW, sb);
-  const float* sBN = DEFER ? load_bn<C>(bn4, sBNm, false) : nullptr;
-  __syncthreads();
-  const int S = tile * tile;
-#pragma unroll 1
-  for (long long px = blockIdx.x * (long long)blockDim.x + threadIdx.x; px < P;
-       px += (long long)gridDim.x * blockDim.x) {
-    const int b = (int)(px / S);
-    const int p = (int)(px - (long long)b * S);
-    const int wy = p / tile, wx = p - wy * tile;
-    const int sy = origins[2 * b] + wy, sx = origins[2 * b + 1] + wx;
-    const float w2 = win[wy] * win[wx];
-    if (sy < 0 || sy >= H || sx < 0 || sx >= W || w2 == 0.f) continue;
-    float z[K];
-    logits_of<C, K, DEFER>(a + px * C, sW, sb, sBN, z);
-    float m = z[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k) m = fmaxf(m, z[k]);
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = __expf(z[k] - m);
-      se += z[k];
-    }
-    const float ws = w2 / se;
-    float4* ap = reinterpret_cast<float4*>(acc + ((long long)sy * W + sx) * KA);
-#pragma unroll
-    for (int q = 0; q < (K + 4) / 4; ++q) {
-      if (4 * q < KA) {
-        const float4 v = ap[q];
-        float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          constexpr int kmax = K - 1;
-          const int k = 4 * q + j;
-          const float pk = ws * z[k < K ? k : kmax];
-          if (k < Kreal) f[j] += pk;
-          else if (k == Kreal) f[j] += w2;
-        }
-        ap[q] = make_float4(f[0], f[1], f[2], f[3]);
-      }
-    }
-  }
-}
-
-// Test-time augmentation: a [B * S][tile][tile][C] holds S views of every window, window-major,
-// view j of a window predicted under symmetry code j of `codes` (3 bits per code, code j at
+// != 0 adds w2 * (the mean softmax_k of its views) to channel k < K and w2 to channel K;
+// channels above K keep their bits, every other pixel is not touched.
+// a [B * S][tile][tile][C] holds S views of every window, window-major, view j of a window
+// predicted under symmetry code j of `codes` (test-time augmentation; 3 bits per code, code j at
 // bits 3 j; the convention of crop_gather / window_gather: network-side pixel (oy, ox) is
 // window-frame pixel (wa, wb) = (oy, ox); code & 4: swap; code & 2: wa = tile - 1 - wa;
-// code & 1: wb = tile - 1 - wb).  One thread owns one WINDOW-FRAME pixel (wa, wb) of one
-// window: it reads its S activations through the inverse map, computes the S softmaxes
-// (e_jk = exp(logit - max), se_j their sum), sums the views before the last in ascending j
-// (r_k = sum_{j < S - 1} (w2 / S) / se_j * e_jk, an fma chain from -0) and does ONE
-// read-modify-write of the scene pixel: acc[.., k] = fma((w2 / S) / se_last, e_last,k,
-// acc[.., k] + r_k), acc[.., K] += w2 — the accumulator traffic of one view, not of S.  The
-// S views of a window belong to one thread and the windows of a launch are disjoint: no
-// atomics, the same bits on every run.  Lanes run along wb: the accumulator and the
+// code & 1: wb = tile - 1 - wb).  A call without codes is S = 1, code 0.  One thread owns one
+// WINDOW-FRAME pixel (wa, wb) of one window: it reads its S activations through the inverse
+// map, computes the S softmaxes (e_jk = exp(logit - max), se_j their sum), sums the views
+// before the last in ascending j (r_k = sum_{j < S - 1} (w2 / S) / se_j * e_jk, an fma chain
+// from -0) and does ONE read-modify-write of the scene pixel: acc[.., k] =
+// fma((w2 / S) / se_last, e_last,k, acc[.., k] + r_k), acc[.., K] += w2 — the accumulator
+// traffic of one view, not of S.  With one view this is acc[.., k] += (w2 / se) * e_k in a single
+// fused multiply-add: w2 / 1 = w2 and x + -0 = x are exact.
+// The windows of one launch are pairwise disjoint (the colour plan) and the S views of a window
+// belong to one thread, so a scene pixel belongs to at most one thread: plain read-modify-write,
+// no atomics, the same bits on every run.  Lanes run along wb: the accumulator and the
 // non-transposing views are read along rows; a transposing view is read with a stride of one
 // activation row between lanes, whole 2 C-byte pixels each.  A thread works through its S
 // views one after the other, so each view's pixel is requested 64 bytes at a time before its
 // first use (with logits_of's one 16-byte load in flight the kernel ran at 0.82 of S
 // single-view launches instead of 0.57, docs/PERF.md).
-// S = 1, code 0 gives the bits of head_predict_accum_kernel: w2 / 1 = w2, x + -0 = x, and the
-// last view is added with the fused multiply-add that kernel's `f += ws * z` compiles to.
 template <int C, int K, bool DEFER>
-__global__ __launch_bounds__(256) void head_predict_accum_codes_kernel(
+__global__ __launch_bounds__(256) void head_predict_accum_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int* __restrict__ origins, const float* __restrict__ win, float* __restrict__ acc,
     long long P, int S, uint32_t codes, int tile, int H, int W, int KA,
@@ -1139,13 +1089,7 @@ __global__ __launch_bounds__(256) void head_predict_accum_codes_kernel(
         for (int i = 0; i < CH / 8; ++i) {
           const int c8 = c0 + 8 * i;
           float f[8];
-          unpack8(row[i], f);
-          if (DEFER) {
-            const float* vn = sBN + opaque_zero();
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) f[jj] = fmaxf(fmaf(f[jj], vn[c8 + jj], vn[C + c8 + jj]), 0.f);
-            unpack8(pack8(f), f);
-          }
+          act8<C, DEFER>(row[i], c8, sBN, f);
 #pragma unroll
           for (int k = 0; k < K; ++k)
 #pragma unroll
@@ -1210,6 +1154,12 @@ __global__ __launch_bounds__(256) void head_predict_accum_codes_kernel(
     else { return false; }                                                          \
     return true;                                                                    \
   }()
+// ... and DD: the deferred BatchNorm on load, chosen by bn4 != nullptr
+#define HEAD_SWITCH_D(C_, K_, bn4_, ...)                                                       \
+  do {                                                                                         \
+    if ((bn4_) != nullptr) HEAD_SWITCH(C_, K_, { constexpr bool DD = true; __VA_ARGS__; });    \
+    else HEAD_SWITCH(C_, K_, { constexpr bool DD = false; __VA_ARGS__; });                     \
+  } while (0)
 
 // the C = 32 kernels with (WT = true) and without the class-weight factor
 #define HEAD32_WT(cw_, ...)                                  \
@@ -1227,12 +1177,8 @@ bool head_supported(int C, int K) {
 void head_ce_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         float* partial, float* out3, const float* bn4, int nblocks, long long P,
                         int C, int K, int ignore_index, hipStream_t st, const float* cw) {
-  if (bn4 != nullptr)
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_fwd_kernel<CC, KK, true>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K, cw));
-  else
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_fwd_kernel<CC, KK, false>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K, cw));
+  HEAD_SWITCH_D(C, K, bn4, hipLaunchKernelGGL((head_ce_fwd_kernel<CC, KK, DD>), dim3(nblocks), dim3(256), 0,
+                                              st, a, Wh, bh, labels, partial, P, ignore_index, bn4, K, cw));
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblocks, out3);
 }
 
@@ -1260,7 +1206,7 @@ int head32_bwd_per_cu() {
 }
 }  // namespace
 
-int head_ce_bwd_blocks(int C, int K, bool /*defer*/, long long P, int num_cus) {
+int head_ce_bwd_blocks(int C, int K, long long P, int num_cus) {
   // C = 32: the MFMA kernels — the same grid for every variant, so the deferred / plain /
   // stats-only paths reduce dWh in the same order (bit-identical weight gradients)
   if (C == 32) return head32_grid(P, head32_bwd_per_cu(), num_cus);
@@ -1280,10 +1226,9 @@ int head_ce_bwd_blocks(int C, int K, bool /*defer*/, long long P, int num_cus) {
 }
 
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
-                        const float* gscale, const float* stats3, int /*unused*/, bf16_t* dA,
-                        float* dW_partial, int nblocks, long long P, int C, int K,
-                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st,
-                        const float* cw) {
+                        const float* gscale, const float* stats3, bf16_t* dA, float* dW_partial,
+                        int nblocks, long long P, int C, int K, int ignore_index, const float* bn4,
+                        float* bnpart, hipStream_t st, const float* cw) {
   if (C == 32 && K <= MAXK) {
 #define HEAD32_BWD(D_, S_)                                                                          \
   HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<D_, S_, false, WT>), dim3(nblocks), dim3(256), 0, st, a, Wh, \
@@ -1295,18 +1240,14 @@ void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const
 #undef HEAD32_BWD
     return;
   }
+#define HEAD_BWD(...)                                                                              \
+  hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, __VA_ARGS__>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, \
+                     labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, cw)
   if (bn4 != nullptr && dA == nullptr)               // stats pass of the two-pass backward
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true, false>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K, nullptr, cw));
-  else if (bn4 != nullptr)
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K, nullptr, cw));
+    HEAD_SWITCH(C, K, HEAD_BWD(true, false));
   else
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, false>), dim3(nblocks), dim3(256), 0,
-                                         st, a, Wh, bh, labels, gscale, stats3, dA, dW_partial, P,
-                                         ignore_index, bn4, bnpart, K, nullptr, cw));
+    HEAD_SWITCH_D(C, K, bn4, HEAD_BWD(DD));
+#undef HEAD_BWD
 }
 
 // the fused forward + statistics pass: head32_kernel<.., LOSS> for C = 32, else the
@@ -1317,7 +1258,7 @@ int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups) {
     const int nb = head32_grid(P, n, num_cus);
     return groups > 1 ? groups * std::max(1, nb / groups) : nb;   // (groups x Rb, group-major)
   }
-  return head_ce_bwd_blocks(C, K, true, P, num_cus);
+  return head_ce_bwd_blocks(C, K, P, num_cus);
 }
 
 void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
@@ -1365,41 +1306,18 @@ void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, con
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st) {
   const int grid = (int)std::min<long long>((P + 255) / 256, 4096);
-  if (bn4 != nullptr)
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_logits_kernel<CC, KK, true>), dim3(grid), dim3(256), 0, st,
-                                         a, Wh, bh, logits, P, HW, bn4, K));
-  else
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_logits_kernel<CC, KK, false>), dim3(grid), dim3(256), 0, st,
-                                         a, Wh, bh, logits, P, HW, bn4, K));
+  HEAD_SWITCH_D(C, K, bn4, hipLaunchKernelGGL((head_logits_kernel<CC, KK, DD>), dim3(grid), dim3(256), 0, st,
+                                              a, Wh, bh, logits, P, HW, bn4, K));
 }
 
 void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh, const int* origins,
-                               const float* win, float* acc, int B, int tile, int H, int W, int KA,
-                               int C, int K, const float* bn4, hipStream_t st) {
-  const long long P = (long long)B * tile * tile;
-  const int grid = (int)std::min<long long>((P + 255) / 256, 4096);
-  if (bn4 != nullptr)
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, true>), dim3(grid), dim3(256),
-                                         0, st, a, Wh, bh, origins, win, acc, P, tile, H, W, KA, bn4, K));
-  else
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, false>), dim3(grid), dim3(256),
-                                         0, st, a, Wh, bh, origins, win, acc, P, tile, H, W, KA, bn4, K));
-}
-
-void head_predict_accum_codes_launch(const bf16_t* a, const float* Wh, const float* bh,
-                                     const int* origins, const float* win, float* acc, int B, int S,
-                                     uint32_t codes, int tile, int H, int W, int KA, int C, int K,
-                                     const float* bn4, hipStream_t st) {
+                               const float* win, float* acc, int B, int S, uint32_t codes, int tile,
+                               int H, int W, int KA, int C, int K, const float* bn4, hipStream_t st) {
   const long long P = (long long)B * tile * tile;        // threads: window-frame pixels
   const int grid = (int)std::min<long long>((P + 255) / 256, 4096);
-  if (bn4 != nullptr)
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_codes_kernel<CC, KK, true>), dim3(grid),
-                                         dim3(256), 0, st, a, Wh, bh, origins, win, acc, P, S, codes,
-                                         tile, H, W, KA, bn4, K));
-  else
-    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_predict_accum_codes_kernel<CC, KK, false>), dim3(grid),
-                                         dim3(256), 0, st, a, Wh, bh, origins, win, acc, P, S, codes,
-                                         tile, H, W, KA, bn4, K));
+  HEAD_SWITCH_D(C, K, bn4, hipLaunchKernelGGL((head_predict_accum_kernel<CC, KK, DD>), dim3(grid), dim3(256),
+                                              0, st, a, Wh, bh, origins, win, acc, P, S, codes, tile, H, W,
+                                              KA, bn4, K));
 }
 
 }  // namespace ddlpc

@@ -255,16 +255,15 @@ void head_ce_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const
                         int C, int K, int ignore_index, hipStream_t st, const float* cw = nullptr);
 // bnpart (with bn4): [nblocks][2][C] BatchNorm-backward partial rows of the stored dA;
 // nblocks from head_ce_bwd_blocks (one persistent wave of workgroups)
-int head_ce_bwd_blocks(int C, int K, bool defer, long long P, int num_cus);
+int head_ce_bwd_blocks(int C, int K, long long P, int num_cus);
 // groups > 1 (C = 32 head only): a batched window whose deferred BatchNorm has per-group
 // statistics — group-major workgroups (grid = groups x Rb, BN partial rows [groups][Rb][2][C]),
 // bn4 [groups][4][C], coefs [groups][3][C]; pixels per group a multiple of 16
 int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups = 1);
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
-                        const float* gscale, const float* stats3, int unused, bf16_t* dA,
-                        float* dW_partial, int nblocks, long long P, int C, int K,
-                        int ignore_index, const float* bn4, float* bnpart, hipStream_t st,
-                        const float* cw = nullptr);
+                        const float* gscale, const float* stats3, bf16_t* dA, float* dW_partial,
+                        int nblocks, long long P, int C, int K, int ignore_index, const float* bn4,
+                        float* bnpart, hipStream_t st, const float* cw = nullptr);
 // two-pass backward with the deferred BatchNorm of the last decoder block: dA == nullptr in
 // head_ce_bwd_launch runs the stats pass (dWh, dbh, BN partials); this second pass
 // recomputes dA and writes that BatchNorm's dY (coefs = [k | m1 | m2] x C); its C = 32 grid
@@ -284,24 +283,20 @@ void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, con
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
 // whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the
-// scene accumulator acc [H][W][KA]; origins [B][2] = (y0, x0), win [tile] blend weights
+// scene accumulator acc [H][W][KA]; origins [B][2] = (y0, x0), win [tile] blend weights;
+// a [B * S][tile][tile][C], window-major views under the symmetry codes packed 3 bits each in
+// `codes` (code j at bits 3 j; S = 1, codes = 0 without test-time augmentation); one
+// read-modify-write per pixel
 void head_predict_accum_launch(const bf16_t* a, const float* Wh, const float* bh, const int* origins,
-                               const float* win, float* acc, int B, int tile, int H, int W, int KA,
-                               int C, int K, const float* bn4, hipStream_t st);
-// test-time augmentation: a [B * S][tile][tile][C], window-major views under the symmetry
-// codes packed 3 bits each in `codes` (code j at bits 3 j); one read-modify-write per pixel
-void head_predict_accum_codes_launch(const bf16_t* a, const float* Wh, const float* bh,
-                                     const int* origins, const float* win, float* acc, int B, int S,
-                                     uint32_t codes, int tile, int H, int W, int KA, int C, int K,
-                                     const float* bn4, hipStream_t st);
+                               const float* win, float* acc, int B, int S, uint32_t codes, int tile,
+                               int H, int W, int KA, int C, int K, const float* bn4, hipStream_t st);
 
 // ---------------------------------------------------------------- scene prediction (scene.hip)
-void window_gather_launch(const uint8_t* scene, const int* origins, int B, int H, int W, int in_ch,
-                          int tile, int cpad, bf16_t* x, hipStream_t st);
 int window_gather_blocks(int tile);   // workgroups per output row / column of one view
-void window_gather_codes_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
-                                int H, int W, int in_ch, int tile, int cpad, bool lds_transpose,
-                                bf16_t* x, hipStream_t st);
+// S views per window under the packed symmetry codes (S = 1, codes = 0: the plain windows)
+void window_gather_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
+                          int H, int W, int in_ch, int tile, int cpad, bool lds_transpose, bf16_t* x,
+                          hipStream_t st);
 void scene_finalize_launch(const float* acc, long long P, int K, int KA, const uint8_t* labels,
                            int ignore_index, uint8_t* pred, int64_t* cm, hipStream_t st);
 

@@ -8,10 +8,9 @@
 //     windows (origins may be negative / overhang: the scene is mirrored at its borders,
 //     edge pixel not repeated) is cut out directly in the first conv's input layout —
 //     channel-last bf16, /255 by IEEE division as tile_gather_kernel, channels zero-padded to
-//     cpad (8 = one 16-byte store per pixel).
-//   * window_gather_codes_kernel: the same cut under a list of symmetry codes (test-time
-//     augmentation): S views per window, window-major, the values of window_gather_kernel
-//     read through crop_gather's index map.
+//     cpad (8 = one 16-byte store per pixel).  With a list of symmetry codes (test-time
+//     augmentation) it cuts S views per window, window-major, read through crop_gather's
+//     index map; a call without codes is the list {0}.
 //   * scene_finalize_kernel: accumulator [H, W, KA] -> uint8 class map (arg-max over the K
 //     class channels, lowest class on ties) and, with labels, the K x K confusion matrix:
 //     counted per workgroup in LDS, then added to HBM with integer atomics (integer sums do
@@ -23,33 +22,7 @@ namespace ddlpc {
 
 namespace {
 
-__global__ __launch_bounds__(256) void window_gather_kernel(
-    const uint8_t* __restrict__ scene, const int* __restrict__ origins, int B, int H, int W,
-    int in_ch, int tile, int cpad, bf16_t* __restrict__ x) {
-  const long long S = (long long)tile * tile;
-  const long long total = (long long)B * S;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int b = (int)(e / S);
-    const int p = (int)(e - (long long)b * S);
-    const int wy = p / tile, wx = p - wy * tile;
-    const int sy = reflect_index(origins[2 * b] + wy, H);
-    const int sx = reflect_index(origins[2 * b + 1] + wx, W);
-    const uint8_t* sp = scene + ((long long)sy * W + sx) * in_ch;
-    float f[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) f[c] = c < in_ch ? __fdiv_rn((float)sp[c], 255.0f) : 0.f;
-    if (cpad == 8) {
-      reinterpret_cast<uint4*>(x)[e] = pack8(f);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; ++c)
-        if (c < cpad) x[e * cpad + c] = f2bf(f[c]);
-    }
-  }
-}
-
-// Test-time augmentation: window b under symmetry code c (the convention of crop_gather,
+// Window b under symmetry code c (test-time augmentation; the convention of crop_gather,
 // data.hip: network-side pixel (oy, ox) reads window-frame pixel (a, b) = (oy, ox); c & 4:
 // swap a, b; c & 2: a = tile - 1 - a; c & 1: b = tile - 1 - b; scene pixel (y0 + a, x0 + b),
 // mirrored).  Output [B * S, tile, tile, cpad], window-major: row b * S + j is window b under
@@ -69,7 +42,7 @@ DDLPC_DEVICE int reflect_in(int i, int n) {
 }
 
 template <bool LDS_T>
-__global__ __launch_bounds__(256) void window_gather_codes_kernel(
+__global__ __launch_bounds__(256) void window_gather_kernel(
     const uint8_t* __restrict__ scene, const int* __restrict__ origins, int S, uint32_t codes, int H,
     int W, int nb, int in_ch, int tile, int cpad, bf16_t* __restrict__ x) {
   __shared__ uint2 s_px[kWinBS][kWinBS + 1];
@@ -175,17 +148,11 @@ int scene_grid(long long total) {
 
 }  // namespace
 
-void window_gather_launch(const uint8_t* scene, const int* origins, int B, int H, int W, int in_ch,
-                          int tile, int cpad, bf16_t* x, hipStream_t st) {
-  hipLaunchKernelGGL(window_gather_kernel, dim3(scene_grid((long long)B * tile * tile)), dim3(256),
-                     0, st, scene, origins, B, H, W, in_ch, tile, cpad, x);
-}
-
 int window_gather_blocks(int tile) { return (tile + kWinBS - 1) / kWinBS; }
 
-void window_gather_codes_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
-                                int H, int W, int in_ch, int tile, int cpad, bool lds_transpose,
-                                bf16_t* x, hipStream_t st) {
+void window_gather_launch(const uint8_t* scene, const int* origins, int B, int S, uint32_t codes,
+                          int H, int W, int in_ch, int tile, int cpad, bool lds_transpose, bf16_t* x,
+                          hipStream_t st) {
   const int nb = window_gather_blocks(tile);
   const dim3 grid((unsigned)((long long)B * S * nb * nb));
   // a list without a transposing code never stages: the direct kernel runs the same
@@ -193,10 +160,10 @@ void window_gather_codes_launch(const uint8_t* scene, const int* origins, int B,
   bool transposing = false;
   for (int j = 0; j < S; ++j) transposing |= ((codes >> (3 * j)) & 4u) != 0;
   if (lds_transpose && transposing)
-    hipLaunchKernelGGL(window_gather_codes_kernel<true>, grid, dim3(256), 0, st, scene, origins, S,
+    hipLaunchKernelGGL(window_gather_kernel<true>, grid, dim3(256), 0, st, scene, origins, S,
                        codes, H, W, nb, in_ch, tile, cpad, x);
   else
-    hipLaunchKernelGGL(window_gather_codes_kernel<false>, grid, dim3(256), 0, st, scene, origins, S,
+    hipLaunchKernelGGL(window_gather_kernel<false>, grid, dim3(256), 0, st, scene, origins, S,
                        codes, H, W, nb, in_ch, tile, cpad, x);
 }
 

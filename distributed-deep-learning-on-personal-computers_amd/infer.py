@@ -207,64 +207,38 @@ class ScenePredictor:
         was_training = model.training
         model.eval()
         try:
+            # a pass: ``per`` windows of one colour per forward, S views each (window-major)
+            S = len(self.codes)
+            per = max(1, self.window_batch // S)
+            # (no codes tensor without augmentation: the ops then take code 0 with no host copy;
+            # the unfused side always cuts plain windows)
+            codes = self._codes_tensor(dev) if self.fused and self.tta != "none" else None
             self.windows = self.inputs = 0
-            if self.tta != "none":
-                self._accumulate_tta(sc, win, w2, acc)
-                return acc
             for host, origins in self._plan(H, W, dev):        # colour groups, in order
-                for i in range(0, len(host), self.window_batch):
-                    o = origins[i:i + self.window_batch]
-                    x = engine_input(F.window_gather(sc, o, self.tile, 8), self.in_channels)
+                for i in range(0, len(host), per):
+                    o, ho = origins[i:i + per], host[i:i + per]
                     self.windows += int(o.shape[0])
-                    self.inputs += int(o.shape[0])
+                    self.inputs += int(o.shape[0]) * S
+                    xw = F.window_gather(sc, o, self.tile, 8, codes)
                     if self.fused:
                         eng = model._engine
-                        a, s = eng.features(x, defer_last=True)
+                        a, s = eng.features(engine_input(xw, self.in_channels), defer_last=True)
                         wh, bh = eng._head_params()
                         F.head_predict_accum(a, wh.detach().contiguous(), bh.detach().contiguous(),
-                                             o, win, acc, s)
+                                             o, win, acc, s, codes)
+                    elif self.tta == "none":
+                        self._accumulate_unfused(engine_input(xw, self.in_channels), ho, w2, acc)
                     else:
-                        self._accumulate_unfused(x, host[i:i + self.window_batch], w2, acc)
+                        self._accumulate_unfused_tta(xw, ho, w2, acc)
         finally:
             model.train(was_training)
         return acc
 
-    def _accumulate_tta(self, sc, win, w2, acc):
-        """The passes of a scene under ``self.codes``: ``max(1, window_batch // S)`` windows of
-        one colour per forward, S views each (window-major)."""
-        from .data.datasets import engine_input
-        F, model, t = self.ops, self.model, self.tile
-        dev = sc.device
-        S = len(self.codes)
-        per = max(1, self.window_batch // S)
-        if self.fused:
-            key = str(dev)
-            if key not in self._codes:
-                self._codes[key] = torch.tensor(self.codes, dtype=torch.int32, device=dev)
-            codes = self._codes[key]
-        else:
-            fwd, inv = self._symmetry_maps(dev)
-        for host, origins in self._plan(int(sc.shape[0]), int(sc.shape[1]), dev):
-            for i in range(0, len(host), per):
-                o = origins[i:i + per]
-                B = int(o.shape[0])
-                self.windows += B
-                self.inputs += B * S
-                if self.fused:
-                    x = engine_input(F.window_gather(sc, o, t, 8, codes), self.in_channels)
-                    eng = model._engine
-                    a, s = eng.features(x, defer_last=True)
-                    wh, bh = eng._head_params()
-                    F.head_predict_accum(a, wh.detach().contiguous(), bh.detach().contiguous(),
-                                         o, win, acc, s, codes)
-                else:
-                    # the views through the index maps, the probabilities mapped back and averaged
-                    xw = F.window_gather(sc, o, t, 8).reshape(B, t * t, 8)
-                    xv = xw[:, fwd].reshape(B * S, t, t, 8)          # fwd [S, t * t]: window-major
-                    p = self._proba(engine_input(xv, self.in_channels))       # [B * S, K, t, t]
-                    p = p.reshape(B, S, self.classes, t * t)
-                    mean = p.gather(3, inv[None, :, None, :].expand_as(p)).sum(1) / S
-                    self._slice_add(mean.reshape(B, self.classes, t, t) * w2, host[i:i + per], w2, acc)
+    def _codes_tensor(self, dev):
+        key = str(dev)
+        if key not in self._codes:
+            self._codes[key] = torch.tensor(self.codes, dtype=torch.int32, device=dev)
+        return self._codes[key]
 
     def _symmetry_maps(self, dev):
         key = str(dev)
@@ -286,6 +260,19 @@ class ScenePredictor:
 
     def _accumulate_unfused(self, x, origins, w2, acc):
         self._slice_add(self._proba(x) * w2, origins, w2, acc)  # [B, K, t, t]
+
+    def _accumulate_unfused_tta(self, xw, origins, w2, acc):
+        """The plain windows ``xw`` under ``self.codes``: the views through the index maps, the
+        probabilities mapped back and averaged."""
+        from .data.datasets import engine_input
+        t, S = self.tile, len(self.codes)
+        B = int(xw.shape[0])
+        fwd, inv = self._symmetry_maps(xw.device)
+        xv = xw.reshape(B, t * t, 8)[:, fwd].reshape(B * S, t, t, 8)     # fwd [S, t * t]: window-major
+        p = self._proba(engine_input(xv, self.in_channels))             # [B * S, K, t, t]
+        p = p.reshape(B, S, self.classes, t * t)
+        mean = p.gather(3, inv[None, :, None, :].expand_as(p)).sum(1) / S
+        self._slice_add(mean.reshape(B, self.classes, t, t) * w2, origins, w2, acc)
 
     def _slice_add(self, p, origins, w2, acc):
         K, t = self.classes, self.tile

@@ -20,7 +20,9 @@ B: the composition without them: the ``codes``-free ops around ``torch.flip`` / 
 
 Both are also reported against S x the single-view (``codes``-free) time, and ``window_gather``
 is timed per code on both mappings of the transposing codes: ``lds`` (knob WINDOW_LDS_T = 1)
-and ``direct`` (0)."""
+and ``direct`` (0).  There is one kernel per op — a call without ``codes`` is the list ``[0]`` —
+so ``single_view`` and ``plain_16`` time the kernels of code 0 (``plain_16`` and
+``code0_direct`` are the same launch, reached without and with a codes tensor)."""
 import argparse
 import json
 import os

@@ -22,9 +22,9 @@ def rel_err(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-12))
 
 
-def rand_scene(H, W, seed, device):
+def rand_scene(H, W, seed, device, in_ch=3):
     g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8).to(device)
+    return torch.randint(0, 256, (H, W, in_ch), generator=g, dtype=torch.uint8).to(device)
 
 
 # ------------------------------------------------------------------ plan (no kernels)

@@ -20,6 +20,11 @@ def test_window_gather_codes(H, W, tile):
     tc.check_window_gather_codes(DEV, H, W, tile)
 
 
+@pytest.mark.parametrize("in_ch,cpad", tc.CHANNEL_CASES)
+def test_window_gather_channels(in_ch, cpad):
+    tc.check_window_gather_channels(DEV, in_ch, cpad)
+
+
 @pytest.mark.parametrize("blend", ["cosine", "core"])
 @pytest.mark.parametrize("C,K", pc.HEAD_CASES)
 def test_head_predict_accum_codes(C, K, blend):
@@ -50,6 +55,10 @@ def test_tta_prediction_is_equivariant(models, name, H, tile, overlap, tta, grou
 
 def test_tta_none_is_the_default_path(models):
     tc.check_none_is_default(DEV, models["d3_convt"])
+
+
+def test_tta_none_counters_and_accumulator(models):
+    tc.check_none_counters(DEV, models["d3_convt"])
 
 
 def test_tta_rejects_bad_arguments(models):

@@ -15,6 +15,7 @@ from predict_cases import HEAD_CASES, HEAD_ORIGINS, PREDICTOR_SHAPES, _bn4, deci
 
 GATHER_CASES = [(40, 27, 16), (40, 27, 40), (5, 7, 16), (5, 7, 40)]
 GATHER_CODES = [[c] for c in range(8)] + [[0, 1, 2, 3], list(range(8)), [6, 1, 4]]
+CHANNEL_CASES = [(1, 1), (3, 4), (5, 8), (8, 8)]                        # (in_ch, cpad)
 HEAD_CODES = [list(range(8)), [0, 1, 2, 3], [5]]
 TTA_SHAPES = PREDICTOR_SHAPES + [(48, 48, 32, 16)]
 EQUIVARIANCE_SHAPES = [(32, 32, 32, 0), (48, 48, 32, 16)]
@@ -69,6 +70,34 @@ def check_window_gather_codes(device, H, W, tile):
         for j, c in enumerate(codes):
             a, b = frame_index(tile, c, device)
             assert torch.equal(got[:, j], plain[:, a, b]), (codes, j)
+
+
+def check_window_gather_channels(device, in_ch, cpad):
+    """Every (in_ch, cpad), not only the 16-byte store of cpad = 8 with 3 channels: a 5 x 7
+    scene (windows of 40 reflect several times), tile 40 = 2 x 2 blocks of 32 with the second
+    ragged; without codes against the torch expression, under codes against the index map."""
+    from ddlpc.infer import reflect
+    H, W, tile = 5, 7, 40
+    origins = [(-39, -39), (4, 6), (-3, 5)]
+    scene = rand_scene(H, W, 3, device, in_ch)
+    o = torch.tensor(origins, dtype=torch.int32, device=device)
+    ref = torch.zeros(len(origins), tile, tile, cpad, device=device)
+    for n, (y0, x0) in enumerate(origins):
+        iy = torch.tensor([reflect(y0 + t, H) for t in range(tile)], device=device)
+        ix = torch.tensor([reflect(x0 + t, W) for t in range(tile)], device=device)
+        ref[n, :, :, :in_ch] = scene.index_select(0, iy).index_select(1, ix).float() / 255
+    plain = ref.bfloat16()
+    F = ops()
+    got = F.window_gather(scene, o, tile, cpad)
+    assert got.dtype == torch.bfloat16 and got.shape == (len(origins), tile, tile, cpad)
+    assert torch.equal(got, plain)
+    codes = [6, 1, 4]
+    got = F.window_gather(scene, o, tile, cpad, codes_tensor(codes, device))
+    assert got.dtype == torch.bfloat16 and got.shape == (len(origins) * len(codes), tile, tile, cpad)
+    got = got.reshape(len(origins), len(codes), tile, tile, cpad)
+    for j, c in enumerate(codes):
+        a, b = frame_index(tile, c, device)
+        assert torch.equal(got[:, j], plain[:, a, b]), (codes, j)
 
 
 # ------------------------------------------------------------------ 2. head_predict_accum with codes
@@ -239,6 +268,36 @@ def check_none_is_default(device, model):
         b = ScenePredictor(model, 32, 16, "cosine", window_batch=3, fused=fused)
         assert torch.equal(a.accumulate(scene), b.accumulate(scene))
         assert a.windows == b.windows == a.inputs == b.inputs
+
+
+def check_none_counters(device, model):
+    """Without test-time augmentation a pass is ``window_batch`` windows, one input each, and the
+    accumulator is that of the codes-free ops called batch by batch in the plan's order."""
+    from ddlpc.data.datasets import engine_input
+    from ddlpc.infer import ScenePredictor, plan_windows
+    H, W, tile, overlap, batch = 70, 52, 32, 16, 3
+    scene = rand_scene(H, W, 2, device)
+    groups = plan_windows(H, W, tile, overlap)
+    sp = ScenePredictor(model, tile, overlap, "cosine", window_batch=batch, tta="none")
+    acc = sp.accumulate(scene)
+    assert sp.windows == sp.inputs == sum(len(g) for g in groups)
+    unfused = ScenePredictor(model, tile, overlap, "cosine", window_batch=batch, fused=False, tta="none")
+    unfused.accumulate(scene)
+    assert unfused.windows == unfused.inputs == sp.windows
+    F, eng = ops(), model._engine
+    win = sp.win.to(device)
+    want = torch.zeros_like(acc)
+    was = model.training
+    model.eval()
+    with torch.no_grad():
+        for g in groups:
+            for i in range(0, len(g), batch):
+                o = torch.tensor(g[i:i + batch], dtype=torch.int32, device=device)
+                a, s = eng.features(engine_input(F.window_gather(scene, o, tile, 8), 3), defer_last=True)
+                wh, bh = eng._head_params()
+                F.head_predict_accum(a, wh.detach().contiguous(), bh.detach().contiguous(), o, win, want, s)
+    model.train(was)
+    assert torch.equal(acc, want)
 
 
 # ------------------------------------------------------------------ 7. arguments
