@@ -78,10 +78,10 @@ int pick_bn(int Cout) {
 
 }  // namespace
 
-// ---- what the last conv / convT / head operator of this thread dispatched to (torch.ops.ddlpc.
-// last_path): "<operator>:<kernel variant>:<decisions that change the code that runs>", e.g.
-// "conv3_fwd:stream:cfg5:ks1", "conv3_wgrad:v3:bco128:ciw1", "convt_fwd:res",
-// "head_ce_bwd:head32:defer:stats"; the CPU kernels
+// ---- what the last conv / convT / head / BatchNorm operator of this thread dispatched to
+// (torch.ops.ddlpc.last_path): "<operator>:<kernel variant>:<decisions that change the code that
+// runs>", e.g. "conv3_fwd:stream:cfg5:ks1", "conv3_wgrad:v3:bco128:ciw1", "convt_fwd:res",
+// "head_ce_bwd:head32:defer:stats", "bn_backward:v2:pool:kwin"; the CPU kernels
 // (cpu_ref.cpp) report "cpu".  Host-side bookkeeping only: tests assert that a shape written
 // for one kernel variant still runs it after the launch heuristics are retuned.
 namespace {
@@ -635,8 +635,10 @@ at::Tensor bn_finalize(const at::Tensor& partial, double count, const at::Tensor
                                   beta.data_ptr<float>(), running_mean.data_ptr<float>(),
                                   running_var.data_ptr<float>(), (float)momentum, (float)eps,
                                   st.data_ptr<float>(), update_running, nbp, cur_stream());
+    set_last_path("bn_finalize:rows");
     return st;
   }
+  set_last_path("bn_finalize:two_pass");
   at::Tensor sums = reduce_rows(partial, P, 2 * C);
   bn_stats_finalize_launch(sums.data_ptr<double>(), C, count, gamma.data_ptr<float>(),
                            beta.data_ptr<float>(), running_mean.data_ptr<float>(),
@@ -694,8 +696,10 @@ std::vector<at::Tensor> bn_relu_apply(const at::Tensor& y, const at::Tensor& sta
                                           : std::vector<int64_t>{g.N, g.D / 2, g.H / 2, g.W / 2, g.C};
     p = at::empty(ps, y.options());
   }
-  bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, full ? bptr_mut(a) : nullptr,
-                       pool ? bptr_mut(p) : nullptr, g.dims, g.N, g.D, g.H, g.W, g.C, cur_stream());
+  const char* variant =
+      bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, full ? bptr_mut(a) : nullptr,
+                           pool ? bptr_mut(p) : nullptr, g.dims, g.N, g.D, g.H, g.W, g.C, cur_stream());
+  set_last_path(std::string("bn_relu_apply:") + variant + (g.dims == 3 ? ":3d" : ""));
   return {a, p.defined() ? p : at::empty({0}, y.options())};
 }
 
@@ -749,7 +753,8 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
   at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
   at::Tensor coefs = at::empty({3, C}, fopts);
   const double count = (double)g.N * g.D * g.H * g.W;
-  if (nb <= 2048) {
+  const bool two_pass = nb > 2048;
+  if (!two_pass) {
     bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, count, gamma.data_ptr<float>(),
                                  s + C, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
                                  coefs.data_ptr<float>(), into, cur_stream());
@@ -760,8 +765,11 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
                             coefs.data_ptr<float>(), into, cur_stream());
   }
   at::Tensor dY = at::empty_like(y);
-  bn_bwd_apply_launch(pA, pP, bptr(y), s + 2 * C, s + 3 * C, s, s + C, coefs.data_ptr<float>(), gs,
-                      bptr_mut(dY), g.dims, g.N, g.D, g.H, g.W, C, cur_stream());
+  const char* variant =
+      bn_bwd_apply_launch(pA, pP, bptr(y), s + 2 * C, s + 3 * C, s, s + C, coefs.data_ptr<float>(), gs,
+                          bptr_mut(dY), g.dims, g.N, g.D, g.H, g.W, C, cur_stream());
+  set_last_path(std::string("bn_backward:") + variant + (g.dims == 3 ? ":3d" : "") + (pre ? ":rows" : "") +
+                (two_pass ? ":two_pass" : ""));
   return {dY, dgamma, dbeta};
 }
 
@@ -789,11 +797,13 @@ std::vector<at::Tensor> bn_grad_coefs(const at::Tensor& partial, const at::Tenso
     bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, count, gamma.data_ptr<float>(),
                                  s + C, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
                                  coefs.data_ptr<float>(), into, cur_stream());
+    set_last_path("bn_grad_coefs:rows");
   } else {
     at::Tensor sums = reduce_rows(partial, nb, 2 * C);
     bn_grad_finalize_launch(sums.data_ptr<double>(), C, count, gamma.data_ptr<float>(), s + C,
                             dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
                             coefs.data_ptr<float>(), into, cur_stream());
+    set_last_path("bn_grad_coefs:two_pass");
   }
   return {coefs, dgamma, dbeta};
 }
@@ -876,9 +886,12 @@ std::vector<at::Tensor> bn_group_apply(const at::Tensor& y, const at::Tensor& st
     p = at::empty(ps, y.options());
   }
   const float* s = stats4.data_ptr<float>();
-  bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, bptr_mut(a), pool ? bptr_mut(p) : nullptr,
-                       g.dims, g.N / (int)groups, g.D, g.H, g.W, g.C, cur_stream(), (int)groups,
-                       4LL * g.C);
+  const char* variant =
+      bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, bptr_mut(a), pool ? bptr_mut(p) : nullptr,
+                           g.dims, g.N / (int)groups, g.D, g.H, g.W, g.C, cur_stream(), (int)groups,
+                           4LL * g.C);
+  set_last_path(std::string("bn_group_apply:") + variant + (g.dims == 3 ? ":3d" : "") +
+                (groups > 1 ? ":groups" : ""));
   return {a, p.defined() ? p : at::empty({0}, y.options())};
 }
 
@@ -923,11 +936,13 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
   at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
   at::Tensor dY = at::empty_like(y);
   at::Tensor gsum = at::empty({groups, 2, C}, y.options().dtype(at::kDouble));
-  bn_group_backward_launch(hasA ? bptr(*dA) : nullptr, hasP ? bptr(*dP) : nullptr, bptr(y),
-                           stats4.data_ptr<float>(), gamma.data_ptr<float>(), dgamma.data_ptr<float>(),
-                           dbeta.data_ptr<float>(), into, coefs.data_ptr<float>(),
-                           part.data_ptr<float>(), nb, bptr_mut(dY), g.dims, (int)groups, Ng, g.D,
-                           g.H, g.W, C, cur_stream(), have_part, gsum.data_ptr<double>());
+  const char* variant = bn_group_backward_launch(
+      hasA ? bptr(*dA) : nullptr, hasP ? bptr(*dP) : nullptr, bptr(y), stats4.data_ptr<float>(),
+      gamma.data_ptr<float>(), dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), into,
+      coefs.data_ptr<float>(), part.data_ptr<float>(), nb, bptr_mut(dY), g.dims, (int)groups, Ng, g.D,
+      g.H, g.W, C, cur_stream(), have_part, gsum.data_ptr<double>());
+  set_last_path(std::string("bn_group_backward:") + variant + (g.dims == 3 ? ":3d" : "") +
+                (have_part ? ":rows" : "") + (groups > 1 ? ":groups" : ""));
   return {dY, dgamma, dbeta};
 }
 

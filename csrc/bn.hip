@@ -488,8 +488,9 @@ bool bn_bwd2_ok(int dims, bool pool, int D, int H, int W, int C) {
   return true;
 }
 
+// -> the kernel variant chosen, for last_path()
 template <int MODE>
-void bn_bwd2_launch(int grid, int dims, bool pool, const bf16_t* dA, const bf16_t* dP,
+const char* bn_bwd2_launch(int grid, int dims, bool pool, const bf16_t* dA, const bf16_t* dP,
                     const bf16_t* y, const float* scale, const float* shift, const float* mean,
                     const float* invstd, const float* coefs, const float* gscale, float* partial,
                     bf16_t* dY, int N, int D, int H, int W, int C, hipStream_t st,
@@ -504,7 +505,7 @@ void bn_bwd2_launch(int grid, int dims, bool pool, const bf16_t* dA, const bf16_
     else
       hipLaunchKernelGGL((bn_bwd2_kernel<2, true, MODE, true>), gr, dim3(256), 0, st, dA, dP, y,
                          scale, shift, mean, invstd, coefs, gscale, partial, dY, ND, H, W, C, sstride);
-    return;
+    return "v2:pool:kwin";
   }
   if (dims == 3 && pool)
     hipLaunchKernelGGL((bn_bwd2_kernel<3, true, MODE>), gr, dim3(256), 0, st, dA, dP, y,
@@ -515,12 +516,13 @@ void bn_bwd2_launch(int grid, int dims, bool pool, const bf16_t* dA, const bf16_
   else
     hipLaunchKernelGGL((bn_bwd2_kernel<2, false, MODE>), gr, dim3(256), 0, st, dA, dP, y,
                        scale, shift, mean, invstd, coefs, gscale, partial, dY, ND, H, W, C, sstride);
+  return pool ? "v2:pool" : "v2";
 }
 }  // namespace
 
-void bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
-                          bf16_t* pooled, int dims, int N, int D, int H, int W, int C,
-                          hipStream_t st, int groups, long long sstride) {
+const char* bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
+                                 bf16_t* pooled, int dims, int N, int D, int H, int W, int C,
+                                 hipStream_t st, int groups, long long sstride) {
   // groups > 1: N = images per group (per-micro-batch BatchNorm, statistics rows sstride apart)
   const long long G = C / 8;
   const int cap = std::max(1, 8192 / groups);
@@ -533,7 +535,7 @@ void bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shif
     else
       hipLaunchKernelGGL((bn_relu_apply_kernel<3, false>), gr, dim3(256), 0,
                          st, y, scale, shift, out, pooled, N, D, H, W, C, sstride);
-    return;
+    return "flat";
   }
   const long long items = (long long)N * (dims == 3 ? D / 2 : 1) * (H / 2) * (W / 2) * G;
   const dim3 gr(std::min(grid_for(items, 256), cap), groups);
@@ -550,7 +552,7 @@ void bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shif
     else
       hipLaunchKernelGGL((bn_relu_pool2_kernel<3>), g2, dim3(256), 0, st, y, scale, shift, out, pooled,
                          ND, H, W, C, sstride);
-    return;
+    return "pool2";
   }
   if (dims == 2)
     hipLaunchKernelGGL((bn_relu_apply_kernel<2, true>), gr, dim3(256), 0, st, y, scale,
@@ -558,6 +560,7 @@ void bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shif
   else
     hipLaunchKernelGGL((bn_relu_apply_kernel<3, true>), gr, dim3(256), 0, st, y, scale,
                        shift, out, pooled, N, D, H, W, C, sstride);
+  return "pool";
 }
 
 #define BN_BWD_DISPATCH(MODE, grid)                                                         \
@@ -594,10 +597,10 @@ void bn_bwd_reduce_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
   BN_BWD_DISPATCH(0, nblocks);
 }
 
-void bn_bwd_apply_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y, const float* scale,
-                         const float* shift, const float* mean, const float* invstd,
-                         const float* coefs, const float* gscale, bf16_t* dY, int dims, int N,
-                         int D, int H, int W, int C, hipStream_t st) {
+const char* bn_bwd_apply_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y, const float* scale,
+                                const float* shift, const float* mean, const float* invstd,
+                                const float* coefs, const float* gscale, bf16_t* dY, int dims, int N,
+                                int D, int H, int W, int C, hipStream_t st) {
   const bool pool = dP != nullptr;
   float* partial = nullptr;
   const int G = C / 8;
@@ -607,12 +610,12 @@ void bn_bwd_apply_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y, co
   if (bn_bwd2_ok(dims, pool, D, H, W, C)) {
     const int upb = 256 / ((pool && G <= 32) ? 2 * G : G);
     const int grid2 = (int)std::max<long long>(1, std::min<long long>((items + 2 * upb - 1) / (2 * upb), 8192));
-    bn_bwd2_launch<1>(grid2, dims, pool, dA, dP, y, scale, shift, mean, invstd, coefs, gscale,
-                      partial, dY, N, D, H, W, C, st);
-    return;
+    return bn_bwd2_launch<1>(grid2, dims, pool, dA, dP, y, scale, shift, mean, invstd, coefs, gscale,
+                             partial, dY, N, D, H, W, C, st);
   }
   const int grid = std::min(grid_for(items, per), 16384);
   BN_BWD_DISPATCH(1, grid);
+  return pool ? "v1:pool" : "v1";
 }
 
 // ===================================================================== per-micro-batch groups
@@ -810,11 +813,11 @@ void bn_group_finalize_rows_launch(const float* partial, int nb, int groups, lon
                      partial, nb, groups, C, (double)gpix, gamma, beta, eps, out4, arena, astride);
 }
 
-void bn_group_backward_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
-                              const float* stats4, const float* gamma, float* dgamma, float* dbeta,
-                              bool accumulate, float* coefs, float* partial_scratch, int nb,
-                              bf16_t* dY, int dims, int groups, int N, int D, int H, int W, int C,
-                              hipStream_t st, bool have_partial, double* gsum_scratch) {
+const char* bn_group_backward_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
+                                     const float* stats4, const float* gamma, float* dgamma, float* dbeta,
+                                     bool accumulate, float* coefs, float* partial_scratch, int nb,
+                                     bf16_t* dY, int dims, int groups, int N, int D, int H, int W, int C,
+                                     hipStream_t st, bool have_partial, double* gsum_scratch) {
   const bool pool = dP != nullptr;
   const long long sstride = 4LL * C;
   const float* s = stats4;
@@ -833,8 +836,8 @@ void bn_group_backward_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* 
   const int upb = 256 / ((pool && C / 8 <= 32) ? 2 * (C / 8) : C / 8);
   const int grid2 = (int)std::max<long long>(
       1, std::min<long long>((items + 2 * upb - 1) / (2 * upb), std::max(1, 8192 / groups)));
-  bn_bwd2_launch<1>(grid2, dims, pool, dA, dP, y, s + 2 * C, s + 3 * C, s, s + C, coefs, nullptr,
-                    nullptr, dY, N, D, H, W, C, st, groups, sstride);
+  return bn_bwd2_launch<1>(grid2, dims, pool, dA, dP, y, s + 2 * C, s + 3 * C, s, s + C, coefs, nullptr,
+                           nullptr, dY, N, D, H, W, C, st, groups, sstride);
 }
 
 void bn_group_grad_rows_launch(const float* partial, int nb, int groups, int C, double count,

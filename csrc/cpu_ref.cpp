@@ -318,7 +318,7 @@ Tensor stats4_from_sums(const Tensor& sums, double count, const Tensor& gamma, c
       const double mean = s[(k * 2) * C + c] / count;
       double var = s[(k * 2 + 1) * C + c] / count - mean * mean;
       if (var < 0) var = 0;
-      const float inv = (float)(1.0 / std::sqrt(var + eps));
+      const float inv = (float)(1.0 / std::sqrt(var + (double)(float)eps));   // eps as fp32, as the GPU kernels take it
       const float sc = g[c] * inv;
       float* ok = o + k * 4 * C;
       ok[c] = (float)mean;
@@ -336,6 +336,7 @@ Tensor stats4_from_sums(const Tensor& sums, double count, const Tensor& gamma, c
 Tensor bn_finalize(const Tensor& partial, double count, const Tensor& gamma, const Tensor& beta,
                    Tensor running_mean, Tensor running_var, double momentum, double eps,
                    bool update_running, const optional<Tensor>& nbt) {
+  ddlpc::set_last_path("cpu");
   const int64_t C = gamma.numel();
   const Tensor sums = partial.reshape({-1, 2, C}).to(at::kDouble).sum(0, true);
   Tensor arena;
@@ -396,6 +397,7 @@ void bn_running_apply_all(const Tensor& entries, const Tensor& arena, int64_t K,
 }
 
 std::vector<Tensor> relu_apply_groups(const Tensor& y, const Tensor& stats4, int64_t G, bool pool, bool full) {
+  ddlpc::set_last_path("cpu");
   const int64_t C = y.size(-1);
   const Tensor a = bn_act(f32(y), s4row(stats4, G, C, 2), s4row(stats4, G, C, 3), G);
   const Tensor none = at::empty({0}, y.options());
@@ -412,6 +414,7 @@ std::vector<Tensor> bn_backward_groups(const optional<Tensor>& dA, const optiona
                                        const Tensor& stats4, const Tensor& gamma, int64_t G, double gs,
                                        const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
                                        const optional<Tensor>& partial) {
+  ddlpc::set_last_path("cpu");
   const bool hasA = has(dA), hasP = has(dP);
   TORCH_CHECK(hasA || hasP, "bn_backward needs dA or dP");
   const int64_t C = y.size(-1);
@@ -449,6 +452,7 @@ std::vector<Tensor> bn_backward(const optional<Tensor>& dA, const optional<Tenso
 
 std::vector<Tensor> bn_grad_coefs(const Tensor& partial, const Tensor& y, const Tensor& stats4, const Tensor& gamma,
                                   const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out) {
+  ddlpc::set_last_path("cpu");
   const int64_t C = y.size(-1);
   const Tensor sums = partial.reshape({1, -1, 2, C}).to(at::kDouble).sum(1);
   const bool into = has(dgamma_out);

@@ -203,18 +203,20 @@ bool convt_res_launch(GemmArgs& a, int num_cus, hipStream_t st);
 
 
 // ---------------------------------------------------------------- BatchNorm / ReLU / pool
-// out may be null with pool (deferred skip: only the pooled tensor is materialised)
-void bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
-                          bf16_t* pooled, int dims, int N, int D, int H, int W, int C,
-                          hipStream_t st, int groups = 1, long long sstride = 0);
+// out may be null with pool (deferred skip: only the pooled tensor is materialised).
+// The apply launchers return the kernel variant they chose, for last_path(): "flat" | "pool2"
+// (lane pair) | "pool" (generic); "v2" | "v2:pool" | "v2:pool:kwin" | "v1" | "v1:pool"
+const char* bn_relu_apply_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
+                                 bf16_t* pooled, int dims, int N, int D, int H, int W, int C,
+                                 hipStream_t st, int groups = 1, long long sstride = 0);
 void bn_bwd_reduce_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
                           const float* scale, const float* shift, const float* mean,
                           const float* invstd, const float* gscale, float* partial, int nblocks,
                           int dims, int N, int D, int H, int W, int C, hipStream_t st);
-void bn_bwd_apply_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y, const float* scale,
-                         const float* shift, const float* mean, const float* invstd,
-                         const float* coefs, const float* gscale, bf16_t* dY, int dims, int N,
-                         int D, int H, int W, int C, hipStream_t st);
+const char* bn_bwd_apply_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y, const float* scale,
+                                const float* shift, const float* mean, const float* invstd,
+                                const float* coefs, const float* gscale, bf16_t* dY, int dims, int N,
+                                int D, int H, int W, int C, hipStream_t st);
 int bn_bwd_reduce_blocks(long long pixels_or_quads);
 // per-micro-batch BatchNorm groups (bn.hip): `groups` statistics groups of gpix pixels each,
 // the batch = the groups' tensors one after another; stats4 [groups][4][C]
@@ -228,11 +230,11 @@ void bn_group_stats_finalize_launch(const bf16_t* y, int groups, long long gpix,
                                     int nb, hipStream_t st);
 int bn_group_bwd_rows(long long items_per_group, int groups);
 // dY per group (N = images per group), coefs [groups][3][C], dgamma / dbeta summed over groups
-void bn_group_backward_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
-                              const float* stats4, const float* gamma, float* dgamma, float* dbeta,
-                              bool accumulate, float* coefs, float* partial_scratch, int nb,
-                              bf16_t* dY, int dims, int groups, int N, int D, int H, int W, int C,
-                              hipStream_t st, bool have_partial, double* gsum_scratch);
+const char* bn_group_backward_launch(const bf16_t* dA, const bf16_t* dP, const bf16_t* y,
+                                     const float* stats4, const float* gamma, float* dgamma, float* dbeta,
+                                     bool accumulate, float* coefs, float* partial_scratch, int nb,
+                                     bf16_t* dY, int dims, int groups, int N, int D, int H, int W, int C,
+                                     hipStream_t st, bool have_partial, double* gsum_scratch);
 // per-group BatchNorm-backward coefficients [groups][3][C] and dgamma / dbeta (summed over the
 // groups in order) from group-major partial rows [groups][nb][2][C]; dscale: optional device
 // factor on the rows (rows reduced at a unit gradient scale)
