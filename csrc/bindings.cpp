@@ -1470,10 +1470,22 @@ at::Tensor head_logits(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
 }
 
 // ------------------------------------------------------------------------ optimizer / pack
+// the flat buffers of one Adam step: fp32, contiguous (the kernel walks raw pointers), one device
+namespace {
+void check_adam_buffers(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m,
+                        const at::Tensor& v) {
+  CHECK_DEV(p); CHECK_F32(p); CHECK_F32(g); CHECK_F32(m); CHECK_F32(v);
+  CHECK_CONTIG(p); CHECK_CONTIG(g); CHECK_CONTIG(m); CHECK_CONTIG(v);
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(),
+              "adam: p, g, m, v must be on one device");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "size");
+}
+}  // namespace
+
 void adam_step(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, double b1, double b2,
                double eps, double wd, double step_size, double inv_sqrt_bc2) {
-  CHECK_DEV(p); CHECK_F32(p); CHECK_F32(g); CHECK_F32(m); CHECK_F32(v);
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "size");
+  check_adam_buffers(p, g, m, v);
+  if (p.numel() == 0) return;
   c10::DeviceGuard guard(p.device());
   adam_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
               p.numel(), (float)b1, (float)b2, (float)eps, (float)wd, (float)step_size,
@@ -1484,32 +1496,49 @@ void adam_step(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, do
 // the device by this call
 void adam_step_dev(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor scal,
                    double lr, double b1, double b2, double eps, double wd) {
-  CHECK_DEV(p); CHECK_F32(p); CHECK_F32(g); CHECK_F32(m); CHECK_F32(v); CHECK_F32(scal);
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "size");
-  TORCH_CHECK(scal.numel() >= 3 && scal.is_contiguous(), "scal must be float[3]");
+  check_adam_buffers(p, g, m, v);
+  CHECK_F32(scal);
+  TORCH_CHECK(scal.numel() >= 3 && scal.is_contiguous() && scal.device() == p.device(),
+              "scal must be float[3] on p's device");
   c10::DeviceGuard guard(p.device());
   adam_scalars_launch(scal.data_ptr<float>(), lr, b1, b2, cur_stream());
+  if (p.numel() == 0) return;           // (the step counter advances, as on the CPU)
   adam_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
               p.numel(), (float)b1, (float)b2, (float)eps, (float)wd, 0.f, 1.f, cur_stream(),
               scal.data_ptr<float>());
 }
 
 void weight_pack(const at::Tensor& entries, int64_t n, int64_t max_elems) {
-  CHECK_DEV(entries);
-  TORCH_CHECK(entries.scalar_type() == at::kLong && entries.numel() == n * 6,
+  CHECK_DEV(entries); CHECK_CONTIG(entries);
+  TORCH_CHECK(entries.scalar_type() == at::kLong && n >= 0 && entries.numel() == n * 6,
               "entries must be int64 [n, 6] (48-byte PackEntry records)");
   static_assert(sizeof(PackEntry) == 48, "PackEntry layout");
+  if (n == 0) return;                   // (a grid of zero entries is no launch)
   c10::DeviceGuard guard(entries.device());
   weight_pack_launch(reinterpret_cast<const PackEntry*>(entries.data_ptr()), (int)n, max_elems,
                      cur_stream());
 }
 
 // ------------------------------------------------------------------------ codec
+namespace {
+// the flat fp32 buffer of a codec call and its segment table: int64 (start, end) pairs on the
+// buffer's device -> the number of segments
+int check_codec_segments(const at::Tensor& x, const at::Tensor& seg) {
+  CHECK_DEV(x); CHECK_F32(x); CHECK_CONTIG(x); CHECK_CONTIG(seg);
+  TORCH_CHECK(seg.scalar_type() == at::kLong && seg.device() == x.device() && seg.numel() % 2 == 0,
+              "seg must be int64 (start, end) pairs on the buffer's device");
+  return (int)(seg.numel() / 2);
+}
+void check_codec_id(int64_t codec) {
+  TORCH_CHECK(codec == 0 || codec == 1, "codec must be 0 (fp16_absmax) or 1 (int8_absmax)");
+}
+}  // namespace
+
 at::Tensor codec_absmax(const at::Tensor& x, const at::Tensor& seg) {
-  CHECK_DEV(x); CHECK_F32(x);
+  const int nseg = check_codec_segments(x, seg);
   c10::DeviceGuard guard(x.device());
-  const int nseg = (int)(seg.numel() / 2);
   at::Tensor s = at::empty({nseg}, x.options());
+  if (nseg == 0) return s;
   codec_absmax_launch(x.data_ptr<float>(), seg.data_ptr<int64_t>(), nseg, s.data_ptr<float>(),
                       cur_stream());
   return s;
@@ -1517,10 +1546,14 @@ at::Tensor codec_absmax(const at::Tensor& x, const at::Tensor& seg) {
 
 at::Tensor codec_encode(const at::Tensor& x, const at::Tensor& seg, const at::Tensor& scales,
                         int64_t codec) {
-  CHECK_DEV(x); CHECK_F32(x);
+  const int nseg = check_codec_segments(x, seg);
+  check_codec_id(codec);
+  CHECK_F32(scales); CHECK_CONTIG(scales);
+  TORCH_CHECK(scales.device() == x.device() && scales.numel() == nseg,
+              "scales must be fp32 [nseg] on the buffer's device");
   c10::DeviceGuard guard(x.device());
-  const int nseg = (int)(seg.numel() / 2);
   at::Tensor out = at::zeros({x.numel()}, x.options().dtype(codec == 0 ? at::kHalf : at::kChar));
+  if (nseg == 0 || x.numel() == 0) return out;
   codec_encode_launch(x.data_ptr<float>(), seg.data_ptr<int64_t>(), nseg, scales.data_ptr<float>(),
                       out.data_ptr(), (int)codec, x.numel(), cur_stream());
   return out;
@@ -1528,10 +1561,19 @@ at::Tensor codec_encode(const at::Tensor& x, const at::Tensor& seg, const at::Te
 
 void codec_decode_sum(at::Tensor out, const at::Tensor& q, const at::Tensor& scales,
                       const at::Tensor& w, const at::Tensor& seg, int64_t codec) {
-  CHECK_DEV(out); CHECK_F32(out); CHECK_CONTIG(q);
-  c10::DeviceGuard guard(out.device());
-  const int nseg = (int)(seg.numel() / 2);
+  const int nseg = check_codec_segments(out, seg);
+  check_codec_id(codec);
+  CHECK_CONTIG(q); CHECK_F32(scales); CHECK_CONTIG(scales); CHECK_F32(w); CHECK_CONTIG(w);
+  TORCH_CHECK(q.dim() >= 1 && q.device() == out.device() &&
+              q.scalar_type() == (codec == 0 ? at::kHalf : at::kChar),
+              "q must be the codec's wire dtype (fp16 / int8) [world][n] on out's device");
   const int world = (int)q.size(0);
+  TORCH_CHECK(q.numel() == (int64_t)world * out.numel(), "q must hold world x out.numel() elements");
+  TORCH_CHECK(scales.device() == out.device() && scales.numel() == (int64_t)world * nseg,
+              "scales must be fp32 [world][nseg] on out's device");
+  TORCH_CHECK(w.device() == out.device() && w.numel() == world, "w must be fp32 [world] on out's device");
+  if (nseg == 0 || out.numel() == 0) return;
+  c10::DeviceGuard guard(out.device());
   codec_decode_sum_launch(out.data_ptr<float>(), q.data_ptr(), scales.data_ptr<float>(),
                           w.data_ptr<float>(), seg.data_ptr<int64_t>(), nseg, world, (int)codec,
                           out.numel(), cur_stream());
@@ -1564,10 +1606,12 @@ at::Tensor bilinear_up2_bwd(const at::Tensor& dy) {
 at::Tensor to_nhwc_bf16(const at::Tensor& x, int64_t cpad) {
   CHECK_DEV(x);
   TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "fp32/bf16 input");
+  TORCH_CHECK((x.dim() == 4 || x.dim() == 5) && cpad >= 1, "to_nhwc_bf16: [N, C, (D,) H, W] input, cpad >= 1");
   c10::DeviceGuard guard(x.device());
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int Cp = (int)((C + cpad - 1) / cpad * cpad);
-  const long long S = x.numel() / ((long long)N * C);
+  long long S = 1;
+  for (int i = 2; i < x.dim(); ++i) S *= x.size(i);
   // supported memory layouts: NCHW-contiguous or channel-last-contiguous
   long long sC, sS;
   if (x.is_contiguous()) { sC = S; sS = 1; }
@@ -1580,6 +1624,7 @@ at::Tensor to_nhwc_bf16(const at::Tensor& x, int64_t cpad) {
   for (int i = 2; i < x.dim(); ++i) shape.push_back(x.size(i));
   shape.push_back(Cp);
   at::Tensor y = at::empty(shape, x.options().dtype(at::kBFloat16));
+  if (y.numel() == 0) return y;
   to_nhwc_pad_launch(x.data_ptr(), x.scalar_type() == at::kFloat ? 0 : 1, bptr_mut(y), N, C, Cp, S,
                      x.stride(0), sC, sS, cur_stream());
   return y;

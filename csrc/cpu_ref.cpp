@@ -837,7 +837,7 @@ Tensor codec_encode(const Tensor& x, const Tensor& seg, const Tensor& scales, in
   for (size_t k = 0; k < segs.size(); ++k) {
     const int64_t a = segs[k].first, len = segs[k].second - segs[k].first;
     const float s = sc.data_ptr<float>()[k];
-    if (len <= 0 || !(s > 0.f)) continue;
+    if (len <= 0 || !(s > 0.f) || std::isinf(s)) continue;        // zero / NaN / Inf scale: zeros
     const Tensor q = at::round(x.narrow(0, a, len) / s * L);      // round half to even
     out.narrow(0, a, len).copy_(q);
   }

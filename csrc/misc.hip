@@ -126,27 +126,28 @@ __global__ __launch_bounds__(256) void weight_pack_kernel(const PackEntry* __res
 }
 
 // ---- codec -----------------------------------------------------------------------------
-DDLPC_DEVICE void atomic_max_pos(float* addr, float v) {
-  // non-negative floats order like their unsigned bit patterns
-  atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
+// The absmax is reduced on the unsigned bit pattern of |x| (the sign bit cleared), never with
+// fmaxf: non-negative floats, +Inf included, order like their bit patterns, and every NaN
+// pattern lies above +Inf's, so a NaN anywhere in the segment becomes the segment's scale (as
+// torch's abs().max() gives), where fmaxf(m, NaN) = m would hide it.  Subnormals are compared
+// as they are stored.
 __global__ void codec_absmax_kernel(const float* __restrict__ x, const int64_t* __restrict__ seg,
                                     float* __restrict__ scales) {
   const int s = blockIdx.y;
   const long long a = seg[2 * s], b = seg[2 * s + 1];
-  float m = 0.f;
+  unsigned int m = 0u;
   for (long long i = a + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < b;
        i += (long long)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(x[i]));
-  m = wave_max(m);
-  __shared__ float red[4];
+    m = max(m, __float_as_uint(x[i]) & 0x7fffffffu);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned int)__shfl_xor((int)m, o, 64));
+  __shared__ unsigned int red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t = fmaxf(t, red[w]);
-    atomic_max_pos(scales + s, t);
+    unsigned int t = 0u;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t = max(t, red[w]);
+    atomicMax(reinterpret_cast<unsigned int*>(scales + s), t);
   }
 }
 
@@ -157,10 +158,13 @@ __global__ void codec_encode_kernel(const float* __restrict__ x, const int64_t* 
   const long long a = seg[2 * s], b = seg[2 * s + 1];
   const float sc = scales[s];
   const float L = codec == 0 ? 100.f : 10.f;
+  // a zero scale (all-zero segment) and a NaN / Inf scale (a non-finite gradient) encode
+  // zeros: the decode 0 / L * scale then gives 0, or NaN over the whole poisoned segment
+  const bool ok = sc > 0.f && sc < INFINITY;
   for (long long i = a + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < b;
        i += (long long)gridDim.x * blockDim.x) {
     // torch.round(g / max * L): IEEE division then multiply, round half to even
-    const float q = sc > 0.f ? rintf(__fdiv_rn(x[i], sc) * L) : 0.f;
+    const float q = ok ? rintf(__fdiv_rn(x[i], sc) * L) : 0.f;
     if (codec == 0) reinterpret_cast<__half*>(out)[i] = __float2half_rn(q);
     else reinterpret_cast<int8_t*>(out)[i] = (int8_t)q;
   }

@@ -6,6 +6,10 @@ multi-segment absmax pass, K16), ``codec_encode`` (quantise to fp16/int8 levels,
 gradient, K18) — the fused HIP kernels of ``csrc/misc.hip`` for GPU tensors, the C++ kernels
 of ``csrc/cpu_ref.cpp`` for CPU tensors.  ``parallel.codec`` is the torch oracle both are
 tested against (same formulas, bit-exact rounding: round-half-to-even like torch.round).
+
+Non-finite gradients are not hidden: a segment that holds a NaN gets the scale NaN, one that
+holds an Inf the scale +Inf, its payload is zeros, and ``0 / L * scale`` decodes the whole
+segment to NaN on every rank (tests/test_update_exact_gpu.py::test_codec_nonfinite).
 """
 from __future__ import annotations
 
