@@ -33,6 +33,7 @@ mean subtraction cancels them); stock PyTorch returns float noise of ~1e-9 there
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import os
 from typing import List, Optional, Tuple
 
@@ -55,6 +56,26 @@ def _nhwc_shape_to_nchw(t: torch.Tensor) -> torch.Tensor:
     """View a channel-last [N,(D,)H,W,C] tensor as NCHW (no copy)."""
     nd = t.dim()
     return t.permute(0, nd - 1, *range(1, nd - 1))
+
+
+@dataclasses.dataclass
+class _GradNote:
+    """What a backward node tells the node that receives its gradient, carried on the gradient
+    tensor as ``_ddlpc_note`` (autograd passes the tensor object through when the output has
+    one consumer; a second consumer's sum drops the note)."""
+    head: Optional[tuple] = None                   # two-pass head: head_ce_bn_bwd's leading arguments
+    class_weight: Optional[torch.Tensor] = None    # ... and the loss's class weights
+    bn_partial: Optional[torch.Tensor] = None      # BN-backward partial rows the consumer reduced
+    bn_pscale: Optional[torch.Tensor] = None       # ... and the scale they are still to take
+    colsum_rows: Optional[torch.Tensor] = None     # per-channel sums: a transposed conv's db
+
+
+def _grad_of(p):
+    return p.grad
+
+
+def _no_grad(p):
+    return None
 
 
 class _ConvPack:
@@ -124,7 +145,8 @@ class _BNState:
         eng = self.engine
         arena = eng._bn_arena if (bn.track_running_stats and eng._bn_arena is not None) else None
         off = eng._bn_offs[self.index] if arena is not None else 0
-        return _ops().bn_group_finalize(y, groups, bn.weight, bn.bias, float(bn.eps), arena, off)
+        return _ops().bn_group_finalize(y, groups, bn.weight, bn.bias, float(bn.eps),
+                                        arena=arena, aoff=off)
 
     def finalize_group_rows(self, rows: torch.Tensor, groups: int, count: float) -> torch.Tensor:
         """``finalize_groups`` from group-major partial rows a conv epilogue wrote
@@ -134,7 +156,7 @@ class _BNState:
         arena = eng._bn_arena if (bn.track_running_stats and eng._bn_arena is not None) else None
         off = eng._bn_offs[self.index] if arena is not None else 0
         return _ops().bn_group_finalize_rows(rows, groups, float(count), bn.weight, bn.bias,
-                                             float(bn.eps), arena, off)
+                                             float(bn.eps), arena=arena, aoff=off)
 
     def eval_stats(self) -> torch.Tensor:
         bn = self.bn
@@ -156,68 +178,56 @@ class _DoubleConvFn(torch.autograd.Function):
         p1, p2 = blk.pack1, blk.pack2
         training = blk.bn1.bn.training
         G = blk.engine.bn_groups if training else 0
+        rc, a1 = 0, None
         if G >= 1:
             assert not defer_skip and x2_bn is None, "BN groups: no deferred skips"
-            return _DoubleConvFn._group_forward(ctx, x1, x2, b1, b2, g1, g2, blk, pool, G, defer)
-        ctx.groups = 0
-        c1 = p1.cout
-        sc2 = x2_bn[2] if x2_bn is not None else None
-        sh2 = x2_bn[3] if x2_bn is not None else None
-        ctx.x2_bn = x2_bn
-        y1, _, st1 = F.conv3_fwd(x1, x2, p1.fwd, b1, None, None, c1, 0, training, sc2, sh2)
-        count = float(y1.numel() // c1)
-        s1 = blk.bn1.finalize(st1, count) if training else blk.bn1.eval_stats()
-        y2, _, st2 = F.conv3_fwd(y1, None, p2.fwd, b2, s1[2], s1[3], p2.cout, 0, training)
-        s2 = blk.bn2.finalize(st2, count) if training else blk.bn2.eval_stats()
-        ctx.blk = blk
-        ctx.pool = pool
-        ctx.defer = defer
-        # activation recompute: y1 is not kept; backward re-runs conv1 (same kernel, same
-        # bits) from the saved inputs.  b1 rides along for that (its own grad stays zero)
+            assert not (defer and pool), "BN groups: only the head's input is deferred"
+            y1, y2, s1, s2, a1, ctx.fused = _DoubleConvFn._group_convs(x1, x2, b1, b2, blk, G)
+        else:
+            sc2 = x2_bn[2] if x2_bn is not None else None
+            sh2 = x2_bn[3] if x2_bn is not None else None
+            y1, _, st1 = F.conv3_fwd(x1, x2, p1.fwd, b1, None, None, p1.cout, 0, training,
+                                     pscale2=sc2, pshift2=sh2)
+            count = float(y1.numel() // p1.cout)
+            s1 = blk.bn1.finalize(st1, count) if training else blk.bn1.eval_stats()
+            y2, _, st2 = F.conv3_fwd(y1, None, p2.fwd, b2, s1[2], s1[3], p2.cout, 0, training)
+            s2 = blk.bn2.finalize(st2, count) if training else blk.bn2.eval_stats()
+            # activation recompute: y1 is not kept; backward re-runs conv1 (same kernel, same
+            # bits) from the saved inputs.  b1 rides along for that (its own grad stays zero)
+            rc = int(blk.engine.recompute) if training else 0
+        ctx.groups, ctx.x2_bn = G, x2_bn
+        ctx.blk, ctx.pool, ctx.defer = blk, pool, defer
+        ctx.has_x2 = x2 is not None
         # recompute level 2 also drops y2 when the block hands out a materialised activation
         # (a deferred block's y2 IS its output, held by the consumer anyway)
-        rc = int(blk.engine.recompute) if training else 0
         ctx.recompute = rc
-        ctx.recompute_y2 = rc >= 2 and not defer and not defer_skip   # those save y2 anyway
+        ctx.recompute_y2 = rc >= 2 and not defer and not defer_skip
         ctx.b1 = b1 if rc else None
         ctx.b2 = b2 if ctx.recompute_y2 else None
-        empty = torch.empty(0, device=y1.device, dtype=y1.dtype)
-        y1_keep = empty if rc else y1
-        y2_keep = empty if ctx.recompute_y2 else y2
         if defer:
             # deferred activation: the block hands out its PRE-BN output y2 with the BN
             # statistics s2; the consumer (transposed conv / head kernels) applies BN + ReLU
             # on load and returns dL/da2 with BN-backward partial sums attached
-            ctx.has_x2 = x2 is not None
-            ctx.x1_requires_grad = ctx.needs_input_grad[0]
-            ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), y1_keep, y2, s1,
-                                  s2, g1, g2)                     # (y2: the output itself)
-            ctx.set_materialize_grads(False)
-            ctx.mark_non_differentiable(s2)
-            return y2, None, s2
-        if defer_skip:
+            out = y2, None, s2
+        elif defer_skip:
             # the skip leaves as y2 (its BN + ReLU is applied by the decoder's concat conv);
             # only the pooled activation is written.  s2 rides along (non-differentiable)
-            _, pooled = F.bn_relu_apply(y2, s2, True, False)
-            ctx.has_x2 = x2 is not None
-            ctx.x1_requires_grad = ctx.needs_input_grad[0]
-            ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), y1_keep, y2, s1,
-                                  s2, g1, g2)
-            ctx.set_materialize_grads(False)
-            ctx.mark_non_differentiable(s2)
-            return y2, pooled, s2
-        a2, pooled = F.bn_relu_apply(y2, s2, pool)
-        ctx.has_x2 = x2 is not None
-        ctx.x1_requires_grad = ctx.needs_input_grad[0]
-        ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), y1_keep, y2_keep, s1,
-                              s2, g1, g2)
+            out = y2, F.bn_relu_apply(y2, s2, True, full=False)[1], s2
+        else:
+            a2, pooled = (F.bn_group_apply(y2, s2, G, pool) if G >= 1 else
+                          F.bn_relu_apply(y2, s2, pool))
+            out = a2, (pooled if pool else None), None
+        empty = torch.empty(0, device=y1.device, dtype=y1.dtype)
+        ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), empty if rc else y1,
+                              empty if ctx.recompute_y2 else y2, s1, s2, g1, g2,
+                              a1 if a1 is not None else empty)
         ctx.set_materialize_grads(False)
-        if pool:
-            return a2, pooled, None
-        return a2, None, None
+        if out[2] is not None:
+            ctx.mark_non_differentiable(s2)
+        return out
 
     @staticmethod
-    def _group_forward(ctx, x1, x2, b1, b2, g1, g2, blk, pool: bool, G: int, defer: bool = False):
+    def _group_convs(x1, x2, b1, b2, blk, G: int):
         """A batched window of G micro-batches (``UNetEngine.bn_groups``): the convolutions
         run over the whole batch, every BatchNorm normalises each micro-batch with its own
         statistics (ref.py:580,583 at batch_size 1).
@@ -227,302 +237,178 @@ class _DoubleConvFn(torch.autograd.Function):
         statistics pass), the second conv applies the per-group BN1 + ReLU in its prologue
         (a1 is never materialised) and its weight gradient re-applies it on load.
         Otherwise BN + ReLU is materialised per group (a1) and the convs read it plainly.
-        a2 (+ pool) is materialised in both — except for the last decoder block with
-        ``defer`` (``UNetEngine.group_head_defer``): it hands out the pre-BN y2 and the group
-        statistics to the C = 32 head kernels, which apply each group's BN + ReLU on load and
-        return the two-pass head gradient with group-major BN-backward partial rows.  y1 / y2
-        stay for the backward."""
+        -> (y1, y2, s1, s2, a1 | None, fused).  The caller materialises a2 (+ pool) in both —
+        except for the last decoder block with ``defer`` (``UNetEngine.group_head_defer``): it
+        hands out the pre-BN y2 and the group statistics to the C = 32 head kernels, which apply
+        each group's BN + ReLU on load and return the two-pass head gradient with group-major
+        BN-backward partial rows.  y1 / y2 stay for the backward."""
         F = _ops()
         p1, p2 = blk.pack1, blk.pack2
         fused = blk.engine.group_fused(x1, G, p1.cout)
-        ctx.fused = fused
         if fused:
             count = float(x1.shape[0] // G * x1.shape[1] * x1.shape[2])   # pixels per group
-            y1, _, r1 = F.conv3_fwd(x1, x2, p1.fwd, b1, None, None, p1.cout, 0, True,
-                                    None, None, None, None, G)
+            y1, _, r1 = F.conv3_fwd(x1, x2, p1.fwd, b1, None, None, p1.cout, 0, True, groups=G)
             s1 = blk.bn1.finalize_group_rows(r1, G, count)
             y2, _, r2 = F.conv3_fwd(y1, None, p2.fwd, b2, s1[:, 2], s1[:, 3], p2.cout, 0, True,
-                                    None, None, None, None, G)
+                                    groups=G)
             s2 = blk.bn2.finalize_group_rows(r2, G, count)
-            a1 = torch.empty(0, device=y1.device, dtype=y1.dtype)
+            a1 = None
         else:
             y1 = F.conv3_fwd(x1, x2, p1.fwd, b1, None, None, p1.cout, 0, False)[0]
             s1 = blk.bn1.finalize_groups(y1, G)
             a1 = F.bn_group_apply(y1, s1, G, False)[0]
             y2 = F.conv3_fwd(a1, None, p2.fwd, b2, None, None, p2.cout, 0, False)[0]
             s2 = blk.bn2.finalize_groups(y2, G)
-        ctx.groups = G
-        ctx.blk, ctx.pool, ctx.defer = blk, pool, defer
-        ctx.has_x2 = x2 is not None
-        if defer:
-            assert not pool, "BN groups: only the head's input is deferred"
-            ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), y1, y2, s1, s2, g1,
-                                  g2, a1)
-            ctx.set_materialize_grads(False)
-            ctx.mark_non_differentiable(s2)
-            return y2, None, s2
-        a2, pooled = F.bn_group_apply(y2, s2, G, pool)
-        ctx.save_for_backward(x1, x2 if x2 is not None else torch.empty(0), y1, y2, s1, s2, g1,
-                              g2, a1)
-        ctx.set_materialize_grads(False)
-        return a2, (pooled if pool else None), None
-
-    @staticmethod
-    def _group_backward(ctx, da2, dpool):
-        F = _ops()
-        x1, x2, y1, y2, s1, s2, g1, g2, a1 = ctx.saved_tensors
-        blk = ctx.blk
-        eng = blk.engine
-        G = ctx.groups
-        x2 = x2 if ctx.has_x2 else None
-        if da2 is None and dpool is None:
-            return (None,) * 15
-        if da2 is not None and not ctx.defer:
-            da2 = da2.contiguous()
-        dpool = dpool.contiguous() if dpool is not None else None
-        bn1, bn2 = blk.bn1.bn, blk.bn2.bn
-        p1, p2 = blk.pack1, blk.pack2
-        w1 = blk.conv1.weight
-        direct = eng.direct_grads
-        fused = ctx.fused
-        # (fused: conv2's input is relu(bn1(y1)) per group, formed on load from y1)
-        xw2, psc, psh = (y1, s1[:, 2], s1[:, 3]) if fused else (a1, None, None)
-        # deferred into the head: its second pass recomputes dA and applies each group's BN2
-        # backward (group-major partial rows from the fused forward, at unit scale)
-        head = getattr(da2, "_ddlpc_head", None) if (ctx.defer and da2 is not None) else None
-        if ctx.defer and head is None:
-            raise RuntimeError("BN groups: the deferred head input has a second autograd consumer")
-        hargs = ((*head, s2, da2._ddlpc_bn_partial, g2) if head is not None else None)
-        hps = getattr(da2, "_ddlpc_bn_pscale", None) if head is not None else None
-        # ---- second conv: per-group BN2 + ReLU (+ unpool + skip sum) backward
-        if head is not None:
-            dy2, dg2, dbe2 = F.head_ce_bn_bwd(*hargs, bn2.weight.grad if direct else None,
-                                              bn2.bias.grad if direct else None, hps, G,
-                                              getattr(da2, "_ddlpc_head_cw", None))
-        else:
-            dy2, dg2, dbe2 = F.bn_group_backward(da2, dpool, y2, s2, g2, G,
-                                                 bn2.weight.grad if direct else None,
-                                                 bn2.bias.grad if direct else None)
-        if direct:
-            dg2 = dbe2 = None
-        # its gradients: at 32 -> 32 channels on the fused levels one kernel (conv3x3_bwd32,
-        # group-major) for both; otherwise the weight gradient (per-group prologue when fused)
-        # and the data gradient (per-group BN1-backward partials in its epilogue when fused)
-        g32 = fused and eng.bwd32 and p2.cin == 32 and p2.cout == 32
-        part1 = None
-        dw2 = None
-        if g32:
-            if direct:
-                da1, part1, _ = F.conv3_bwd32(dy2, y1, s1, p2.dgrad, blk.conv2.weight.grad, G)
-                with eng.wgrad_stream():
-                    eng.ready(bn2.weight, bn2.bias, blk.conv2.weight, blk.conv2.bias)
-            else:
-                da1, part1, dw2 = F.conv3_bwd32(dy2, y1, s1, p2.dgrad, None, G)
-                dw2 = dw2.view_as(blk.conv2.weight)
-        else:
-            if direct:
-                with eng.wgrad_stream(dy2, xw2, s1):
-                    F.conv3_wgrad(dy2, xw2, None, psc, psh, blk.conv2.weight.grad, groups=G)
-                    eng.ready(bn2.weight, bn2.bias, blk.conv2.weight, blk.conv2.bias)
-            else:
-                dw2 = F.conv3_wgrad(dy2, xw2, None, psc, psh, groups=G).view_as(blk.conv2.weight)
-            if fused:
-                da1, _, part1 = F.conv3_fwd(dy2, None, p2.dgrad, None, None, None, p2.cin, 0, False,
-                                            None, None, y1, s1, G)
-            else:
-                da1 = F.conv3_fwd(dy2, None, p2.dgrad, None, None, None, p2.cin, 0, False)[0]
-        # ---- first conv
-        padded_in = x2 is None and x1.shape[-1] != w1.shape[1]     # first layer: 3 -> 8 ch
-        if direct:
-            dy1 = F.bn_group_backward(da1, None, y1, s1, g1, G, bn1.weight.grad, bn1.bias.grad,
-                                      part1)[0]
-            with eng.wgrad_stream(dy1, x1, x2):
-                if padded_in:
-                    w1.grad.add_(F.conv3_wgrad(dy1, x1, None, None, None,
-                                               cin_real=w1.shape[1])[:, :w1.shape[1]])
-                else:
-                    F.conv3_wgrad(dy1, x1, x2, None, None, w1.grad)
-                eng.ready(bn1.weight, bn1.bias, w1, blk.conv1.bias)
-            dg1 = dbe1 = dw1 = None
-        else:
-            dy1, dg1, dbe1 = F.bn_group_backward(da1, None, y1, s1, g1, G, None, None, part1)
-            dw1 = F.conv3_wgrad(dy1, x1, x2, None, None, None,
-                                cin_real=w1.shape[1] if padded_in else 0)
-            dw1 = (dw1[:, :w1.shape[1]] if padded_in else dw1).reshape(w1.shape)
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
-            co1 = x1.shape[-1] if x2 is not None else 0
-            want_sums = x2 is not None and blk.up_is_convt
-            dx1, dx2, sums = F.conv3_fwd(dy1, None, p1.dgrad, None, None, None, p1.cin, co1,
-                                         want_sums)
-            if want_sums:
-                dx1._ddlpc_colsum_rows = sums
-            if x2 is None:
-                dx2 = None
-        if blk.first:
-            eng.join()
-        zb1 = torch.zeros_like(g1) if (not direct and ctx.needs_input_grad[3]) else None
-        zb2 = torch.zeros_like(g2) if (not direct and ctx.needs_input_grad[7]) else None
-        return (dx1, dx2, dw1, zb1, dg1, dbe1, dw2, zb2, dg2, dbe2, None, None, None, None, None)
+        return y1, y2, s1, s2, a1, fused
 
     @staticmethod
     def backward(ctx, da2, dpool, _ds2):
-        if ctx.groups:
-            return _DoubleConvFn._group_backward(ctx, da2, dpool)
+        """One sequence of steps for every variant; what varies enters as data: ``G`` (BN groups:
+        the group BN-backward operator, per-group prologue rows, ``groups=``), ``acc`` (direct
+        gradients: the kernels' output arguments, else None and the results are returned) and
+        the note a deferred consumer left on ``da2``."""
+        if da2 is None and dpool is None:
+            return (None,) * 15
         F = _ops()
-        x1, x2, y1, y2, s1, s2, g1, g2 = ctx.saved_tensors
-        blk = ctx.blk
+        x1, x2, y1, y2, s1, s2, g1, g2, a1 = ctx.saved_tensors
+        blk, G = ctx.blk, ctx.groups
         eng = blk.engine
         x2 = x2 if ctx.has_x2 else None
-        # head gradient still to be formed (two-pass head backward, see _HeadCEFn)
-        head = getattr(da2, "_ddlpc_head", None) if (ctx.defer and da2 is not None) else None
-        if (ctx.defer and head is None and da2 is not None and da2.dim() > 0
-                and all(st == 0 for st in da2.stride())):
-            # the head's zero-stride stand-in lost its attribute: another autograd consumer
-            # of the deferred output summed into it, so the head's gradient would be dropped
-            raise RuntimeError("deferred block output has a second autograd consumer besides "
-                               "the two-pass head; set engine.head_apply = False")
+        bn1, bn2 = blk.bn1.bn, blk.bn2.bn
+        p1, p2 = blk.pack1, blk.pack2
+        w1, w2 = blk.conv1.weight, blk.conv2.weight
+        direct = eng.direct_grads
+        acc = _grad_of if direct else _no_grad
+        # what the consumer of a deferred output left on its gradient: BN-backward partial sums
+        # its kernel already reduced, and from the head the gradient still to be formed (two-pass
+        # head backward, see _HeadCEFn)
+        note = getattr(da2, "_ddlpc_note", None) if ctx.defer else None
+        head = note.head if note is not None else None
+        if ctx.defer and head is None and da2 is not None:
+            if G:
+                raise RuntimeError("BN groups: the deferred head input has a second autograd consumer")
+            if da2.dim() > 0 and all(st == 0 for st in da2.stride()):
+                # the head's zero-stride stand-in lost its note: another autograd consumer of
+                # the deferred output summed into it, so the head's gradient would be dropped
+                raise RuntimeError("deferred block output has a second autograd consumer besides "
+                                   "the two-pass head; set engine.head_apply = False")
         if da2 is not None and head is None:
             da2 = da2.contiguous()
         if dpool is not None:
             dpool = dpool.contiguous()
-        if da2 is None and dpool is None:
-            return (None,) * 15
+
+        def bn_backward(dA, dP, y, s4, gamma, bn, partial):
+            out = dict(dgamma_out=acc(bn.weight), dbeta_out=acc(bn.bias), partial=partial)
+            if G:
+                return F.bn_group_backward(dA, dP, y, s4, gamma, G, **out)
+            return F.bn_backward(dA, dP, y, s4, gamma, None, **out)
+
+        # ---- recompute (same kernels, same bits as the forward)
         x2_bn = ctx.x2_bn
         sc2 = x2_bn[2] if x2_bn is not None else None
         sh2 = x2_bn[3] if x2_bn is not None else None
         if ctx.recompute:
-            y1 = F.conv3_fwd(x1, x2, blk.pack1.fwd, ctx.b1, None, None, blk.pack1.cout, 0, False,
-                             sc2, sh2)[0]
+            y1 = F.conv3_fwd(x1, x2, p1.fwd, ctx.b1, None, None, p1.cout, 0, False,
+                             pscale2=sc2, pshift2=sh2)[0]
         if ctx.recompute_y2:
-            y2 = F.conv3_fwd(y1, None, blk.pack2.fwd, ctx.b2, s1[2], s1[3], blk.pack2.cout, 0, False)[0]
-        # BN-backward partial sums already reduced by the consumer's kernel (deferred BN)
-        part2 = getattr(da2, "_ddlpc_bn_partial", None) if ctx.defer else None
-        # (the class weights of the loss: the second pass must see the first pass's)
-        hcw = getattr(da2, "_ddlpc_head_cw", None) if head is not None else None
-        bn1, bn2 = blk.bn1.bn, blk.bn2.bn
-        direct = eng.direct_grads
-        p1, p2 = blk.pack1, blk.pack2
-        # the 32-channel level: conv2's data and weight gradients in ONE kernel that reads dY2
-        # and y1 once (conv3x3_bwd32.hip; BN1-backward partials in its epilogue)
-        bwd32 = (eng.bwd32 and eng.bnb_epilogue and y1.dim() == 4 and p2.cin == 32 and
-                 p2.cout == 32)
-        # ---- second conv: BN2 + ReLU (+ unpool + skip sum) backward, then its gradients
-        if direct:
-            if head is not None:
-                dy2, _, _ = F.head_ce_bn_bwd(*head, s2, part2, g2, bn2.weight.grad, bn2.bias.grad,
-                                             getattr(da2, "_ddlpc_bn_pscale", None), 0, hcw)
-            else:
-                dy2, _, _ = F.bn_backward(da2, dpool, y2, s2, g2, None, bn2.weight.grad,
-                                          bn2.bias.grad, part2)
-            if bwd32:
-                da1, part1, _ = F.conv3_bwd32(dy2, y1, s1, p2.dgrad, blk.conv2.weight.grad)
-                with eng.wgrad_stream():
-                    eng.ready(bn2.weight, bn2.bias, blk.conv2.weight, blk.conv2.bias)
-            else:
-                with eng.wgrad_stream(dy2, y1, s1):
-                    F.conv3_wgrad(dy2, y1, None, s1[2], s1[3], blk.conv2.weight.grad)
-                    eng.ready(bn2.weight, bn2.bias, blk.conv2.weight, blk.conv2.bias)
-            dg2 = dbe2 = dw2 = None
+            y2 = F.conv3_fwd(y1, None, p2.fwd, ctx.b2, s1[2], s1[3], p2.cout, 0, False)[0]
+        # ---- BN2 + ReLU (+ unpool + skip sum) backward; deferred into the head: its second
+        # pass recomputes dA and applies BN2's backward (the class weights of the loss: the
+        # second pass must see the first pass's)
+        if head is not None:
+            dy2, dg2, dbe2 = F.head_ce_bn_bwd(*head, s2, note.bn_partial, g2,
+                                              dgamma_out=acc(bn2.weight), dbeta_out=acc(bn2.bias),
+                                              pscale=note.bn_pscale, groups=G,
+                                              class_weight=note.class_weight)
         else:
-            if head is not None:
-                dy2, dg2, dbe2 = F.head_ce_bn_bwd(*head, s2, part2, g2, None, None,
-                                                  getattr(da2, "_ddlpc_bn_pscale", None), 0, hcw)
+            dy2, dg2, dbe2 = bn_backward(da2, dpool, y2, s2, g2, bn2,
+                                         note.bn_partial if note is not None else None)
+        # ---- conv2's gradients.  Its input is relu(bn1(y1)), formed on load from y1 (per group
+        # on the fused group levels; the unfused ones materialised a1).  ``epi``: the data
+        # gradient's epilogue also reduces BN1 backward's (sum dyh, sum dyh * xhat) against y1
+        # (2-D).  32 -> 32 channels with the epilogue: ONE kernel for both gradients that reads
+        # dY2 and y1 once (conv3x3_bwd32.hip, group-major with groups)
+        epi = ctx.fused if G else (eng.bnb_epilogue and y1.dim() == 4)
+        if epi and eng.bwd32 and p2.cin == 32 and p2.cout == 32:
+            da1, part1, dw2 = F.conv3_bwd32(dy2, y1, s1, p2.dgrad, dw_out=acc(w2), groups=G)
+            eng.ready_after(bn2.weight, bn2.bias, w2, blk.conv2.bias)
+        else:
+            if G and not ctx.fused:
+                xw2, psc, psh = a1, None, None
             else:
-                dy2, dg2, dbe2 = F.bn_backward(da2, dpool, y2, s2, g2, None, None, None, part2)
-            if bwd32:
-                da1, part1, dw2 = F.conv3_bwd32(dy2, y1, s1, p2.dgrad)
-                dw2 = dw2.view_as(blk.conv2.weight)
-            else:
-                dw2 = F.conv3_wgrad(dy2, y1, None, s1[2], s1[3]).view_as(blk.conv2.weight)
-        if not bwd32 and eng.bnb_epilogue and y1.dim() == 4:
-            # the epilogue also reduces BN1 backward's (sum dyh, sum dyh*xhat) against y1
+                xw2, psc, psh = (y1, s1[:, 2], s1[:, 3]) if G else (y1, s1[2], s1[3])
+            with eng.wgrad_stream(dy2, xw2, s1):
+                dw2 = F.conv3_wgrad(dy2, xw2, None, psc, psh, out=acc(w2), groups=G)
+                eng.ready(bn2.weight, bn2.bias, w2, blk.conv2.bias)
             da1, _, part1 = F.conv3_fwd(dy2, None, p2.dgrad, None, None, None, p2.cin, 0, False,
-                                        None, None, y1, s1)
-        elif not bwd32:
-            part1 = None
-            da1, _, _ = F.conv3_fwd(dy2, None, p2.dgrad, None, None, None, p2.cin, 0, False)
-        # ---- first conv
-        w1 = blk.conv1.weight
-        padded_in = x2 is None and x1.shape[-1] != w1.shape[1]   # first layer: 3 -> 8 ch
+                                        bnb_y=y1 if epi else None, bnb_s4=s1 if epi else None,
+                                        groups=G if epi else 0)
+            if not epi:
+                part1 = None
+        # ---- BN1 backward and conv1's weight gradient
+        cin = w1.shape[1]
+        padded_in = x2 is None and x1.shape[-1] != cin           # first layer: 3 -> 8 ch
         # first block, input gradient not wanted: the weight gradient is BN1 backward's only
         # consumer, so it applies that backward on load (dY prologue) from dA1 and y1 — the
         # apply pass (read dA1 + y1, write dY1) is skipped
-        wg_pro = (padded_in and part1 is not None and eng.wgrad_dy_prologue and
+        wg_pro = (not G and padded_in and part1 is not None and eng.wgrad_dy_prologue and
                   not ctx.needs_input_grad[0])
         # 32-output-channel concat conv (dec1.a): its weight-gradient kernel (every input
         # chunk per workgroup) applies BN1's backward on load from dA1 and y1 and stores the
         # formed dY1 for the data gradient — no separate apply pass (read dA1 + y1, write dY1).
         # It runs on the compute stream: the data gradient below reads its dY1
-        c32p = (not wg_pro and part1 is not None and eng.c32_bnp and x2_bn is None and
+        c32p = (not G and not wg_pro and part1 is not None and eng.c32_bnp and x2_bn is None and
                 eng.c32_eligible(x1, x2, w1.shape[0]))
-        if c32p:
-            dy1 = torch.empty_like(da1)
-            if direct:
-                coefs, _, _ = F.bn_grad_coefs(part1, y1, s1, g1, bn1.weight.grad, bn1.bias.grad)
-                F.conv3_wgrad(da1, x1, x2, None, None, w1.grad, None, None, y1, s1, coefs,
-                              dy_out=dy1)
-                with eng.wgrad_stream():     # (readiness after both streams' writes)
-                    eng.ready(bn1.weight, bn1.bias, w1, blk.conv1.bias)
-                dg1 = dbe1 = dw1 = None
-            else:
-                coefs, dg1, dbe1 = F.bn_grad_coefs(part1, y1, s1, g1)
-                dw1 = F.conv3_wgrad(da1, x1, x2, None, None, None, None, None, y1, s1, coefs,
-                                    dy_out=dy1).reshape(w1.shape)
-        elif direct and wg_pro:
-            coefs, _, _ = F.bn_grad_coefs(part1, y1, s1, g1, bn1.weight.grad, bn1.bias.grad)
-            with eng.wgrad_stream(da1, y1, x1, coefs, s1):
-                w1.grad.add_(F.conv3_wgrad(da1, x1, None, None, None, None, None, None,
-                                           y1, s1, coefs, cin_real=w1.shape[1])[:, :w1.shape[1]])
-                eng.ready(bn1.weight, bn1.bias, w1, blk.conv1.bias)
-            dg1 = dbe1 = dw1 = None
-        elif wg_pro:
-            coefs, dg1, dbe1 = F.bn_grad_coefs(part1, y1, s1, g1)
-            dw1 = F.conv3_wgrad(da1, x1, None, None, None, None, None, None, y1, s1, coefs,
-                                cin_real=w1.shape[1])
-            dw1 = dw1[:, :w1.shape[1]].reshape(w1.shape)
-        elif direct:
-            dy1, _, _ = F.bn_backward(da1, None, y1, s1, g1, None, bn1.weight.grad, bn1.bias.grad,
-                                      part1)
-            with eng.wgrad_stream(dy1, x1, x2, x2_bn):
-                if padded_in:
-                    w1.grad.add_(F.conv3_wgrad(dy1, x1, None, None, None,
-                                               cin_real=w1.shape[1])[:, :w1.shape[1]])
-                else:
-                    F.conv3_wgrad(dy1, x1, x2, None, None, w1.grad, sc2, sh2)
-                eng.ready(bn1.weight, bn1.bias, w1, blk.conv1.bias)
-            dg1 = dbe1 = dw1 = None
+        if wg_pro or c32p:
+            dy1 = torch.empty_like(da1) if c32p else None
+            coefs, dg1, dbe1 = F.bn_grad_coefs(part1, y1, s1, g1, dgamma_out=acc(bn1.weight),
+                                               dbeta_out=acc(bn1.bias))
+            src, marked = da1, (da1, y1, x1, coefs, s1)
+            pro = dict(dy_y=y1, dy_s4=s1, dy_coefs=coefs, dy_out=dy1)
         else:
-            dy1, dg1, dbe1 = F.bn_backward(da1, None, y1, s1, g1, None, None, None, part1)
-            dw1 = F.conv3_wgrad(dy1, x1, x2, None, None, None, sc2, sh2,
-                                cin_real=w1.shape[1] if padded_in else 0)
-            dw1 = (dw1[:, :w1.shape[1]] if padded_in else dw1).reshape(w1.shape)
+            dy1, dg1, dbe1 = bn_backward(da1, None, y1, s1, g1, bn1, part1)
+            src, marked = dy1, (dy1, x1, x2, x2_bn)
+            pro = {}
+        with contextlib.nullcontext() if c32p else eng.wgrad_stream(*marked):
+            # (the padded first layer: the kernel returns 8 input channels, .grad has 3)
+            dw1 = F.conv3_wgrad(src, x1, x2, None, None, out=None if padded_in else acc(w1),
+                                pscale2=sc2, pshift2=sh2, cin_real=cin if padded_in else 0, **pro)
+            if padded_in:
+                dw1 = dw1[:, :cin]
+                if direct:
+                    w1.grad.add_(dw1)
+            if not c32p:
+                eng.ready(bn1.weight, bn1.bias, w1, blk.conv1.bias)
+        if c32p:
+            eng.ready_after(bn1.weight, bn1.bias, w1, blk.conv1.bias)   # (both streams' writes)
+        # ---- conv1's data gradient, split across the concat inputs
         dx1 = dx2 = None
         if not wg_pro and (ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1])):
-            c_x1 = x1.shape[-1]
-            co1 = c_x1 if x2 is not None else 0
             # for a decoder block dx1 is the transposed conv's output gradient: keep the
             # epilogue's per-channel sums, they are that conv's bias gradient
             want_sums = x2 is not None and blk.up_is_convt
-            dx1, dx2, sums = F.conv3_fwd(dy1, None, p1.dgrad, None, None, None, p1.cin, co1,
-                                         want_sums)
+            dx1, dx2, sums = F.conv3_fwd(dy1, None, p1.dgrad, None, None, None, p1.cin,
+                                         x1.shape[-1] if x2 is not None else 0, want_sums)
             if want_sums:
-                dx1._ddlpc_colsum_rows = sums
+                dx1._ddlpc_note = _GradNote(colsum_rows=sums)
             if x2 is None:
                 dx2 = None
         if blk.first:
             eng.join()                   # last backward node: main stream waits for wgrads
+        if direct:
+            return (dx1, dx2) + (None,) * 13
         # conv biases feeding a training-mode BN have an exactly-zero gradient
-        zb1 = torch.zeros_like(g1) if (not direct and ctx.needs_input_grad[3]) else None
-        zb2 = torch.zeros_like(g2) if (not direct and ctx.needs_input_grad[7]) else None
-        return (dx1, dx2, dw1, zb1, dg1, dbe1, dw2, zb2, dg2, dbe2, None, None, None, None, None)
+        zb1 = torch.zeros_like(g1) if ctx.needs_input_grad[3] else None
+        zb2 = torch.zeros_like(g2) if ctx.needs_input_grad[7] else None
+        return (dx1, dx2, dw1.reshape(w1.shape), zb1, dg1, dbe1, dw2.view_as(w2), zb2, dg2, dbe2,
+                None, None, None, None, None)
 
 
 class _ConvTFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, pack: _ConvPack, engine, bn: Optional[torch.Tensor] = None):
         # bn: statistics of a deferred-BN input (x = pre-BN y2 of the previous block)
-        out = _ops().convt_fwd(x, pack.fwd, b, pack.cout, bn)
+        out = _ops().convt_fwd(x, pack.fwd, b, pack.cout, bn4=bn)
         ctx.save_for_backward(x, bn if bn is not None else torch.empty(0))
         ctx.has_bn = bn is not None
         ctx.pack = pack
@@ -535,42 +421,36 @@ class _ConvTFn(torch.autograd.Function):
         x, bn = ctx.saved_tensors
         bn = bn if ctx.has_bn else None
         dout = dout.contiguous()
-        eng = ctx.engine
-        conv = ctx.pack.conv
-        rows = getattr(dout, "_ddlpc_colsum_rows", None)
+        eng, pack = ctx.engine, ctx.pack
+        conv = pack.conv
+        direct = eng.direct_grads
+        note = getattr(dout, "_ddlpc_note", None)
+        grads = dict(dw_out=conv.weight.grad if direct else None,
+                     db_out=conv.bias.grad if direct else None,
+                     colsum_rows=note.colsum_rows if note is not None else None, bn4=bn)
+        dx = part = None
         if (eng.convt_fused and ctx.needs_input_grad[0] and x.dim() == 4 and x.shape[-1] == 64
-                and ctx.pack.cout == 64):
+                and pack.cout == 64):
             # 64 -> 64-channel 2-D transposed conv (the 256^2 level): one kernel reads dOut
             # once for both gradients (convt_bwd_fused; other shapes fall back inside)
-            if eng.direct_grads:
-                dx, part, _, _ = F.convt_bwd_fused(x, dout, ctx.pack.dgrad, conv.weight.grad,
-                                                   conv.bias.grad, rows, bn)
-                with eng.wgrad_stream():
+            dx, part, dw, db = F.convt_bwd_fused(x, dout, pack.dgrad, **grads)
+            eng.ready_after(conv.weight, conv.bias)
+        else:
+            if ctx.needs_input_grad[0]:
+                dx, part = F.convt_dgrad(dout, pack.dgrad, pack.cin,
+                                         bny=x if bn is not None else None, bn4=bn)
+            side = eng.side_convt
+            with (eng.wgrad_stream(x, dout, grads["colsum_rows"], bn) if side else
+                  contextlib.nullcontext()):
+                dw, db = F.convt_wgrad(x, dout, **grads)
+                if side:
                     eng.ready(conv.weight, conv.bias)
-                dw = db = None
-            else:
-                dx, part, dw, db = F.convt_bwd_fused(x, dout, ctx.pack.dgrad, None, None, rows, bn)
-                dw = dw.view_as(conv.weight)
-            if bn is not None:
-                dx._ddlpc_bn_partial = part
-            return dx, dw, db, None, None, None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx, part = F.convt_dgrad(dout, ctx.pack.dgrad, ctx.pack.cin, x if bn is not None else None,
-                                     bn)
-            if bn is not None:
-                dx._ddlpc_bn_partial = part
-        if eng.direct_grads:
-            if eng.side_convt:
-                with eng.wgrad_stream(x, dout, rows, bn):
-                    F.convt_wgrad(x, dout, conv.weight.grad, conv.bias.grad, rows, bn)
-                    eng.ready(conv.weight, conv.bias)
-            else:
-                F.convt_wgrad(x, dout, conv.weight.grad, conv.bias.grad, rows, bn)
-                with eng.wgrad_stream():
-                    eng.ready(conv.weight, conv.bias)
+            if not side:
+                eng.ready_after(conv.weight, conv.bias)
+        if bn is not None and dx is not None:
+            dx._ddlpc_note = _GradNote(bn_partial=part)
+        if direct:
             return dx, None, None, None, None, None
-        dw, db = F.convt_wgrad(x, dout, None, None, rows, bn)
         return dx, dw.view_as(conv.weight), db, None, None, None
 
 
@@ -598,11 +478,12 @@ class _HeadCEFn(torch.autograd.Function):
         groups = bn.shape[0] if (bn is not None and bn.dim() == 3) else 0
         if (bn is not None and engine.head_apply and engine.head_fused_fwd
                 and any(ctx.needs_input_grad[:3])):
-            out3, wrows, brows = _ops().head_ce_fwd_stats(a, wh, bh, labels, ignore_index, bn, groups, cw)
+            out3, wrows, brows = _ops().head_ce_fwd_stats(a, wh, bh, labels, ignore_index, bn,
+                                                          groups=groups, class_weight=cw)
             ctx.rows = (wrows, brows)
         else:
             assert groups == 0, "grouped head statistics need the fused training forward"
-            out3 = _ops().head_ce_fwd(a, wh, bh, labels, ignore_index, bn, cw)
+            out3 = _ops().head_ce_fwd(a, wh, bh, labels, ignore_index, bn4=bn, class_weight=cw)
         ctx.save_for_backward(a, wh, bh, labels, out3, bn if bn is not None else torch.empty(0))
         ctx.has_bn = bn is not None
         ctx.ignore_index = ignore_index
@@ -617,52 +498,40 @@ class _HeadCEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, dcorrect):
+        F = _ops()
         a, wh, bh, labels, out3, bn = ctx.saved_tensors
         bn = bn if ctx.has_bn else None
         gs = dloss.reshape(1).float().contiguous() if dloss is not None else None
         eng = ctx.engine
-        cw = ctx.cw
+        head = eng.head
+        direct = eng.direct_grads
+        grads = dict(dw_out=head.weight.grad if direct else None,
+                     db_out=head.bias.grad if direct else None)
         # two-pass backward with the deferred BatchNorm: this pass reduces dWh, dbh and the
         # BN partials without storing dA; the block's backward then runs head_ce_bn_bwd,
         # which recomputes dA and applies the BatchNorm backward in registers (no dA
         # round trip through HBM, no separate BN-apply pass).  engine.head_apply = False: one pass
-        two_pass = bn is not None and eng.head_apply
+        two_pass = ctx.rows is not None or (bn is not None and eng.head_apply)
+        scale = None
         if ctx.rows is not None:
             # statistics already reduced by the forward at unit scale: scale = dL / count
-            wrows, brows = ctx.rows
-            scale = _ops().head_grad_scale(out3, gs)       # one launch, on the device
-            K, C = wh.shape
-            head = eng.head
-            if eng.direct_grads:
-                _ops().head_wgrad_from_rows(wrows, scale, K, C, head.weight.grad, head.bias.grad)
-                with eng.wgrad_stream():
-                    eng.ready(head.weight, head.bias)
-                dw = db = None
-            else:
-                dw, db = _ops().head_wgrad_from_rows(wrows, scale, K, C)
-            da = eng.zero_scalar(a).expand(a.shape)
-            da._ddlpc_head = (a, wh, bh, labels, out3, gs, ctx.ignore_index)
-            da._ddlpc_head_cw = cw
-            da._ddlpc_bn_partial = brows
-            da._ddlpc_bn_pscale = scale
-            return da, dw, db, None, None, None, None, None
-        if eng.direct_grads:
-            head = eng.head
-            da, _, _, part = _ops().head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index,
-                                                head.weight.grad, head.bias.grad, bn, not two_pass, cw)
-            with eng.wgrad_stream():
-                eng.ready(head.weight, head.bias)
-            dw = db = None
+            wrows, part = ctx.rows
+            scale = F.head_grad_scale(out3, gs=gs)         # one launch, on the device
+            dw, db = F.head_wgrad_from_rows(wrows, scale, wh.shape[0], wh.shape[1], **grads)
         else:
-            da, dw, db, part = _ops().head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index,
-                                                  None, None, bn, not two_pass, cw)
+            da, dw, db, part = F.head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index, bn4=bn,
+                                             store_da=not two_pass, class_weight=ctx.cw, **grads)
+        eng.ready_after(head.weight, head.bias)
         if two_pass:
-            # stand-in gradient of the right shape (no storage); the consumer recognises it
+            # stand-in gradient of the right shape (no storage); the consumer recognises it by
+            # the note's head arguments
             da = eng.zero_scalar(a).expand(a.shape)
-            da._ddlpc_head = (a, wh, bh, labels, out3, gs, ctx.ignore_index)
-            da._ddlpc_head_cw = cw
         if bn is not None:
-            da._ddlpc_bn_partial = part
+            da._ddlpc_note = _GradNote(
+                head=(a, wh, bh, labels, out3, gs, ctx.ignore_index) if two_pass else None,
+                class_weight=ctx.cw, bn_partial=part, bn_pscale=scale)
+        if direct:
+            dw = db = None
         return da, dw, db, None, None, None, None, None
 
 
@@ -918,7 +787,7 @@ class UNetEngine:
             c2 = 2 * bn.num_features
             _ops().bn_running_apply(bn.running_mean, bn.running_var,
                                     self._bn_arena[:n, off:off + c2], float(mom),
-                                    bn.num_batches_tracked)
+                                    nbt=bn.num_batches_tracked)
 
     def enable_direct_grads(self, grad_ready=None):
         for p in self.model.parameters():
@@ -987,6 +856,12 @@ class UNetEngine:
             for p in params:
                 self.grad_ready(p)
 
+    def ready_after(self, *params):
+        """``ready`` for gradients a compute-stream kernel wrote: reported from the side stream
+        once it has joined the compute stream, like every other readiness call."""
+        with self.wgrad_stream():
+            self.ready(*params)
+
     # ------------------------------------------------------------------ weights
     def _params_version(self):
         return sum(p.conv.weight._version for p in self.packs)
@@ -1023,7 +898,7 @@ class UNetEngine:
         cl = torch.channels_last if nd == 4 else torch.channels_last_3d
         if not (x.is_contiguous() or x.is_contiguous(memory_format=cl)):
             x = x.contiguous(memory_format=cl)
-        return _ops().to_nhwc_bf16(x, 8)
+        return _ops().to_nhwc_bf16(x, cpad=8)
 
     # ------------------------------------------------------------------ graph
     def features(self, x: torch.Tensor, defer_last: bool = False):
@@ -1129,7 +1004,7 @@ class UNetEngine:
             logits = torch.einsum("n...c,kc->n...k", a.float(), wh) + bh
             return _nhwc_shape_to_nchw(logits)
         a, s = self.features(x, defer_last=True)
-        return _ops().head_logits(a, wh.detach().contiguous(), bh.detach(), s)
+        return _ops().head_logits(a, wh.detach().contiguous(), bh.detach(), bn4=s)
 
     def loss_and_correct(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int = -100,
                          class_weight: Optional[torch.Tensor] = None):
