@@ -1760,6 +1760,83 @@ std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum
   return {params, color};
 }
 
+// crop_gather under a zoom and a rotation: wparams int64 [B, 6] of (scene, cy, cx, code, A, Bm)
+// rows, 16.16 fixed point (the recipe: data.hip) -> {x bf16 [B, T, T, cpad], y int64}
+std::vector<at::Tensor> warp_gather(const at::Tensor& scenes, const at::Tensor& labels,
+                                    const at::Tensor& table, const at::Tensor& wparams,
+                                    const c10::optional<at::Tensor>& color, int64_t tile,
+                                    int64_t cpad) {
+  CHECK_DEV(scenes); CHECK_CONTIG(scenes); CHECK_DEV(labels); CHECK_CONTIG(labels);
+  CHECK_DEV(table); CHECK_CONTIG(table); CHECK_DEV(wparams); CHECK_CONTIG(wparams);
+  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
+  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
+              "labels must be uint8 [pixels]");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
+              "table must be int64 [n, 3] (pixel offset, H, W)");
+  TORCH_CHECK(wparams.scalar_type() == at::kLong && wparams.dim() == 2 && wparams.size(1) == 6,
+              "wparams must be int64 [B, 6] (scene, cy, cx, code, A, Bm)");
+  const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0);
+  TORCH_CHECK(cpad == 4 || cpad == 8, "cpad must be 4 or 8");
+  TORCH_CHECK(in_ch >= 1 && in_ch <= cpad, "1 <= in_ch <= cpad");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  TORCH_CHECK(n < (1LL << 31), "too many scenes");
+  TORCH_CHECK(labels.device() == scenes.device() && table.device() == scenes.device() &&
+              wparams.device() == scenes.device(), "warp_gather: tensors on different devices");
+  const bool has_color = color.has_value() && color->defined();
+  if (has_color) {
+    CHECK_DEV(*color); CHECK_CONTIG(*color); CHECK_F32(*color);
+    TORCH_CHECK(color->dim() == 2 && color->size(0) == B && color->size(1) == 2 &&
+                color->device() == scenes.device(), "color must be fp32 [B, 2] (gain, bias)");
+  }
+  const int64_t nb = crop_gather_blocks((int)tile);
+  TORCH_CHECK(B * nb * nb < (1LL << 31), "warp_gather: batch too large");
+  c10::DeviceGuard guard(scenes.device());
+  at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
+  at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
+  if (B > 0)
+    warp_gather_launch(scenes.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
+                       (int)n, (long long)labels.size(0), wparams.data_ptr<int64_t>(),
+                       has_color ? color->data_ptr<float>() : nullptr, (int)B, (int)in_ch, (int)tile,
+                       (int)cpad, bptr_mut(x), y.data_ptr<int64_t>(), cur_stream());
+  return {x, y};
+}
+
+// virtual sample numbers -> {wparams int64 [B, 6], color fp32 [B, 2]}: crop_params with a zoom
+// step and a rotation drawn from the int32 tables steps [S] and rot [T, 2] (data.hip)
+std::vector<at::Tensor> warp_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
+                                    const at::Tensor& steps, const at::Tensor& rot, int64_t seed,
+                                    int64_t tile, int64_t mode, double gain_jitter, double bias_jitter) {
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(cum); CHECK_CONTIG(cum); CHECK_DEV(table); CHECK_CONTIG(table);
+  CHECK_DEV(steps); CHECK_CONTIG(steps); CHECK_DEV(rot); CHECK_CONTIG(rot);
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
+              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
+  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
+              "cum must be int64 [n + 1]");
+  TORCH_CHECK(steps.scalar_type() == at::kInt && steps.dim() == 1 && steps.size(0) >= 1 &&
+              steps.size(0) <= 65536, "steps must be int32 [S], 1 <= S <= 65536");
+  TORCH_CHECK(rot.scalar_type() == at::kInt && rot.dim() == 2 && rot.size(1) == 2 && rot.size(0) >= 1 &&
+              rot.size(0) <= 65536, "rot must be int32 [T, 2] (cos, sin), 1 <= T <= 65536");
+  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device() &&
+              steps.device() == idx.device() && rot.device() == idx.device(),
+              "warp_params: tensors on different devices");
+  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  c10::DeviceGuard guard(idx.device());
+  const int64_t B = idx.numel();
+  TORCH_CHECK(B < (1LL << 31), "too many samples");
+  at::Tensor wparams = at::empty({B, 6}, idx.options().dtype(at::kLong));
+  at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
+  if (B > 0)
+    warp_params_launch(idx.data_ptr<int64_t>(), (int)B, cum.data_ptr<int64_t>(), table.data_ptr<int64_t>(),
+                       (int)table.size(0), steps.data_ptr<int>(), (int)steps.size(0), rot.data_ptr<int>(),
+                       (int)rot.size(0), (uint32_t)(seed & 0xffffffff), (int)tile, (int)mode,
+                       (float)gain_jitter, (float)bias_jitter, wparams.data_ptr<int64_t>(),
+                       color.data_ptr<float>(), cur_stream());
+  return {wparams, color};
+}
+
 // ------------------------------------------------------------------------ scene prediction
 static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
   CHECK_DEV(origins); CHECK_CONTIG(origins);
@@ -1996,6 +2073,10 @@ TORCH_LIBRARY(ddlpc, m) {
         "int tile, int cpad) -> Tensor[]");
   m.def("crop_params(Tensor idx, Tensor cum, Tensor table, int seed, int tile, int mode, "
         "float gain_jitter, float bias_jitter) -> Tensor[]");
+  m.def("warp_gather(Tensor scenes, Tensor labels, Tensor table, Tensor wparams, Tensor? color, "
+        "int tile, int cpad) -> Tensor[]");
+  m.def("warp_params(Tensor idx, Tensor cum, Tensor table, Tensor steps, Tensor rot, int seed, int tile, "
+        "int mode, float gain_jitter, float bias_jitter) -> Tensor[]");
   m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad, Tensor? codes=None) -> Tensor");
   // (the windows of one call must be pairwise disjoint: acc is updated without atomics)
   m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
@@ -2043,6 +2124,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("tile_gather", &ddlpc::tile_gather);
   m.impl("crop_gather", &ddlpc::crop_gather);
   m.impl("crop_params", &ddlpc::crop_params);
+  m.impl("warp_gather", &ddlpc::warp_gather);
+  m.impl("warp_params", &ddlpc::warp_params);
   m.impl("window_gather", &ddlpc::window_gather);
   m.impl("head_predict_accum", &ddlpc::head_predict_accum);
   m.impl("scene_finalize", &ddlpc::scene_finalize);

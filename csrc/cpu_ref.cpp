@@ -1163,6 +1163,142 @@ std::vector<Tensor> crop_params(const Tensor& idx, const Tensor& cum, const Tens
   return {params, color};
 }
 
+// csrc/data.hip warp_params_kernel / warp_gather_kernel, bit for bit: 16.16 fixed-point affine
+// coordinates, bilinear image taps (every float operation rounds on its own), nearest labels
+std::vector<Tensor> warp_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+                                const Tensor& wparams, const optional<Tensor>& color, int64_t tile,
+                                int64_t cpad) {
+  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
+  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
+              "labels must be uint8 [pixels]");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
+              "table must be int64 [n, 3] (pixel offset, H, W)");
+  TORCH_CHECK(wparams.scalar_type() == at::kLong && wparams.dim() == 2 && wparams.size(1) == 6,
+              "wparams must be int64 [B, 6] (scene, cy, cx, code, A, Bm)");
+  const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0), P = labels.size(0);
+  TORCH_CHECK(cpad == 4 || cpad == 8, "cpad must be 4 or 8");
+  TORCH_CHECK(in_ch >= 1 && in_ch <= cpad, "1 <= in_ch <= cpad");
+  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
+  const bool has_color = has(color);
+  Tensor cc;
+  if (has_color) {
+    TORCH_CHECK(color->scalar_type() == at::kFloat && color->dim() == 2 && color->size(0) == B &&
+                color->size(1) == 2, "color must be fp32 [B, 2] (gain, bias)");
+    cc = color->contiguous();
+  }
+  const Tensor sc = scenes.contiguous(), lc = labels.contiguous(), tc = table.contiguous(),
+               wc = wparams.contiguous();
+  const uint8_t* sp = sc.data_ptr<uint8_t>();
+  const uint8_t* lp = lc.data_ptr<uint8_t>();
+  const int64_t* tp = tc.data_ptr<int64_t>();
+  const int64_t* wp = wc.data_ptr<int64_t>();
+  const float* cp = has_color ? cc.data_ptr<float>() : nullptr;
+  Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
+  Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
+  int64_t* yp = y.data_ptr<int64_t>();
+  auto* xp = x.data_ptr<c10::BFloat16>();
+  constexpr int64_t kCoef = 1LL << 20, kCentre = 1LL << 46;
+  at::parallel_for(0, B * tile, 16, [&](int64_t row0, int64_t row1) {
+    for (int64_t row = row0; row < row1; ++row) {
+      const int64_t b = row / tile, oy = row - b * tile;
+      const int64_t s = wp[6 * b], cy = wp[6 * b + 1], cx = wp[6 * b + 2], A = wp[6 * b + 4], Bm = wp[6 * b + 5];
+      const int code = (int)wp[6 * b + 3] & 7;
+      const bool listed = s >= 0 && s < n;
+      const int64_t off = listed ? tp[3 * s] : 0, H = listed ? tp[3 * s + 1] : 1, W = listed ? tp[3 * s + 2] : 1;
+      const bool valid = listed && H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30) && off >= 0 &&
+                         off <= P && H * W <= P - off && A >= -kCoef && A <= kCoef && Bm >= -kCoef &&
+                         Bm <= kCoef && cy > -kCentre && cy < kCentre && cx > -kCentre && cx < kCentre;
+      const float gain = has_color ? cp[2 * b] : 1.f, bias = has_color ? cp[2 * b + 1] : 0.f;
+      for (int64_t ox = 0; ox < tile; ++ox) {
+        const int64_t e = row * tile + ox;
+        c10::BFloat16* o = xp + e * cpad;
+        if (!valid) {
+          yp[e] = -100;
+          for (int64_t ch = 0; ch < cpad; ++ch) o[ch] = c10::BFloat16(0.f);
+          continue;
+        }
+        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+        if (code & 2) a = tile - 1 - a;
+        if (code & 1) c = tile - 1 - c;
+        const int64_t v2 = 2 * a - (tile - 1), u2 = 2 * c - (tile - 1);
+        const int64_t py = cy + ((Bm * u2 + A * v2) >> 1), px = cx + ((A * u2 - Bm * v2) >> 1);
+        const int64_t iy = py >> 16, ix = px >> 16;
+        const float wy = (float)(py & 65535) * (1.0f / 65536.0f), wx = (float)(px & 65535) * (1.0f / 65536.0f);
+        const int64_t r0 = off + reflect_index(iy, H) * W, r1 = off + reflect_index(iy + 1, H) * W;
+        const int64_t c0 = reflect_index(ix, W), c1 = reflect_index(ix + 1, W);
+        yp[e] = (int64_t)lp[off + reflect_index((py + 32768) >> 16, H) * W + reflect_index((px + 32768) >> 16, W)];
+        for (int64_t ch = 0; ch < cpad; ++ch) {
+          float v = 0.f;
+          if (ch < in_ch) {
+            const float p00 = (float)sp[(r0 + c0) * in_ch + ch], p01 = (float)sp[(r0 + c1) * in_ch + ch];
+            const float p10 = (float)sp[(r1 + c0) * in_ch + ch], p11 = (float)sp[(r1 + c1) * in_ch + ch];
+            volatile float mt = (p01 - p00) * wx;
+            volatile float top = p00 + mt;
+            volatile float mb = (p11 - p10) * wx;
+            volatile float bot = p10 + mb;
+            volatile float d = bot - top;
+            volatile float mv = d * wy;
+            volatile float val = top + mv;
+            v = (float)val / 255.0f;
+            if (has_color) {
+              volatile float m = v * gain;
+              volatile float t = m + bias;
+              v = std::fmin(std::fmax((float)t, 0.f), 1.f);
+            }
+          }
+          o[ch] = c10::BFloat16(v);
+        }
+      }
+    }
+  });
+  return {x, y};
+}
+
+std::vector<Tensor> warp_params(const Tensor& idx, const Tensor& cum, const Tensor& table, const Tensor& steps,
+                                const Tensor& rot, int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
+                                double bias_jitter) {
+  TORCH_CHECK(steps.scalar_type() == at::kInt && steps.dim() == 1 && steps.size(0) >= 1 &&
+              steps.size(0) <= 65536, "steps must be int32 [S], 1 <= S <= 65536");
+  TORCH_CHECK(rot.scalar_type() == at::kInt && rot.dim() == 2 && rot.size(1) == 2 && rot.size(0) >= 1 &&
+              rot.size(0) <= 65536, "rot must be int32 [T, 2] (cos, sin), 1 <= T <= 65536");
+  // scene, code and colour are crop_params's (the same draws r0, r3, r4, r5)
+  const std::vector<Tensor> crop = crop_params(idx, cum, table, seed, tile, mode, gain_jitter, bias_jitter);
+  const Tensor ix = idx.contiguous(), tc = table.contiguous(), stc = steps.contiguous(), rc = rot.contiguous();
+  const int64_t B = ix.numel(), S = steps.size(0), T = rot.size(0);
+  const int64_t* ip = ix.data_ptr<int64_t>();
+  const int64_t* tp = tc.data_ptr<int64_t>();
+  const int* stp = stc.data_ptr<int>();
+  const int* rp = rc.data_ptr<int>();
+  const int* pp = crop[0].data_ptr<int>();
+  Tensor wparams = at::empty({B, 6}, idx.options().dtype(at::kLong));
+  int64_t* wp = wparams.data_ptr<int64_t>();
+  const uint32_t skey = mix32((uint32_t)(seed & 0xffffffff) ^ 0xC2B2AE35u);
+  // 16.16 centre of an F-pixel footprint drawn from max(size - F, 0) + 1 origins (unsigned: a
+  // wild table entry wraps, as on the GPU)
+  auto centre = [](uint32_t r, int64_t size, int64_t F) {
+    const uint64_t cnt = (size > F ? (uint64_t)size - (uint64_t)F : 0u) + 1u;
+    const uint64_t o = ((uint64_t)r * cnt) >> 32;
+    return (int64_t)((2u * o + (uint64_t)F - 1u) * 32768u);
+  };
+  for (int64_t i = 0; i < B; ++i) {
+    const uint64_t s = (uint64_t)ip[i];
+    const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
+    auto draw = [key](int j) { return mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u); };
+    const int64_t lo = pp[4 * i], H = tp[3 * lo + 1], W = tp[3 * lo + 2];
+    const int64_t step = stp[((uint64_t)draw(6) * (uint64_t)S) >> 32];
+    const int64_t k = (int64_t)(((uint64_t)draw(7) * (uint64_t)T) >> 32);
+    const int64_t c = rp[2 * k], sn = rp[2 * k + 1];
+    const int64_t F = (tile * step + 65535) >> 16;
+    wp[6 * i] = lo;
+    wp[6 * i + 1] = centre(draw(1), H, F);
+    wp[6 * i + 2] = centre(draw(2), W, F);
+    wp[6 * i + 3] = pp[4 * i + 3];
+    wp[6 * i + 4] = (step * c + 32768) >> 16;
+    wp[6 * i + 5] = (step * sn + 32768) >> 16;
+  }
+  return {wparams, crop[1]};
+}
+
 void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& origins,
                         const Tensor& win, Tensor& acc, const optional<Tensor>& bn4,
                         const optional<Tensor>& codes) {
@@ -1297,6 +1433,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("window_gather", &window_gather);
   m.impl("crop_gather", &crop_gather);
   m.impl("crop_params", &crop_params);
+  m.impl("warp_gather", &warp_gather);
+  m.impl("warp_params", &warp_params);
   m.impl("head_predict_accum", &head_predict_accum);
   m.impl("scene_finalize", &scene_finalize);
 }

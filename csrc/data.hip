@@ -39,6 +39,37 @@
 //     the scene (reflect_index): (a, b) = (oy, ox); code & 4: swap a, b; code & 2: a = tile -
 //     1 - a; code & 1: b = tile - 1 - b.  Value: v = u8 / 255, with colour clamp(round(v *
 //     gain) + bias, 0, 1), every op rounded on its own, then bf16.
+//   * warp_params_kernel + warp_gather_kernel: the same crops under a random zoom and a
+//     rotation by an arbitrary angle — a resampling, where crop_gather is a permutation.
+//     Coordinates are 16.16 fixed point in int64 (ONE = 65536; >> is arithmetic = floor).  The
+//     zoom and the angle reach the kernels as two int32 tables the host builds in float64
+//     (data/scenes.py): steps[S] = rint(ONE / z_k), z_k = zoom_min (zoom_max / zoom_min)^((k +
+//     .5) / S) (log-uniform zoom; step = source pixels per output pixel) and rot[T] = (rint(cos
+//     t_k ONE), rint(sin t_k ONE)), t_k = -rotate_deg + (k + .5) 2 rotate_deg / T — integers
+//     only on the device, no pow / cos to match.  Twins: warp_params_reference /
+//     warp_gather_reference.
+//     warp_params: key, r_0..r_5, scene, code, gain, bias exactly as crop_params (the scene
+//     choice keeps the unit-scale cum table: with zoom an approximation of "uniform over all
+//     valid crops"), r_6, r_7 by the same rule, and
+//       step  = steps[(r6 * S) >> 32],  (c, sn) = rot[(r7 * T) >> 32]
+//       A     = (step * c + 32768) >> 16,  Bm = (step * sn + 32768) >> 16
+//       F     = (tile * step + 65535) >> 16                 (the un-rotated source footprint)
+//       ny    = max(H - F, 0) + 1,  y0 = (r1 * ny) >> 32,  cy = (2 y0 + F - 1) * 32768
+//     and cx likewise from r2 and W: the un-rotated footprint lies inside a scene that is
+//     large enough; whatever overhangs (small scenes, rotated corners) is mirrored.  Output:
+//     wparams int64 [B, 6] = (scene, cy, cx, code, A, Bm), color fp32 [B, 2].
+//     warp_gather: (a, b) from (oy, ox) and code as crop_gather;
+//       v2 = 2 a - (tile - 1),  u2 = 2 b - (tile - 1)
+//       py = cy + ((Bm * u2 + A * v2) >> 1),  px = cx + ((A * u2 - Bm * v2) >> 1)
+//       iy = py >> 16,  wy = float(py & 65535) * 2^-16       (ix, wx likewise from px)
+//     taps p00, p01, p10, p11 at rows reflect(iy), reflect(iy + 1), columns reflect(ix),
+//     reflect(ix + 1); per channel, the u8 taps as fp32, every op rounded on its own:
+//       top = p00 + (p01 - p00) * wx,  bot = p10 + (p11 - p10) * wx,  val = top + (bot - top) * wy
+//     v = val / 255 (IEEE), the colour clamp of crop_gather, bf16.  Label: nearest,
+//     lab[reflect((py + 32768) >> 16)][reflect((px + 32768) >> 16)].  A row whose scene is
+//     not listed, whose table row fails crop_gather's checks, with |A| or |Bm| > 2^20 or |cy|
+//     or |cx| >= 2^46 reads nothing (zero image, labels -100).  (A, Bm) = (ONE, 0) and cy = (2
+//     y0 + tile - 1) * 32768 is crop_gather's (y0, x0) crop, bit for bit.
 #include "common.h"
 #include "ops.h"
 
@@ -163,6 +194,34 @@ int data_grid(long long total) {
 }
 
 // ---- augmented random crops -------------------------------------------------------------
+// the draws of virtual sample s (the recipe in the header), shared by crop_params and warp_params
+DDLPC_DEVICE uint32_t sample_key(uint32_t seed, uint64_t s) {
+  const uint32_t skey = mix32(seed ^ 0xC2B2AE35u);
+  return mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
+}
+
+DDLPC_DEVICE uint32_t draw(uint32_t key, int j) { return mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u); }
+
+// the scene with cum[lo] <= (r0 * cum[n]) >> 32 < cum[lo + 1]
+DDLPC_DEVICE int pick_scene(const int64_t* __restrict__ cum, int n, uint32_t r0) {
+  const uint64_t t = ((uint64_t)r0 * (uint64_t)cum[n]) >> 32;
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint64_t)cum[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+DDLPC_DEVICE int symmetry_code(uint32_t r3, int mode) {
+  return mode == 0 ? 0 : (int)(r3 & (mode == 1 ? 3u : 7u));
+}
+
+DDLPC_DEVICE void color_jitter(uint32_t r4, uint32_t r5, float gj, float bj, float* __restrict__ color) {
+  color[0] = __fadd_rn(1.0f, mul_rn(gj, __fadd_rn(mul_rn(2.0f, u24(r4)), -1.0f)));
+  color[1] = mul_rn(bj, __fadd_rn(mul_rn(2.0f, u24(r5)), -1.0f));
+}
+
 // one thread per virtual sample number: see the recipe in the header
 __global__ __launch_bounds__(256) void crop_params_kernel(
     const int64_t* __restrict__ idx, int B, const int64_t* __restrict__ cum,
@@ -170,27 +229,48 @@ __global__ __launch_bounds__(256) void crop_params_kernel(
     int* __restrict__ params, float* __restrict__ color) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
-  const uint64_t s = (uint64_t)idx[i];
-  const uint32_t skey = mix32(seed ^ 0xC2B2AE35u);
-  const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
-  uint32_t r[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) r[j] = mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u);
-  const uint64_t t = ((uint64_t)r[0] * (uint64_t)cum[n]) >> 32;
-  int lo = 0, hi = n;                        // the scene with cum[lo] <= t < cum[lo + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((uint64_t)cum[mid] <= t) lo = mid; else hi = mid;
-  }
+  const uint32_t key = sample_key(seed, (uint64_t)idx[i]);
+  const int lo = pick_scene(cum, n, draw(key, 0));
   const long long H = table[3 * lo + 1], W = table[3 * lo + 2];
   const uint64_t ny = (uint64_t)(H > tile ? H - tile : 0) + 1u;
   const uint64_t nx = (uint64_t)(W > tile ? W - tile : 0) + 1u;
   params[4 * i] = lo;
-  params[4 * i + 1] = (int)(((uint64_t)r[1] * ny) >> 32);
-  params[4 * i + 2] = (int)(((uint64_t)r[2] * nx) >> 32);
-  params[4 * i + 3] = mode == 0 ? 0 : (int)(r[3] & (mode == 1 ? 3u : 7u));
-  color[2 * i] = __fadd_rn(1.0f, mul_rn(gj, __fadd_rn(mul_rn(2.0f, u24(r[4])), -1.0f)));
-  color[2 * i + 1] = mul_rn(bj, __fadd_rn(mul_rn(2.0f, u24(r[5])), -1.0f));
+  params[4 * i + 1] = (int)(((uint64_t)draw(key, 1) * ny) >> 32);
+  params[4 * i + 2] = (int)(((uint64_t)draw(key, 2) * nx) >> 32);
+  params[4 * i + 3] = symmetry_code(draw(key, 3), mode);
+  color_jitter(draw(key, 4), draw(key, 5), gj, bj, color + 2 * i);
+}
+
+// 16.16 centre of an F-pixel footprint whose origin is drawn from max(size - F, 0) + 1
+// positions.  Unsigned arithmetic: a wild table entry wraps (warp_gather then rejects the row)
+DDLPC_DEVICE long long footprint_centre(uint32_t r, long long size, long long F) {
+  const uint64_t cnt = (size > F ? (uint64_t)size - (uint64_t)F : 0u) + 1u;
+  const uint64_t o = ((uint64_t)r * cnt) >> 32;
+  return (long long)((2u * o + (uint64_t)F - 1u) * 32768u);
+}
+
+__global__ __launch_bounds__(256) void warp_params_kernel(
+    const int64_t* __restrict__ idx, int B, const int64_t* __restrict__ cum,
+    const int64_t* __restrict__ table, int n, const int* __restrict__ steps, int S,
+    const int* __restrict__ rot, int T, uint32_t seed, int tile, int mode, float gj, float bj,
+    int64_t* __restrict__ wparams, float* __restrict__ color) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const uint32_t key = sample_key(seed, (uint64_t)idx[i]);
+  const int lo = pick_scene(cum, n, draw(key, 0));
+  const long long H = table[3 * lo + 1], W = table[3 * lo + 2];
+  const long long step = steps[(int)(((uint64_t)draw(key, 6) * (uint64_t)S) >> 32)];
+  const int k = (int)(((uint64_t)draw(key, 7) * (uint64_t)T) >> 32);
+  const long long c = rot[2 * k], sn = rot[2 * k + 1];
+  const long long F = ((long long)tile * step + 65535) >> 16;
+  int64_t* w = wparams + 6 * (long long)i;
+  w[0] = lo;
+  w[1] = footprint_centre(draw(key, 1), H, F);
+  w[2] = footprint_centre(draw(key, 2), W, F);
+  w[3] = symmetry_code(draw(key, 3), mode);
+  w[4] = (step * c + 32768) >> 16;
+  w[5] = (step * sn + 32768) >> 16;
+  color_jitter(draw(key, 4), draw(key, 5), gj, bj, color + 2 * i);
 }
 
 // reflect_index without the division for a coordinate already inside the scene (all of them,
@@ -298,6 +378,89 @@ __global__ __launch_bounds__(256) void crop_gather_kernel(
   }
 }
 
+// warp_gather: crop_gather's work split (one workgroup per kCropBS^2 output block of one sample,
+// lanes along ox, one 16-byte store per pixel); the sample's code and matrix are uniform in a
+// workgroup.  A lane's source coordinate moves by (Bm, A) per ox (or (A, -Bm) for the
+// transposing codes): at zooms near 1 neighbouring lanes read neighbouring source pixels, so
+// the 4 taps and the label come straight from global memory (L2 serves the re-reads).
+__global__ __launch_bounds__(256) void warp_gather_kernel(
+    const uint8_t* __restrict__ src, const uint8_t* __restrict__ lab,
+    const int64_t* __restrict__ table, int n, long long total_px, const int64_t* __restrict__ wparams,
+    const float* __restrict__ color, int nb, int in_ch, int tile, int cpad,
+    bf16_t* __restrict__ x, int64_t* __restrict__ y) {
+  const int blk = blockIdx.x;
+  const int b = blk / (nb * nb);
+  const int rem = blk - b * nb * nb;
+  const int by = rem / nb, bx = rem - by * nb;
+  const int lx = threadIdx.x & (kCropBS - 1), ly0 = threadIdx.x / kCropBS;
+  constexpr int kRows = 256 / kCropBS;
+  const int64_t* wp = wparams + 6 * (long long)b;
+  const long long sc = wp[0], cy = wp[1], cx = wp[2], Al = wp[4], Bl = wp[5];
+  const int code = (int)wp[3] & 7;
+  const bool listed = sc >= 0 && sc < n;
+  const long long off = listed ? table[3 * sc] : 0;
+  const long long Hl = listed ? table[3 * sc + 1] : 1, Wl = listed ? table[3 * sc + 2] : 1;
+  constexpr long long kCoef = 1LL << 20, kCentre = 1LL << 46;
+  // crop_gather's checks, and a matrix / centre small enough that every coordinate below
+  // stays far inside int64 and its integer part inside int
+  const bool valid = listed && Hl >= 1 && Wl >= 1 && Hl < (1 << 30) && Wl < (1 << 30) && off >= 0 &&
+                     off <= total_px && Hl * Wl <= total_px - off && Al >= -kCoef && Al <= kCoef &&
+                     Bl >= -kCoef && Bl <= kCoef && cy > -kCentre && cy < kCentre && cx > -kCentre &&
+                     cx < kCentre;
+  const int H = valid ? (int)Hl : 1, W = valid ? (int)Wl : 1;
+  const int A = valid ? (int)Al : 0, Bm = valid ? (int)Bl : 0;     // 32 x 32 -> 64-bit products
+  const bool has_color = color != nullptr;
+  const float gain = has_color ? color[2 * b] : 1.f, bias = has_color ? color[2 * b + 1] : 0.f;
+  for (int ly = ly0; ly < kCropBS; ly += kRows) {
+    const int oy = by * kCropBS + ly, ox = bx * kCropBS + lx;
+    if (oy >= tile || ox >= tile) continue;
+    const long long e = ((long long)b * tile + oy) * tile + ox;
+    float f[8];
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) f[ch] = 0.f;
+    int64_t l = -100;
+    if (valid) {
+      int a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
+      if (code & 2) a = tile - 1 - a;
+      if (code & 1) c = tile - 1 - c;
+      const int v2 = 2 * a - (tile - 1), u2 = 2 * c - (tile - 1);
+      const long long py = cy + (((long long)Bm * u2 + (long long)A * v2) >> 1);
+      const long long px = cx + (((long long)A * u2 - (long long)Bm * v2) >> 1);
+      // |py|, |px| < 2^46 + 2^36: the integer part (+ 1) fits an int; H, W < 2^30
+      const int iy = (int)(py >> 16), ix = (int)(px >> 16);
+      const float wy = (float)(int)(py & 65535) * (1.0f / 65536.0f);       // exact
+      const float wx = (float)(int)(px & 65535) * (1.0f / 65536.0f);
+      const long long r0 = off + (long long)reflect_fast(iy, H) * W;
+      const long long r1 = off + (long long)reflect_fast(iy + 1, H) * W;
+      const int c0 = reflect_fast(ix, W), c1 = reflect_fast(ix + 1, W);
+      const uint8_t* q00 = src + (r0 + c0) * in_ch;
+      const uint8_t* q01 = src + (r0 + c1) * in_ch;
+      const uint8_t* q10 = src + (r1 + c0) * in_ch;
+      const uint8_t* q11 = src + (r1 + c1) * in_ch;
+#pragma unroll
+      for (int ch = 0; ch < 8; ++ch)
+        if (ch < in_ch) {
+          const float p00 = (float)q00[ch], p01 = (float)q01[ch], p10 = (float)q10[ch], p11 = (float)q11[ch];
+          const float top = __fadd_rn(p00, mul_rn(__fsub_rn(p01, p00), wx));
+          const float bot = __fadd_rn(p10, mul_rn(__fsub_rn(p11, p10), wx));
+          float v = __fdiv_rn(__fadd_rn(top, mul_rn(__fsub_rn(bot, top), wy)), 255.0f);
+          if (has_color) v = fminf(fmaxf(__fadd_rn(mul_rn(v, gain), bias), 0.f), 1.f);
+          f[ch] = v;
+        }
+      const int ny = reflect_fast((int)((py + 32768) >> 16), H), nx = reflect_fast((int)((px + 32768) >> 16), W);
+      l = (int64_t)lab[off + (long long)ny * W + nx];
+    }
+    y[e] = l;
+    if (cpad == 8) {
+      reinterpret_cast<uint4*>(x)[e] = pack8(f);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 8; ++ch)
+        if (ch < cpad) x[e * cpad + ch] = f2bf(f[ch]);
+    }
+  }
+}
+
 }  // namespace
 
 void crop_params_launch(const int64_t* idx, int B, const int64_t* cum, const int64_t* table, int n,
@@ -308,6 +471,22 @@ void crop_params_launch(const int64_t* idx, int B, const int64_t* cum, const int
 }
 
 int crop_gather_blocks(int tile) { return (tile + kCropBS - 1) / kCropBS; }
+
+void warp_params_launch(const int64_t* idx, int B, const int64_t* cum, const int64_t* table, int n,
+                        const int* steps, int S, const int* rot, int T, uint32_t seed, int tile,
+                        int mode, float gain_jitter, float bias_jitter, int64_t* wparams, float* color,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(warp_params_kernel, dim3((B + 255) / 256), dim3(256), 0, st, idx, B, cum, table,
+                     n, steps, S, rot, T, seed, tile, mode, gain_jitter, bias_jitter, wparams, color);
+}
+
+void warp_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
+                        long long total_px, const int64_t* wparams, const float* color, int B,
+                        int in_ch, int tile, int cpad, bf16_t* x, int64_t* y, hipStream_t st) {
+  const int nb = crop_gather_blocks(tile);
+  hipLaunchKernelGGL(warp_gather_kernel, dim3((unsigned)((long long)B * nb * nb)), dim3(256), 0, st, src,
+                     lab, table, n, total_px, wparams, color, nb, in_ch, tile, cpad, x, y);
+}
 
 void crop_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
                         long long total_px, const int* params, const float* color, int B, int in_ch,

@@ -381,6 +381,14 @@ int crop_gather_blocks(int tile);   // workgroups per output row / column of one
 void crop_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
                         long long total_px, const int* params, const float* color, int B, int in_ch,
                         int tile, int cpad, bool lds_transpose, bf16_t* x, int64_t* y, hipStream_t st);
+// zoomed / rotated crops: steps int32 [S], rot int32 [T, 2], wparams int64 [B, 6]
+void warp_params_launch(const int64_t* idx, int B, const int64_t* cum, const int64_t* table, int n,
+                        const int* steps, int S, const int* rot, int T, uint32_t seed, int tile,
+                        int mode, float gain_jitter, float bias_jitter, int64_t* wparams, float* color,
+                        hipStream_t st);
+void warp_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
+                        long long total_px, const int64_t* wparams, const float* color, int B,
+                        int in_ch, int tile, int cpad, bf16_t* x, int64_t* y, hipStream_t st);
 
 void bn_running_apply_launch(float* rm, float* rv, const float* slots, int K, int C, long long stride,
                              float momentum, int64_t* nbt, hipStream_t st);

@@ -19,7 +19,8 @@ flags override).  ``train`` prints the final reduced metrics as one JSON line on
 counterpart of ``train --augment d4``.)
 
 ``train --data scene_dir --data-dir scenes/ --augment d4`` trains on uncut scenes of unequal size
-(augmented random crops cut on the device, ``data/scenes.py``);
+(augmented random crops cut on the device, ``data/scenes.py``), and with ``--zoom-min 0.5
+--zoom-max 2 --rotate-deg 30`` the crops are zoomed and rotated at random on the way;
 ``--class-weights 1,1,1,1,4,4`` (one number per class) or ``--class-weights median_freq`` (from
 the training split's labels) trains with ``CrossEntropyLoss(weight=...)``, fused into the head
 kernels — the validation loss stays unweighted, the per-class IoU shows the effect;

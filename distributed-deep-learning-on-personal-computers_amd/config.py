@@ -105,11 +105,17 @@ class TrainConfig:
     data_on_device: bool = True          # GPU: render / keep the dataset in HBM (K20)
     data_hbm_gb: Optional[float] = None  # HBM budget for a real dataset (None: half the free)
     # augmented random crops, cut on the device (data/scenes.py; 2-D): always for scene_dir,
-    # for vaihingen_dir when augment or a jitter is set (each tile = a tile-sized scene)
+    # for vaihingen_dir when augment, a jitter, a zoom or a rotation is set (each tile = a
+    # tile-sized scene)
     crops_per_epoch: int = 0             # 0 = total scene area / tile^2, rounded up
     augment: str = "none"                # none | flip (the 4 mirrorings) | d4 (+ transposes)
     gain_jitter: float = 0.0             # per-sample gain 1 +- this (uniform) and bias +- this,
     bias_jitter: float = 0.0             # x = clamp(x * gain + bias, 0, 1)
+    # random zoom and rotation of the crops (the warp kernels: bilinear image taps, nearest
+    # labels, mirrored overhang); zoom 1 and rotation 0 keep the crop kernels
+    zoom_min: float = 1.0                # per-sample zoom, log-uniform in [zoom_min, zoom_max]:
+    zoom_max: float = 1.0                # > 1 magnifies; 0.25 <= zoom_min <= zoom_max <= 4
+    rotate_deg: float = 0.0              # per-sample angle, uniform in +- this many degrees (<= 180)
     # CrossEntropyLoss(weight=...) of the training loss (validation stays unweighted):
     # None | "w0,w1,..." (out_classes non-negative numbers, not all zero; a YAML list too)
     # | "median_freq" (from the training split's label histogram; real data only)
@@ -209,6 +215,10 @@ class TrainConfig:
         for name in ("gain_jitter", "bias_jitter"):
             if not 0.0 <= getattr(self, name) <= 1.0:
                 raise ValueError(f"{name} must be in [0, 1]")
+        if not 0.25 <= self.zoom_min <= self.zoom_max <= 4.0:
+            raise ValueError("zoom_min and zoom_max must satisfy 0.25 <= zoom_min <= zoom_max <= 4")
+        if not 0.0 <= self.rotate_deg <= 180.0:
+            raise ValueError("rotate_deg must be in [0, 180]")
         if isinstance(self.class_weights, (list, tuple)):      # a YAML / JSON list
             self.class_weights = ",".join(repr(float(v)) for v in self.class_weights)
         cw = parse_class_weights(self.class_weights, self.model.out_classes)
@@ -218,17 +228,19 @@ class TrainConfig:
             raise ValueError("class_weights=median_freq needs data=scene_dir or vaihingen_dir (the "
                              "histogram of the training split's label files)")
         if self.data == "synthetic" and (self.crops_per_epoch or self.augmented):
-            raise ValueError("crops_per_epoch, augment and the colour jitters need data=scene_dir or "
-                             "vaihingen_dir (the synthetic tiles are rendered, not cropped)")
+            raise ValueError("crops_per_epoch, augment, the colour jitters, zoom and rotation need "
+                             "data=scene_dir or vaihingen_dir (the synthetic tiles are rendered, not "
+                             "cropped)")
         if self.model.dims == 3 and (self.data == "scene_dir" or self.crops_per_epoch or self.augmented):
-            raise ValueError("scene_dir, crops_per_epoch, augment and the colour jitters are 2-D only "
-                             "(model.dims == 2)")
+            raise ValueError("scene_dir, crops_per_epoch, augment, the colour jitters, zoom and rotation "
+                             "are 2-D only (model.dims == 2)")
         return self
 
     @property
     def augmented(self) -> bool:
-        """Batches go through the augmenting crop kernels."""
-        return self.augment != "none" or self.gain_jitter != 0.0 or self.bias_jitter != 0.0
+        """Batches go through the augmenting crop (or warp) kernels."""
+        return self.augment != "none" or self.gain_jitter != 0.0 or self.bias_jitter != 0.0 or \
+            self.zoom_min != 1.0 or self.zoom_max != 1.0 or self.rotate_deg != 0.0
 
     # ---- (de)serialisation ---------------------------------------------------------
     def to_dict(self) -> Dict[str, Any]:

@@ -20,8 +20,15 @@ differing sizes; here they are trained on as they are:
 * a directory of pre-cut tiles is the same packing with one scene per tile
   (``SceneCropDataset.from_tiles``): a tile-sized scene always gets origin (0, 0).
 
-``crop_params_reference`` / ``crop_gather_reference`` are the numpy twins of the two kernels
-(the same bits); they serve ``layout="nchw"`` and are the oracle of the tests.
+* random zoom and rotation (``zoom_min`` / ``zoom_max`` / ``rotate_deg``): the crop is a
+  resampled window — ``warp_params`` draws a zoom step and an angle from two integer tables
+  built here (``zoom_steps``, ``rotation_table``) and ``warp_gather`` reads bilinear image
+  taps and nearest labels at 16.16 fixed-point affine coordinates, in the same single pass.
+  With zoom 1 and rotation 0 (the defaults) the crop kernels run, unchanged.
+
+``crop_params_reference`` / ``crop_gather_reference`` and ``warp_params_reference`` /
+``warp_gather_reference`` are the numpy twins of the kernels (the same bits); they serve
+``layout="nchw"`` and are the oracle of the tests.
 """
 from __future__ import annotations
 
@@ -36,6 +43,10 @@ from .datasets import TileDataset, _read_image, device_indices, engine_input
 AUGMENT_MODES = ("none", "flip", "d4")
 _M32 = np.uint64(0xFFFFFFFF)
 _F = np.float32
+ONE = 65536                              # 1.0 in the warp kernels' 16.16 fixed point
+WARP_TABLE = 256                         # entries of the zoom and of the rotation table
+WARP_MAX_COEF = 2 ** 20                  # warp_gather: |A|, |Bm| <= this (a step of 16 pixels)
+WARP_MAX_CENTRE = 2 ** 46                # ... and |cy|, |cx| < this
 
 
 # ---------------------------------------------------------------------- the numpy twins
@@ -136,6 +147,112 @@ def crop_gather_reference(scenes, labels, table, params, color, tile: int
     return torch.from_numpy(x).permute(0, 3, 1, 2).contiguous(), torch.from_numpy(y)
 
 
+# ---------------------------------------------------------------------- warped crops
+# Random zoom and rotation (the recipe: csrc/data.hip).  Coordinates are 16.16 fixed point in
+# int64; the zoom and the angle reach the kernels only as integer tables built here, in
+# float64, once per data set — there is no device pow / cos to match.
+def zoom_steps(zoom_min: float, zoom_max: float, S: int = WARP_TABLE) -> np.ndarray:
+    """int32 [S]: source pixels per output pixel in 16.16, ``rint(ONE / z_k)`` for the
+    log-uniform zooms ``z_k = zoom_min * (zoom_max / zoom_min) ** ((k + 0.5) / S)``."""
+    if not (0.0 < zoom_min <= zoom_max) or S < 1:
+        raise ValueError("zoom_steps needs 0 < zoom_min <= zoom_max and S >= 1")
+    k = (np.arange(S, dtype=np.float64) + 0.5) / S
+    z = np.float64(zoom_min) * np.power(np.float64(zoom_max) / np.float64(zoom_min), k)
+    return np.rint(ONE / z).astype(np.int32)
+
+
+def rotation_table(rotate_deg: float, T: int = WARP_TABLE) -> np.ndarray:
+    """int32 [T, 2]: ``(rint(cos t_k * ONE), rint(sin t_k * ONE))`` for the angles
+    ``t_k = -rotate_deg + (k + 0.5) * 2 rotate_deg / T``; all ``(ONE, 0)`` for 0 degrees."""
+    if rotate_deg < 0.0 or T < 1:
+        raise ValueError("rotation_table needs rotate_deg >= 0 and T >= 1")
+    t = np.deg2rad(-np.float64(rotate_deg) + (np.arange(T, dtype=np.float64) + 0.5) * 2.0 * rotate_deg / T)
+    return np.stack([np.rint(np.cos(t) * ONE), np.rint(np.sin(t) * ONE)], 1).astype(np.int32)
+
+
+def _footprint_centre(r: np.ndarray, size: np.ndarray, F: np.ndarray) -> np.ndarray:
+    """Centre (16.16) of an F-pixel footprint whose origin is drawn from ``max(size - F, 0) +
+    1`` positions: ``(2 origin + F - 1) * 32768``."""
+    n = (np.maximum(size - F, 0) + 1).astype(np.uint64)
+    o = ((r * n) >> np.uint64(32)).astype(np.int64)
+    return (2 * o + F - 1) * 32768
+
+
+def warp_params_reference(idx, cum, table, steps, rot, seed: int, tile: int, mode: int,
+                          gain_jitter: float = 0.0, bias_jitter: float = 0.0
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """numpy twin of the ``warp_params`` kernels: wparams int64 [B, 6] of ``(scene, cy, cx,
+    code, A, Bm)`` rows, color fp32 [B, 2].  Scene, code and colour are ``crop_params``'s."""
+    p, color = crop_params_reference(idx, cum, table, seed, tile, mode, gain_jitter, bias_jitter)
+    s = np.asarray(torch.as_tensor(idx, dtype=torch.int64).reshape(-1).cpu().numpy()).astype(np.uint64)
+    table = np.asarray(torch.as_tensor(table).cpu().numpy(), dtype=np.int64).reshape(-1, 3)
+    steps = np.asarray(torch.as_tensor(steps).cpu().numpy(), dtype=np.int64).reshape(-1)
+    rot = np.asarray(torch.as_tensor(rot).cpu().numpy(), dtype=np.int64).reshape(-1, 2)
+    skey = _mix32(np.array([(seed & 0xFFFFFFFF) ^ 0xC2B2AE35], dtype=np.uint64))
+    hi = _mix32(((s >> np.uint64(32)) + np.uint64(0x85EBCA6B)) & _M32)
+    key = _mix32(_mix32(skey ^ (s & _M32)) ^ hi)
+    r = {j: _mix32((key + np.uint64(((j + 1) * 0x9E3779B9) & 0xFFFFFFFF)) & _M32) for j in (1, 2, 6, 7)}
+    sc = p[:, 0].numpy().astype(np.int64)
+    code = p[:, 3].numpy().astype(np.int64)
+    step = steps[((r[6] * np.uint64(len(steps))) >> np.uint64(32)).astype(np.int64)]
+    cs = rot[((r[7] * np.uint64(len(rot))) >> np.uint64(32)).astype(np.int64)]
+    A = (step * cs[:, 0] + 32768) >> 16
+    Bm = (step * cs[:, 1] + 32768) >> 16
+    F = (tile * step + 65535) >> 16
+    cy = _footprint_centre(r[1], table[sc, 1], F)
+    cx = _footprint_centre(r[2], table[sc, 2], F)
+    return torch.from_numpy(np.stack([sc, cy, cx, code, A, Bm], 1).astype(np.int64)), color
+
+
+def warp_gather_reference(scenes, labels, table, wparams, color, tile: int
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """numpy twin of the ``warp_gather`` kernels: float32 NCHW (before the bf16 rounding) and
+    int64 labels.  Bilinear image taps and nearest labels at the affine coordinates of
+    csrc/data.hip; every float32 operation rounds on its own."""
+    scenes = torch.as_tensor(scenes).cpu().numpy()
+    labels = torch.as_tensor(labels).cpu().numpy()
+    table = torch.as_tensor(table).cpu().numpy().reshape(-1, 3)
+    wp = torch.as_tensor(wparams).cpu().numpy().astype(np.int64)
+    col = None if color is None else torch.as_tensor(color).cpu().numpy().astype(_F)
+    B, C, n, P = wp.shape[0], scenes.shape[1], table.shape[0], labels.shape[0]
+    x = np.zeros((B, tile, tile, C), dtype=_F)
+    y = np.full((B, tile, tile), -100, dtype=np.int64)
+    oy, ox = np.meshgrid(np.arange(tile, dtype=np.int64), np.arange(tile, dtype=np.int64), indexing="ij")
+    for b in range(B):
+        s, cy, cx, code, A, Bm = (int(v) for v in wp[b])
+        code &= 7
+        if not 0 <= s < n or max(abs(A), abs(Bm)) > WARP_MAX_COEF or max(abs(cy), abs(cx)) >= WARP_MAX_CENTRE:
+            continue                                  # reads nothing: zero image, ignored labels
+        off, H, W = (int(v) for v in table[s])
+        if not (1 <= H < 2 ** 30 and 1 <= W < 2 ** 30 and 0 <= off <= P and H * W <= P - off):
+            continue
+        a, c = (ox, oy) if code & 4 else (oy, ox)
+        if code & 2:
+            a = tile - 1 - a
+        if code & 1:
+            c = tile - 1 - c
+        v2, u2 = 2 * a - (tile - 1), 2 * c - (tile - 1)
+        py = cy + ((Bm * u2 + A * v2) >> 1)
+        px = cx + ((A * u2 - Bm * v2) >> 1)
+        iy, ix = py >> 16, px >> 16
+        wy = (py & 65535).astype(_F) * _F(2.0 ** -16)
+        wx = (px & 65535).astype(_F) * _F(2.0 ** -16)
+        img = scenes[off:off + H * W].reshape(H, W, C)
+        r0, r1 = _reflect(iy, H), _reflect(iy + 1, H)
+        c0, c1 = _reflect(ix, W), _reflect(ix + 1, W)
+        p00, p01 = img[r0, c0].astype(_F), img[r0, c1].astype(_F)
+        p10, p11 = img[r1, c0].astype(_F), img[r1, c1].astype(_F)
+        top = p00 + (p01 - p00) * wx[..., None]
+        bot = p10 + (p11 - p10) * wx[..., None]
+        v = (top + (bot - top) * wy[..., None]) / _F(255.0)
+        if col is not None:
+            v = np.clip(v * col[b, 0] + col[b, 1], _F(0.0), _F(1.0))
+        x[b] = v
+        y[b] = labels[off:off + H * W].reshape(H, W)[_reflect((py + 32768) >> 16, H),
+                                                     _reflect((px + 32768) >> 16, W)]
+    return torch.from_numpy(x).permute(0, 3, 1, 2).contiguous(), torch.from_numpy(y)
+
+
 # ---------------------------------------------------------------------- directory loader
 Scene = Tuple[np.ndarray, np.ndarray]
 
@@ -197,7 +314,8 @@ class SceneCropDataset:
 
     def __init__(self, scenes: Sequence[Scene], tile: int, crops_per_epoch: int = 0,
                  augment: str = "none", gain_jitter: float = 0.0, bias_jitter: float = 0.0,
-                 seed: int = 0, layout: str = "nchw", params=None):
+                 seed: int = 0, layout: str = "nchw", params=None, zoom_min: float = 1.0,
+                 zoom_max: float = 1.0, rotate_deg: float = 0.0):
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment={augment!r} not in {AUGMENT_MODES}")
         if layout not in ("nchw", "engine"):
@@ -207,6 +325,7 @@ class SceneCropDataset:
         self.tile, self.seed, self.layout = int(tile), int(seed), layout
         self.mode = AUGMENT_MODES.index(augment)
         self.gain_jitter, self.bias_jitter = float(gain_jitter), float(bias_jitter)
+        self.zoom_min, self.zoom_max, self.rotate_deg = float(zoom_min), float(zoom_max), float(rotate_deg)
         rows, off = [], 0
         for x, y in scenes:
             if x.dtype != np.uint8 or x.ndim != 3 or tuple(y.shape) != tuple(x.shape[:2]):
@@ -224,6 +343,11 @@ class SceneCropDataset:
         self.cum = torch.from_numpy(crop_cum(self.table.numpy(), self.tile))
         self.params = None if params is None else \
             torch.as_tensor(params, dtype=torch.int32).reshape(-1, 4).contiguous()
+        # random zoom / rotation: the integer tables of warp_params (None = the crop kernels)
+        self.steps = self.rot = None
+        if self.warped:
+            self.steps = torch.from_numpy(zoom_steps(self.zoom_min, self.zoom_max))
+            self.rot = torch.from_numpy(rotation_table(self.rotate_deg))
         t2 = self.tile * self.tile
         self.length = len(self.params) if self.params is not None else \
             int(crops_per_epoch) if crops_per_epoch > 0 else -(-off // t2)
@@ -272,7 +396,7 @@ class SceneCropDataset:
                 raise MemoryError(f"scene set of {nbytes} bytes exceeds the HBM budget of "
                                   f"{budget_bytes} bytes; scene sets are served from HBM only "
                                   f"(raise data_hbm_gb or train on fewer scenes)")
-        for name in ("pixels", "labels", "table", "cum", "params"):
+        for name in ("pixels", "labels", "table", "cum", "params", "steps", "rot"):
             t = getattr(self, name)
             if t is not None:
                 setattr(self, name, t.to(device))
@@ -286,6 +410,13 @@ class SceneCropDataset:
     @property
     def resident(self) -> bool:
         return True
+
+    @property
+    def warped(self) -> bool:
+        """Random crops are zoomed / rotated: batches go through ``warp_params`` / ``warp_gather``
+        (an explicit ``params`` list, the evaluation grid, stays un-warped)."""
+        return self.params is None and (self.zoom_min != 1.0 or self.zoom_max != 1.0 or
+                                        self.rotate_deg != 0.0)
 
     def __len__(self):
         return self.length
@@ -307,7 +438,13 @@ class SceneCropDataset:
         if self.params is not None:
             return self.params.index_select(0, device_indices(idx, self.device)), None
         s = self.sample_numbers(idx)
-        if self.layout == "engine":
+        jitter = (self.seed, self.tile, self.mode, self.gain_jitter, self.bias_jitter)
+        if self.warped and self.layout == "engine":
+            from ..ops import _ext
+            p, c = _ext.ops().warp_params(s, self.cum, self.table, self.steps, self.rot, *jitter)
+        elif self.warped:
+            p, c = warp_params_reference(s, self.cum, self.table, self.steps, self.rot, *jitter)
+        elif self.layout == "engine":
             from ..ops import _ext
             p, c = _ext.ops().crop_params(s, self.cum, self.table, self.seed, self.tile, self.mode,
                                           self.gain_jitter, self.bias_jitter)
@@ -320,6 +457,9 @@ class SceneCropDataset:
         p, c = self.crop_rows(idx)
         if self.layout == "engine":
             from ..ops import _ext
-            xp, y = _ext.ops().crop_gather(self.pixels, self.labels, self.table, p, c, self.tile, 8)
+            gather = _ext.ops().warp_gather if self.warped else _ext.ops().crop_gather
+            xp, y = gather(self.pixels, self.labels, self.table, p, c, self.tile, 8)
             return engine_input(xp, self.in_channels), y
+        if self.warped:
+            return warp_gather_reference(self.pixels, self.labels, self.table, p, c, self.tile)
         return crop_gather_reference(self.pixels, self.labels, self.table, p, c, self.tile)

@@ -286,10 +286,12 @@ class Trainer:
             raise ValueError(f"data={c.data} needs data_dir")
         budget = None if c.data_hbm_gb is None else int(c.data_hbm_gb * 2**30)
         if c.data == "scene_dir" or (c.data == "vaihingen_dir" and c.augmented):
-            # random augmented crops cut by the crop_params / crop_gather kernels; the held-out
-            # scenes (tiles) are served un-augmented through the same gather
+            # random augmented crops cut by the crop_params / crop_gather kernels (warp_params /
+            # warp_gather under a zoom or a rotation); the held-out scenes (tiles) are served
+            # un-augmented through crop_gather
             crop = dict(crops_per_epoch=c.crops_per_epoch, augment=c.augment, seed=c.seed,
-                        gain_jitter=c.gain_jitter, bias_jitter=c.bias_jitter, layout=layout)
+                        gain_jitter=c.gain_jitter, bias_jitter=c.bias_jitter, layout=layout,
+                        zoom_min=c.zoom_min, zoom_max=c.zoom_max, rotate_deg=c.rotate_deg)
             if c.data == "scene_dir":
                 tr, te = SceneCropDataset.from_dir(c.data_dir, c.tile, c.test_holdout, **crop)
             else:

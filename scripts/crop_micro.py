@@ -6,8 +6,15 @@ same bytes of output), interleaved in one process (docs/PERF.md convention).
 Every code is timed on both paths of the transposing codes: ``lds`` (knob CROP_LDS_T = 1, the
 shipped kernel: bit-4 codes staged through LDS) and ``direct`` (CROP_LDS_T = 0: every code
 reads its source pixel straight from HBM; for codes 0..3 the two are the same code path, so
-their difference is the run-to-run spread).  Prints one JSON line per entry and a markdown
-table."""
+their difference is the run-to-run spread).
+
+``warp_gather`` (random zoom and rotation: 4 bilinear taps and a nearest label per pixel) is
+timed at the same batch in the same rounds: ``warp_unit`` with the identity matrix on the rows
+``crop_params`` drew (it must write ``crop_gather``'s bits: the cost of the resampling
+arithmetic alone), ``warp_z0.5-2_r30`` on rows ``warp_params`` draws from the tables of
+``--zoom-min 0.5 --zoom-max 2 --rotate-deg 30``, and ``warp_z0.5_r45`` with every row at zoom
+0.5 and 45 degrees (the widest source footprint of that range).  Prints one JSON line per
+entry, a markdown table, and the ``warp_gather / crop_gather`` ratios against ``coded4_lds``."""
 import argparse
 import json
 import os
@@ -41,7 +48,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("crop_micro.py measures on the GPU; none found")
-    from ddlpc.data.scenes import crop_cum
+    from ddlpc.data.scenes import ONE, crop_cum, rotation_table, zoom_steps
     from ddlpc.ops import _ext
     F = _ext.ops()
     dev = "cuda"
@@ -69,6 +76,20 @@ def main():
             p[:, 3] = code
         for path, knob in (("lds", 1), ("direct", 0)):
             entries[f"code{code}_{path}"] = (knob, lambda p=p: F.crop_gather(pixels, labels, table, p, color, T, 8))
+    # warp_gather: the identity on crop_params' rows, rows drawn from the zoom / rotation
+    # tables, and the widest footprint (zoom 0.5 at 45 degrees) for every row
+    pl = params.long()
+    unit = torch.stack([pl[:, 0], (2 * pl[:, 1] + T - 1) * 32768, (2 * pl[:, 2] + T - 1) * 32768, pl[:, 3],
+                        torch.full_like(pl[:, 0], ONE), torch.zeros_like(pl[:, 0])], 1).contiguous()
+    steps = torch.from_numpy(zoom_steps(0.5, 2.0)).to(dev)
+    rot = torch.from_numpy(rotation_table(30.0)).to(dev)
+    drawn, _ = F.warp_params(idx, cum, table, steps, rot, 0, T, 2, a.jitter, a.jitter)
+    wide, _ = F.warp_params(idx, cum, table, torch.full_like(steps, 2 * ONE),
+                            torch.from_numpy(rotation_table(0.0)).to(dev), 0, T, 2, a.jitter, a.jitter)
+    wide[:, 4] = wide[:, 5] = int(round(2 * ONE * 0.5 ** 0.5))
+    warps = {"warp_unit": unit, "warp_z0.5-2_r30": drawn, "warp_z0.5_r45": wide}
+    for name, w in warps.items():
+        entries[name] = (None, lambda w=w: F.warp_gather(pixels, labels, table, w, color, T, 8))
     times = {k: [] for k in entries}
 
     def run(name, iters):
@@ -87,6 +108,10 @@ def main():
             outs.append(fn())
         if not (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])):
             raise SystemExit(f"code {code}: the lds and the direct path differ")
+    F.set_knob("CROP_LDS_T", 1)
+    outs = [entries["coded4_lds"][1](), entries["warp_unit"][1]()]
+    if not (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])):
+        raise SystemExit("warp_gather with the identity matrix differs from crop_gather")
     del outs
     for _ in range(a.rounds):
         for name in entries:
@@ -105,6 +130,10 @@ def main():
     for name, ts in times.items():
         print(f"| {name} | {res[name]:.1f} | {min(ts):.1f} .. {max(ts):.1f} | "
               f"{res[name] / res['tile_gather']:.2f} |")
+    print()
+    for name in warps:
+        print(json.dumps({"ratio": f"{name} / coded4_lds", "value": round(res[name] / res["coded4_lds"], 3)}),
+              flush=True)
 
 
 if __name__ == "__main__":
