@@ -99,8 +99,11 @@ std::string last_path() { return g_last_path; }
 //   strided read, kept for scripts/crop_micro.py's A/B (docs/PERF.md)
 //   WINDOW_LDS_T (default 1): the same choice for window_gather's transposing codes
 //   (scripts/predict_micro.py --tta, docs/PERF.md)
+//   CONVT_WGRAD_WIDE (default: unset = convt_wgrad_wide_rule): the transposed-conv weight
+//   gradient's 256-column-tile kernel; 0 = never, 1 = wherever its shape constraints hold
+//   (scripts/conv_micro.py --passes twgradbn --ab, tests/test_convt_wgrad_wide_gpu.py)
 namespace {
-const char* const kKnobs[] = {"CROP_LDS_T", "WINDOW_LDS_T"};
+const char* const kKnobs[] = {"CROP_LDS_T", "WINDOW_LDS_T", "CONVT_WGRAD_WIDE"};
 bool knob_registered(const std::string& name) {
   for (const char* k : kKnobs)
     if (k[0] != 0 && name == k) return true;
@@ -1067,6 +1070,20 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
                                     const c10::optional<at::Tensor>& colsum_rows,
                                     const c10::optional<at::Tensor>& bn4);
 
+// Shapes whose weight gradient takes the 256-column-tile kernel when CONVT_WGRAD_WIDE is
+// unset: the two (M, N) families measured (256 and 128 channels, channels preserved), from the
+// smallest pixel count at which its median beat the 128-column kernel's whole min..max
+// (scripts/conv_micro.py --ab at batch 32 / 128 / 384, docs/PERF.md "Transposed-conv weight
+// gradient: 256-column tiles").  With the deferred BN of x the gain is larger (the wide kernel
+// keeps a lane's scales and shifts in registers) and starts earlier; 128 channels without it
+// tie at every size.  Other shapes keep the 128-column kernel until they are measured.
+static bool convt_wgrad_wide_rule(const GemmArgs& a) {
+  const bool bn = a.bn4 != nullptr;
+  if (a.M == 256 && a.N == 1024) return a.K >= (bn ? 16384 : 65536);
+  if (a.M == 128 && a.N == 512) return bn && a.K >= 131072;
+  return false;
+}
+
 bool convt_bwd_fused_ok(const at::Tensor& x, const at::Tensor& dout) {
   if (x.dim() != 4 || dout.dim() != 4 || x.size(3) != 64 || dout.size(3) != 64) return false;
   if (dout.size(1) != 2 * x.size(1) || dout.size(2) != 2 * x.size(2)) return false;
@@ -1153,14 +1170,26 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
   int splits;
   a.wg2 = g.C % 8 == 0 && go.C % 8 == 0 && g.C <= 512;
   if (a.wg2) {
-    const int tiles = convt_wgrad2_tiles(a);
-    splits = std::max(1, (2 * num_cus() + tiles - 1) / tiles);
-    splits = std::min(splits, std::max(1, a.K / 256));
-    // the kernel addresses a split's dOut rows through one buffer descriptor (32-bit
-    // offsets): bound the rows a split can span (up to 2 extra input rows / planes)
-    const long long per = ((long long)a.K + splits - 1) / splits + 64;
-    const long long span = g.dims == 2 ? 4 * per + 8LL * g.W : 8 * per + 16LL * g.H * g.W;
-    if (span * go.C * 2 >= (1LL << 31)) a.wg2 = 0;
+    // the 256-column-tile kernel (one 8-wave workgroup per CU): CONVT_WGRAD_WIDE unset = by
+    // convt_wgrad_wide_rule, 0 = never, 1 = wherever its shape constraints hold
+    const int kw = knob("CONVT_WGRAD_WIDE", -1);
+    // splits of the variant a.wg2 names; false = a split's rows exceed a buffer descriptor.
+    // The kernels address a split's x and dOut rows through one descriptor each (32-bit
+    // offsets): bound the rows a split can span (dOut: up to 2 extra input rows / planes)
+    auto plan = [&]() {
+      const int tiles = convt_wgrad2_tiles(a);
+      splits = a.wg2 == 2 ? std::max(1, num_cus() / tiles)
+                          : std::max(1, (2 * num_cus() + tiles - 1) / tiles);
+      splits = std::min(splits, std::max(1, a.K / 256));
+      const long long per = ((long long)a.K + splits - 1) / splits + 64;
+      const long long span = g.dims == 2 ? 4 * per + 8LL * g.W : 8 * per + 16LL * g.H * g.W;
+      return span * go.C * 2 < (1LL << 31) && (a.wg2 != 2 || per * g.C * 2 < (1LL << 31));
+    };
+    if (kw != 0 && convt_wgrad2w_ok(a) && (kw == 1 || convt_wgrad_wide_rule(a))) {
+      a.wg2 = 2;
+      if (!plan()) a.wg2 = 1;
+    }
+    if (a.wg2 == 1 && !plan()) a.wg2 = 0;
   }
   if (!a.wg2) {
     const int base = ((a.M + 63) / 64) * ((a.N + 63) / 64);
@@ -1171,7 +1200,7 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
   auto fopts = x.options().dtype(at::kFloat);
   at::Tensor part = at::empty({(int64_t)splits * a.M * a.N}, fopts);
   a.partial = part.data_ptr<float>();
-  set_last_path(a.wg2 ? "convt_wgrad:wg2" : "convt_wgrad:wg1");
+  set_last_path(a.wg2 == 2 ? "convt_wgrad:wg2w" : a.wg2 ? "convt_wgrad:wg2" : "convt_wgrad:wg1");
   gemm_launch(a, cur_stream());
   std::vector<int64_t> ws = {g.C, go.C, 2, 2};
   if (g.dims == 3) ws.push_back(2);

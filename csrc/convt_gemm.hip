@@ -817,6 +817,10 @@ struct Tn2Cfg {
   // pass at batch 128 — memory bound): 32-pixel stages in a 3-deep ring, the DMA of stage
   // s + 2 in flight while s computes.  Wider layers (compute heavier): 64-pixel stages,
   // double-buffered.  (measured per shape, profiles/convt_wgrad_micro_*_s2.txt)
+  // The chip-filling 128- / 256-channel levels take gemm_tn_wgrad2w_kernel (Tn2wCfg, below)
+  // instead: this kernel's BM = 128 form pulls x into LDS once per 128 of the N columns and,
+  // as compiled, drains its LDS-DMA (a compiler-placed vmcnt(0)) in front of every stage's
+  // first LDS access, so one stage per workgroup is in flight (docs/PERF.md).
   static constexpr int KT = BM == 64 ? 32 : 64;
   static constexpr int NBUF = BM == 64 ? 3 : 2;
   static constexpr int A_RB = BM * 2, B_RB = BN * 2;  // LDS row bytes
@@ -1026,6 +1030,243 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_wgrad2_kernel(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = m0 + wm * 64 + mt * 16 + 4 * (lane >> 4) + i;
+        if (m < p.M && n < p.N) out[(long long)m * p.N + n] = acc[mt][nt][i];
+      }
+    }
+}
+
+// ---------------------------------------------------------------- TN v2 wide (weight gradient)
+// gemm_tn_wgrad2_kernel's product on a 256-column tile: ONE 8-wave workgroup per CU (2 waves
+// along m x 4 along n) owning BM x 256 of dW — 256 x 256 (waves of 128 x 64, 128 accumulator
+// registers per lane) from 256 input channels up, 128 x 256 (waves of 64 x 64) below.  With
+// N = 1024 / M = 256 a pixel range's x is pulled into LDS 4 times and dOut once, against 8
+// and 2 times by the 128 x 128 tiles.
+//   * 32-pixel stages (32 KB / 24 KB: NA + NB = 4 / 3 LDS-DMA instructions per wave) in a
+//     4-slot ring.  Per stage: counted vmcnt wait for the stage's own DMA (two later stages
+//     stay in flight: never vmcnt(0) in the steady-state loop, only in the peeled drain of the
+//     last NBUF - 2 stages), the deferred BN + ReLU by the lane that DMA'd each x piece, ONE
+//     raw barrier, the refill, the MFMAs.
+//   * RAW: a slot is read only after the barrier that follows every wave's wait for its part
+//     of the stage.  WAR: iteration st refills the slot of stage st - 1 after the barrier of
+//     iteration st, in front of which every wave retired its reads of stage st - 1
+//     (lds_sync's lgkmcnt(0)) — placed by the wait-and-barrier count, not by clean runs.
+//   * the 32-byte-group swizzle of tn2_swz on 512-byte rows: a ds_read_b64_tr_b16 half-wave
+//     reads 32 B of each of the rows {r..r+3, r+8..r+11}.  Rows are 512 B = 2 x 256 B, so
+//     every row starts at bank 0 and a group's banks are (group & 7) * 8 .. + 7; the eight
+//     rows' swizzle values (row & 3) | ((row >> 3) & 1) << 2 are 0..7, each once, and XOR by
+//     them sends one logical group to eight different (group & 7): all 64 banks once, as for
+//     256-byte rows.  Rows r + 4 (the second read of a fragment) have the swizzle of row r.
+//   * the carry-walked dOut gather and the per-split descriptors are the narrow kernel's.
+template <int BM>
+struct Tn2wCfg {
+  static constexpr int BN = 256, KT = 32, NBUF = 4, NWAVE = 8;
+  static constexpr int WM = BM / 2;                    // rows of a wave's tile (64 columns)
+  static constexpr int MT = WM / 16;
+  static constexpr int A_RB = BM * 2, B_RB = BN * 2;   // LDS row bytes
+  static constexpr int A_BYTES = KT * A_RB, B_BYTES = KT * B_RB;
+  static constexpr int NA = A_BYTES / (NWAVE * 1024);  // DMA instructions per wave per stage
+  static constexpr int NB = B_BYTES / (NWAVE * 1024);
+  static constexpr int STAGE = A_BYTES + B_BYTES;
+  static constexpr int BN_FLOATS = 512;                // deferred-BN table (M <= 512)
+  static constexpr int SMEM = NBUF * STAGE + 2 * BN_FLOATS * 4;   // 132 KB / 100 KB
+};
+
+template <int BM>
+__global__ __launch_bounds__(512) void gemm_tn_wgrad2w_kernel(GemmArgs p) {
+  using namespace convlds;
+  using Cf = Tn2wCfg<BM>;
+  constexpr int BN = Cf::BN, KT = Cf::KT, NBUF = Cf::NBUF, NBF = Cf::BN_FLOATS, MT = Cf::MT;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_bn = reinterpret_cast<float*>(smem + NBUF * Cf::STAGE);  // scale [NBF] | shift [NBF]
+  auto sA = [&](int b) { return smem + b * Cf::STAGE; };
+  auto sB = [&](int b) { return smem + b * Cf::STAGE + Cf::A_BYTES; };
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const bool has_bn = p.bn4 != nullptr;
+  if (has_bn)
+    for (int i = tid; i < p.M; i += 512) { s_bn[i] = p.bn4[2 * p.M + i]; s_bn[NBF + i] = p.bn4[3 * p.M + i]; }
+  const int nTilesN = (p.N + BN - 1) / BN, nTilesM = (p.M + BM - 1) / BM;
+  // n tiles of one pixel range innermost in XCD-contiguous order (they share x in one L2)
+  int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int ntile = b % nTilesN; b /= nTilesN;
+  const int mtile = b % nTilesM; b /= nTilesM;
+  const int split = b;
+  const int m0 = mtile * BM, n0 = ntile * BN;
+  const long long npx = (long long)p.K;
+  // (64-pixel granules, as the narrow kernel: equal splits cover equal pixels in both)
+  const long long per = ((npx + p.splits - 1) / p.splits + 63) / 64 * 64;
+  const long long k_begin = per * split;
+  const long long k_end = k_begin + per < npx ? k_begin + per : npx;
+  f32x4_t acc[MT][4];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  if (k_begin < k_end) {
+    // buffer descriptors relative to this split's first rows (32-bit offsets)
+    const long long a_lo = k_begin;
+    const auto ra = make_rsrc(p.A + a_lo * p.Cin, (unsigned)((k_end - a_lo) * p.Cin * 2));
+    const long long kb0 = k_begin - k_begin % p.W;           // row start: up_pixel is monotone
+    const long long b_lo = up_pixel((int)kb0, 0, 2, 1, p.H, p.W);
+    const long long b_hi = (long long)up_pixel((int)(k_end - 1), 3, 2, 1, p.H, p.W) + 1;
+    const auto rb = make_rsrc(p.B + b_lo * p.Cout, (unsigned)((b_hi - b_lo) * p.Cout * 2));
+    // per-lane DMA geometry (tile independent): LDS piece e = (i*8 + wave)*64 + lane
+    int a_row[Cf::NA], a_col[Cf::NA], b_row[Cf::NB], b_col[Cf::NB], b_sub[Cf::NB];
+#pragma unroll
+    for (int i = 0; i < Cf::NA; ++i) {
+      const int e = (i * 8 + wave) * 64 + lane;
+      constexpr int ppr = Cf::A_RB / 16;
+      const int row = e / ppr, pc = e % ppr;
+      const int lp = (((pc >> 1) ^ tn2_swz<Cf::A_RB>(row)) << 1) | (pc & 1);
+      a_row[i] = row;
+      a_col[i] = m0 + lp * 8 < p.M ? m0 + lp * 8 : -1;
+    }
+#pragma unroll
+    for (int i = 0; i < Cf::NB; ++i) {
+      const int e = (i * 8 + wave) * 64 + lane;
+      constexpr int ppr = Cf::B_RB / 16;
+      const int row = e / ppr, pc = e % ppr;
+      const int lp = (((pc >> 1) ^ tn2_swz<Cf::B_RB>(row)) << 1) | (pc & 1);
+      const int n = n0 + lp * 8;
+      b_row[i] = row;
+      b_sub[i] = n < p.N ? n / p.Cout : -1;
+      b_col[i] = n < p.N ? n % p.Cout : 0;
+    }
+    // each B piece's up-sampled pixel walked by carries, as in the narrow kernel (the stages
+    // are issued in k order, KT pixels apart)
+    int b_w[Cf::NB], b_base[Cf::NB], b_so[Cf::NB];
+    const int W = p.W, dq = KT / W, dw = KT % W, dbase = 4 * W * dq + 2 * dw;
+#pragma unroll
+    for (int i = 0; i < Cf::NB; ++i) {
+      const long long px0 = k_begin + b_row[i];
+      const int qq = (int)(px0 / W);
+      b_w[i] = (int)(px0 - (long long)qq * W);
+      b_base[i] = 4 * qq * W + 2 * b_w[i];
+      b_so[i] = b_sub[i] >= 0 ? (b_sub[i] >> 1) * 2 * W + (b_sub[i] & 1) : 0;
+    }
+    auto issue = [&](long long k0, int buf) {
+#pragma unroll
+      for (int i = 0; i < Cf::NA; ++i) {
+        const long long px = k0 + a_row[i];
+        const bool ok = px < k_end && a_col[i] >= 0;
+        dma16(ra, sA(buf) + (i * 8 + wave) * 1024,
+              ok ? (unsigned)(((px - a_lo) * p.Cin + a_col[i]) * 2) : kOOB);
+      }
+#pragma unroll
+      for (int i = 0; i < Cf::NB; ++i) {
+        const long long px = k0 + b_row[i];
+        const bool ok = px < k_end && b_sub[i] >= 0;
+        const long long up = ok ? (long long)(b_base[i] + b_so[i]) : b_lo;
+        b_w[i] += dw;
+        b_base[i] += dbase;
+        if (b_w[i] >= W) { b_w[i] -= W; b_base[i] += 2 * W; }
+        dma16(rb, sB(buf) + (i * 8 + wave) * 1024,
+              ok ? (unsigned)(((up - b_lo) * p.Cout + b_col[i]) * 2) : kOOB);
+      }
+    };
+    __syncthreads();                                     // s_bn visible (no DMA in flight yet)
+    // a lane's x columns are the same in every stage: its 8 scales / 8 shifts per piece live
+    // in registers for the whole launch
+    float bsc[Cf::NA][8], bsh[Cf::NA][8];
+#pragma unroll
+    for (int i = 0; i < Cf::NA; ++i) {
+      const int c = has_bn && a_col[i] >= 0 ? a_col[i] : 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 s = *reinterpret_cast<const float4*>(s_bn + c + 4 * h);
+        const float4 t = *reinterpret_cast<const float4*>(s_bn + NBF + c + 4 * h);
+        bsc[i][4 * h] = s.x; bsc[i][4 * h + 1] = s.y; bsc[i][4 * h + 2] = s.z; bsc[i][4 * h + 3] = s.w;
+        bsh[i][4 * h] = t.x; bsh[i][4 * h + 1] = t.y; bsh[i][4 * h + 2] = t.z; bsh[i][4 * h + 3] = t.w;
+      }
+    }
+    // deferred BN + ReLU of this lane's landed x pieces.  (The LDS accesses of transform and
+    // compute go through restrict-qualified parameters of inlined lambdas: their alias scopes
+    // keep the compiler from draining the LDS-DMA in flight, vmcnt(0), in front of them.)
+    auto transform = [&](long long k0, char* __restrict__ A) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < Cf::NA; ++i) {
+        if (k0 + a_row[i] < k_end && a_col[i] >= 0) {
+          uint4* q = reinterpret_cast<uint4*>(A + ((i * 8 + wave) * 64 + lane) * 16);
+          float f[8];
+          unpack8(*q, f);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = fmaxf(fmaf(f[j], bsc[i][j], bsh[i][j]), 0.f);
+          *q = pack8(f);
+        }
+      }
+    };
+    // transposed-read geometry: lane (g, q, pp) reads row 8g + q (+4) of the stage's 32 rows,
+    // columns 4pp..4pp+3 of a 16-wide m / n fragment
+    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+    auto frag_off = [&](int row, int col, auto rb_tag) {
+      constexpr int RB = decltype(rb_tag)::value;
+      const int grp = (col >> 4) ^ tn2_swz<RB>(row);
+      return row * RB + grp * 32 + (col & 15) * 2;
+    };
+    using RA = std::integral_constant<int, Cf::A_RB>;
+    using RBt = std::integral_constant<int, Cf::B_RB>;
+    const int r0 = 8 * g + q;
+    const int nst = (int)((k_end - k_begin + KT - 1) / KT);
+    constexpr int PER = Cf::NA + Cf::NB;
+    // prologue: stages 0 .. NBUF-2 in flight (stages past the end are not issued; the waits
+    // below count only what was issued)
+#pragma unroll
+    for (int j = 0; j < NBUF - 1; ++j)
+      if (j < nst) issue(k_begin + (long long)j * KT, j);
+    auto compute = [&](const char* __restrict__ A_, const char* __restrict__ B_) __attribute__((always_inline)) {
+      uint4 af[MT], bfr[4];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const int c = wm * Cf::WM + mt * 16 + 4 * pp;
+        const uint2 lo = lds_read_tr16(A_ + frag_off(r0, c, RA{}));
+        const uint2 hi = lds_read_tr16(A_ + frag_off(r0 + 4, c, RA{}));
+        af[mt] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const int c = wn * 64 + nt * 16 + 4 * pp;
+        const uint2 lo = lds_read_tr16(B_ + frag_off(r0, c, RBt{}));
+        const uint2 hi = lds_read_tr16(B_ + frag_off(r0 + 4, c, RBt{}));
+        bfr[nt] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+      }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = mfma16x16x32(af[mt], bfr[nt], acc[mt][nt]);
+    };
+    // one stage after its wait: transform, barrier, refill of the slot of stage st - 1, MFMAs
+    auto stage = [&](int st) __attribute__((always_inline)) {
+      const int buf = st % NBUF;
+      const long long k0 = k_begin + (long long)st * KT;
+      if (has_bn) transform(k0, sA(buf));
+      lds_sync();
+      if (st + NBUF - 1 < nst) issue(k0 + (long long)(NBUF - 1) * KT, (st + NBUF - 1) % NBUF);
+      compute(sA(buf), sB(buf));
+    };
+    // steady state: stages st + 1 and st + 2 stay in flight across the wait and the barrier
+    int st = 0;
+#pragma unroll 1
+    for (; st < nst - (NBUF - 2); ++st) {
+      dma_wait<(NBUF - 2) * PER>();
+      stage(st);
+    }
+    // drain: the last NBUF - 2 stages (all of them when a split has fewer stages than slots)
+#pragma unroll 1
+    for (; st < nst; ++st) {
+      vm_wait_dyn((nst - 1 - st) * PER);               // the stages issued after st
+      stage(st);
+    }
+  }
+  float* out = p.partial + (long long)split * p.M * p.N;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int n = n0 + wn * 64 + nt * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = m0 + wm * Cf::WM + mt * 16 + 4 * (lane >> 4) + i;
         if (m < p.M && n < p.N) out[(long long)m * p.N + n] = acc[mt][nt][i];
       }
     }
@@ -1285,7 +1526,17 @@ int convt_bwd_fused_splits(long long K, int num_cus) {
   return (int)std::max<long long>(1, std::min<long long>(2LL * num_cus, K / 128));   // two per CU
 }
 
+// the wide weight-gradient kernel's shape constraints (2-D, at least one 128-row and one
+// 256-column tile; a.wg2 already holds the channel-count conditions of the v2 kernels)
+bool convt_wgrad2w_ok(const GemmArgs& a) {
+  return a.mode == GEMM_CONVT_WGRAD && a.dims == 2 && a.M >= 128 && a.M <= 512 && a.N >= 256;
+}
+
 int convt_wgrad2_tiles(const GemmArgs& a) {
+  if (a.wg2 == 2) {                       // gemm_tn_wgrad2w_kernel: 256 x 256 / 128 x 256
+    const int bm = a.M >= 256 ? 256 : 128;
+    return ((a.M + bm - 1) / bm) * ((a.N + 255) / 256);
+  }
   const int bm = a.M <= 64 ? 64 : 128;
   const int bn = bm == 64 ? 256 : 128;
   return ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
@@ -1305,7 +1556,11 @@ long long gemm_nt_grid(const GemmArgs& a) {
 void gemm_launch(GemmArgs& a, hipStream_t st) {
   if (a.mode == GEMM_CONVT_WGRAD && a.wg2) {
     const int grid = convt_wgrad2_tiles(a) * a.splits;
-    if (a.M <= 64)
+    if (a.wg2 == 2 && a.M >= 256)
+      hipLaunchKernelGGL(gemm_tn_wgrad2w_kernel<256>, dim3(grid), dim3(512), Tn2wCfg<256>::SMEM, st, a);
+    else if (a.wg2 == 2)
+      hipLaunchKernelGGL(gemm_tn_wgrad2w_kernel<128>, dim3(grid), dim3(512), Tn2wCfg<128>::SMEM, st, a);
+    else if (a.M <= 64)
       hipLaunchKernelGGL(gemm_tn_wgrad2_kernel<64>, dim3(grid), dim3(256), Tn2Cfg<64>::SMEM, st, a);
     else
       hipLaunchKernelGGL(gemm_tn_wgrad2_kernel<128>, dim3(grid), dim3(256), Tn2Cfg<128>::SMEM, st, a);

@@ -179,7 +179,8 @@ struct GemmArgs {
   const float* bn4;
   const bf16_t* bny;
   float* bnpart;
-  int wg2;                        // WGRAD: 1 = gemm_tn_wgrad2_kernel (tile from convt_wgrad2_tiles)
+  int wg2;                        // WGRAD: 1 = gemm_tn_wgrad2_kernel, 2 = gemm_tn_wgrad2w_kernel
+                                  // (256-column tiles); tile count from convt_wgrad2_tiles
   const bf16_t* Wd2;              // fused backward: packed data-gradient weights [Cin][S*Cout]
 };
 enum GemmMode {
@@ -192,6 +193,7 @@ int convt_bwd_fused_splits(long long K, int num_cus);   // workgroups of the fus
 int gemm_nt_bn(const GemmArgs& a);            // N tile of the forward / data-gradient GEMM
 long long gemm_nt_grid(const GemmArgs& a);     // its workgroup count (= BN-partial rows)
 int convt_wgrad2_tiles(const GemmArgs& a);
+bool convt_wgrad2w_ok(const GemmArgs& a);      // shape constraints of the 256-column-tile kernel
 // fused data + weight gradient of a 2-D 64 -> 64-channel transposed conv (convt_gemm.hip):
 // A = x [px][64], B = dOut, C = dx [px][64] (bf16), Wd2 = packed dgrad weights, partial =
 // [splits][64][256] weight-gradient slab, bn4/bnpart = deferred BN of x and its partial rows

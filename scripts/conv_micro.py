@@ -142,6 +142,8 @@ def main():
                "tdgrad": lambda: F.convt_dgrad(dout, pk.dgrad, C)[0],
                "tdgradbn": lambda: F.convt_dgrad(dout, pk.dgrad, C, x, bn4)[0],
                "twgrad": lambda: F.convt_wgrad(x, dout),
+               # with the deferred BN + ReLU of x, as the training step calls it
+               "twgradbn": lambda: F.convt_wgrad(x, dout, None, None, None, bn4),
                # full backward with the deferred BN: fused kernel vs the separate pair
                "tbwdf": lambda: F.convt_bwd_fused(x, dout, pk.dgrad, None, None, None, bn4),
                "tbwds": lambda: (F.convt_dgrad(dout, pk.dgrad, C, x, bn4), F.convt_wgrad(x, dout, None, None, None, bn4))}
@@ -159,9 +161,12 @@ def main():
                         F.set_knob(knob, v)
                         samples[v].append(_time(fn, a.iters))
                 med = {v: sorted(x)[len(x) // 2] for v, x in samples.items()}
+                # (min..max of the rounds beside the median: a variant counts as faster only
+                # when its median lies outside the other's range)
                 print(f"{name:8s} {ps:6s} " + "  ".join(
-                    f"{knob}={v}: {med[v]:8.1f} us {flops / med[v] / 1e6:7.1f} TF/s" for v in vals),
-                    flush=True)
+                    f"{knob}={v}: {med[v]:8.1f} us [{min(samples[v]):.1f}..{max(samples[v]):.1f}] "
+                    f"{flops / med[v] / 1e6:7.1f} TF/s" for v in vals)
+                    + f"  ({med[vals[1]] / med[vals[0]]:.3f}x)", flush=True)
                 continue
             fn()
             torch.cuda.synchronize()
