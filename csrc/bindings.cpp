@@ -32,8 +32,9 @@ hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 const bf16_t* bptr(const at::Tensor& t) { return reinterpret_cast<const bf16_t*>(t.data_ptr()); }
 bf16_t* bptr_mut(at::Tensor& t) { return reinterpret_cast<bf16_t*>(t.data_ptr()); }
+bool has(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
 const float* fptr_opt(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? t->data_ptr<float>() : nullptr;
+  return has(t) ? t->data_ptr<float>() : nullptr;
 }
 
 struct Geo {
@@ -55,25 +56,11 @@ std::vector<int64_t> shape_with_c(const Geo& g, int C, int scale = 1) {
   return {g.N, (int64_t)g.D * scale, (int64_t)g.H * scale, (int64_t)g.W * scale, C};
 }
 
-int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-// pixel tile for the 3x3 conv kernels: BM pixels as TD x TH x TW
-void conv_tile(int dims, int BM, int W, int& TD, int& TH, int& TW) {
-  if (dims == 2) {
-    TD = 1;
-    TW = W >= 16 ? 16 : 8;
-    TH = BM / TW;
-  } else {
-    TW = W >= 16 ? 16 : 8;
-    TH = 4;
-    TD = BM / (TW * TH);
-  }
-}
-
-int pick_bn(int Cout) {
-  if (Cout <= 32) return 32;
-  if (Cout <= 64) return 64;
-  return 128;
+// shape of the 2x max-pooled tensor
+std::vector<int64_t> pooled_shape(const Geo& g) {
+  TORCH_CHECK(g.H % 2 == 0 && g.W % 2 == 0 && (g.dims == 2 || g.D % 2 == 0), "pool needs even dims");
+  if (g.dims == 2) return {g.N, g.H / 2, g.W / 2, g.C};
+  return {g.N, g.D / 2, g.H / 2, g.W / 2, g.C};
 }
 
 }  // namespace
@@ -177,6 +164,54 @@ at::Tensor reduce_rows(const at::Tensor& partial, int64_t R, int64_t N) {
   return sums;
 }
 
+// dst (+)= the permuted fp64 row sums of an fp32 slab [R][N] of partial results (a split-K
+// weight gradient, per-workgroup channel sums): reduce_rows_scatter_launch and its scratch
+void sum_slab(const at::Tensor& slab, int R, long long N, at::Tensor& dst, int mode, int A, int T,
+              int B, bool accumulate, long long ld = -1) {
+  at::Tensor tmp = at::empty({(int64_t)reduce_rows_scatter_tmp(R, N)}, slab.options().dtype(at::kDouble));
+  reduce_rows_scatter_launch(slab.data_ptr<float>(), R, N, tmp.data_ptr<double>(), dst.data_ptr<float>(),
+                             mode, A, T, B, accumulate, cur_stream(), ld);
+}
+
+// BatchNorm-backward coefficients [k|m1|m2] x C and dgamma / dbeta (accumulated into the outs
+// when given) from nb partial rows [nb][2][C] of (sum dyh, sum dyh * xhat): one kernel over
+// the rows, or — many rows (per-tile epilogue partials) — the coalesced two-pass fp64
+// reduction first.  dscale: optional device factor on the rows
+struct BnGrad {
+  at::Tensor coefs, dgamma, dbeta;
+  bool two_pass;
+};
+BnGrad bn_grad_from_rows(const at::Tensor& partial, int nb, int C, double count, const at::Tensor& gamma,
+                         const float* invstd, const c10::optional<at::Tensor>& dgamma_out,
+                         const c10::optional<at::Tensor>& dbeta_out, const float* dscale = nullptr) {
+  auto fopts = partial.options();
+  const bool into = has(dgamma_out);
+  BnGrad r{at::empty({3, C}, fopts), into ? *dgamma_out : at::empty({C}, fopts),
+           into ? *dbeta_out : at::empty({C}, fopts), nb > 2048};
+  if (!r.two_pass) {
+    bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, count, gamma.data_ptr<float>(), invstd,
+                                 r.dgamma.data_ptr<float>(), r.dbeta.data_ptr<float>(),
+                                 r.coefs.data_ptr<float>(), into, cur_stream(), dscale);
+  } else {
+    at::Tensor sums = reduce_rows(partial, nb, 2 * C);
+    bn_grad_finalize_launch(sums.data_ptr<double>(), C, count, gamma.data_ptr<float>(), invstd,
+                            r.dgamma.data_ptr<float>(), r.dbeta.data_ptr<float>(),
+                            r.coefs.data_ptr<float>(), into, cur_stream(), dscale);
+  }
+  return r;
+}
+
+// an arena slot (optional): the pointer to column aoff of row 0 and the row stride, for
+// `groups` rows of (mean | unbiased var) = 2C floats each
+std::pair<float*, long long> arena_slot(const c10::optional<at::Tensor>& arena, int64_t groups,
+                                        int64_t aoff, int64_t C) {
+  if (!has(arena)) return {nullptr, 0};
+  CHECK_F32(*arena);
+  TORCH_CHECK(arena->dim() == 2 && arena->size(0) >= groups && arena->stride(1) == 1 &&
+              aoff + 2 * C <= arena->size(1), "arena [rows >= groups][>= aoff + 2C]");
+  return {arena->data_ptr<float>() + aoff, (long long)arena->stride(0)};
+}
+
 // ------------------------------------------------------------------------ conv3 forward
 std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::Tensor>& x2,
                                   const at::Tensor& w, const c10::optional<at::Tensor>& bias,
@@ -195,7 +230,7 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
   a.dims = g.dims; a.N = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
   a.C1 = g.C;
   a.C2 = 0;
-  const bool dual = x2.has_value() && x2->defined();
+  const bool dual = has(x2);
   if (dual) {
     CHECK_CONTIG(*x2); CHECK_BF16(*x2);
     const Geo g2 = geo_of(*x2);
@@ -212,17 +247,17 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
   a.Cout = (int)cout;
   a.Co1 = co1 > 0 ? (int)co1 : (int)cout;
   TORCH_CHECK(a.Cout % 8 == 0 && a.Co1 % 8 == 0, "Cout and Co1 must be multiples of 8");
-  if (pscale.has_value() && pscale->defined()) TORCH_CHECK(a.C1 <= 512, "prologue supports C1 <= 512");
+  if (has(pscale)) TORCH_CHECK(a.C1 <= 512, "prologue supports C1 <= 512");
   // BN groups (ConvFwdArgs::groups): group-major statistics rows; pscale / pshift (and the
   // BNB table) per group — pscale / pshift are [groups][C1] views with a common row stride
   // (the scale / shift rows of group statistics [groups][4][C1])
   const bool grouped = groups > 1;
   if (grouped) {
     TORCH_CHECK(groups <= 1024 && g.N % groups == 0, "conv3_fwd: groups must divide the batch");
-    TORCH_CHECK(!(pscale2.has_value() && pscale2->defined()), "conv3_fwd groups: no X2 prologue");
+    TORCH_CHECK(!has(pscale2), "conv3_fwd groups: no X2 prologue");
     a.groups = (int)groups;
-    if (pscale.has_value() && pscale->defined()) {
-      TORCH_CHECK(pshift.has_value() && pshift->defined(), "conv3_fwd groups: pscale needs pshift");
+    if (has(pscale)) {
+      TORCH_CHECK(has(pshift), "conv3_fwd groups: pscale needs pshift");
       CHECK_F32(*pscale); CHECK_F32(*pshift);
       TORCH_CHECK(pscale->dim() == 2 && pscale->size(0) == groups && pscale->size(1) == g.C &&
                   pscale->stride(1) == 1 && pshift->sizes() == pscale->sizes() &&
@@ -242,11 +277,11 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
                 "X2 prologue: needs x2, both pscale2/pshift2 [C2], and C1 + C2 <= 512");
   a.Wt = bptr(w);
   a.bias = fptr_opt(bias);
-  if (bnb_y.has_value() && bnb_y->defined()) {
+  if (has(bnb_y)) {
     // BN-backward epilogue: the stats rows become that BN's (sum dyh, sum dyh*xhat) partials
     CHECK_CONTIG(*bnb_y); CHECK_BF16(*bnb_y);
     const int64_t ng = grouped ? groups : 1;
-    TORCH_CHECK(bnb_s4.has_value() && bnb_s4->defined() && bnb_s4->numel() == ng * 4 * cout,
+    TORCH_CHECK(has(bnb_s4) && bnb_s4->numel() == ng * 4 * cout,
                 "bnb: stats4 [4][Cout] ([groups][4][Cout] with groups) required");
     if (grouped) a.gstride = 4LL * cout;
     CHECK_F32(*bnb_s4); CHECK_CONTIG(*bnb_s4);
@@ -262,143 +297,31 @@ std::vector<at::Tensor> conv3_fwd(const at::Tensor& x1, const c10::optional<at::
   TORCH_CHECK(a.C2 == 0 || a.C1 % 32 == 0, "concat: first input needs C1 % 32 == 0");
   TORCH_CHECK((a.C1 % 8 == 0) && (a.C2 % 8 == 0), "input channels must be multiples of 8 "
               "(the engine pads the 3-channel image to 8)");
-  auto opts = x1.options();
   a.npix = (long long)g.N * g.D * g.H * g.W;
-  if (g.dims == 3) {
-    // the 3-D 32-input-channel layers: depth-streaming resident kernel (conv3x3x3_ds.hip;
-    // 32-channel output chunks, outputs split at Co1 for a concat conv's data gradient)
-    int grid = 0, smem = 0;
-    if (conv3d_ds_plan(a, num_cus(), grid, smem) >= 0) {
-      at::Tensor y1 = at::empty(shape_with_c(g, a.Co1), opts);
-      at::Tensor y2;
-      if (a.Co1 < a.Cout) y2 = at::empty(shape_with_c(g, a.Cout - a.Co1), opts);
-      at::Tensor stats;
-      if (want_stats) stats = at::empty({(int64_t)grid, 2, a.Cout}, opts.dtype(at::kFloat));
-      a.Y1 = bptr_mut(y1);
-      a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
-      a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
-      set_last_path("conv3_fwd:ds");
-      conv3d_ds_launch(a, grid, smem, cur_stream());
-      at::Tensor none = at::empty({0}, opts);
-      return {y1, y2.defined() ? y2 : none, stats.defined() ? stats : none};
-    }
-  }
-  {
-    // high-resolution few-channel layers: resident-weight kernel (conv3x3_res.hip)
-    int grid = 0, smem = 0;
-    const int variant = conv3_res_plan(a, num_cus(), grid, smem);
-    if (variant >= 0) {
-      at::Tensor y1 = at::empty(shape_with_c(g, a.Co1), opts);
-      at::Tensor y2;
-      if (a.Co1 < a.Cout) y2 = at::empty(shape_with_c(g, a.Cout - a.Co1), opts);
-      at::Tensor stats;
-      if (want_stats) stats = at::empty({(int64_t)grid, 2, a.Cout}, opts.dtype(at::kFloat));
-      a.Y1 = bptr_mut(y1);
-      a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
-      a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
-      set_last_path("conv3_fwd:res:v" + std::to_string(variant) +
-                    (a.Co1 < a.Cout ? ":split" : "") + (a.bnb_y != nullptr ? ":bnb" : ""));
-      conv3_res_launch(a, variant, grid, smem, cur_stream());
-      at::Tensor none = at::empty({0}, opts);
-      return {y1, y2.defined() ? y2 : none, stats.defined() ? stats : none};
-    }
-  }
-  // tile configuration: channel tile from Cout, pixel tile from the image size; the
-  // 128-channel config drops to a 64-pixel tile when the layer would not fill the chip
-  int cfg = a.Cout <= 32 ? 0 : a.Cout <= 64 ? 1 : 2;
-  auto plan = [&](int c) {
-    const int BM = conv3_fwd_cfg_bm(c);
-    conv_tile(g.dims, BM, g.W, a.TD, a.TH, a.TW);
-    a.tilesD = (g.D + a.TD - 1) / a.TD;
-    a.tilesH = (g.H + a.TH - 1) / a.TH;
-    a.tilesW = (g.W + a.TW - 1) / a.TW;
-    a.nTilesM = g.N * a.tilesD * a.tilesH * a.tilesW;
-    a.nTilesN = (a.Cout + conv3_fwd_cfg_bn(c) - 1) / conv3_fwd_cfg_bn(c);
-  };
-  plan(cfg);
-  if (cfg == 2 && g.dims == 2) {    // 256-pixel tiles on 8 waves if they fill the chip
-    plan(4);
-    if (a.nTilesM * a.nTilesN >= num_cus()) cfg = 4;
-    else plan(cfg);
-  }
-  // 512-pixel tiles (cfg 5) wherever they fill the chip without padding.  With the rolling
-  // fragment pipeline (no scratch spills) every eligible layer gains: 128-input-channel layers
-  // 8-10%, K >= 9 x 256 layers 1-2% (same-process A/B at batch 128,
-  // profiles/r3s/conv_ab_cfg5_all_r3s7.txt)
-  if (cfg == 4 && a.bnb_y == nullptr) {
-    plan(5);
-    const double w5 = (double)a.nTilesM * 512 / ((double)g.N * g.D * g.H * g.W);
-    if (a.nTilesM * a.nTilesN >= num_cus() && w5 <= 1.05) cfg = 5;
-    else plan(cfg);
-  }
-  // 3-D: the 8-wave configurations wherever they fill the chip with little padding (the
-  // 4-wave 3-D tiles need so much halo LDS that one workgroup = one wave per SIMD fits a CU)
-  if (g.dims == 3 && cfg <= 2) {
-    const int c8 = cfg == 0 ? 6 : cfg == 1 ? 7 : a.Cout == 96 ? 9 : 8;
-    plan(c8);
-    const double w8 = (double)a.nTilesM * conv3_fwd_cfg_bm(c8) / ((double)g.N * g.D * g.H * g.W);
-    if (a.nTilesM * a.nTilesN >= num_cus() && w8 <= 1.15 && g.W >= 16) cfg = c8;
-    else plan(cfg);
-  }
-  if (cfg == 2 && a.nTilesM * a.nTilesN < 2 * num_cus()) { cfg = 3; plan(cfg); }
-  // small images: a tile larger than the image computes padding (the 8x8 bottleneck layer
-  // under a 256-pixel tile is 75% padding: 48.6 -> 32.5 us with 64-pixel tiles, batch 128)
-  auto waste = [&](int c) {
-    plan(c);
-    return (double)a.nTilesM * conv3_fwd_cfg_bm(c) / ((double)g.N * g.D * g.H * g.W);
-  };
-  while ((cfg == 4 || cfg == 2) && waste(cfg) > 1.3) cfg = cfg == 4 ? 2 : 3;
-  if (cfg == 5 && waste(5) > 1.05) cfg = 4;
-  if (cfg == 5) { plan(5); TORCH_CHECK(a.TW == 16 && g.dims == 2, "cfg 5: 16-wide 2-D tiles"); }
-  plan(cfg);
-  TORCH_CHECK((g.dims == 3 ? a.TD + 2 : 1) * (a.TH + 2) * (a.TW + 2) <= conv3_fwd_cfg_halo(g.dims, cfg),
-              "halo exceeds LDS capacity");
-  // the streaming kernel's epilogue: per-image buffer descriptors (32-bit offsets) and one
-  // output per 16-channel tile
-  TORCH_CHECK((long long)g.D * g.H * g.W * a.Cout * 4 < (1LL << 31), "conv3: image too large for 32-bit offsets");
-  TORCH_CHECK(a.Co1 == a.Cout || a.Co1 % 16 == 0, "split output needs Co1 % 16 == 0");
+  const ConvFwdPlan p = conv3_fwd_plan(a, num_cus(), want_stats);
+  TORCH_CHECK(p.error == nullptr, p.error);
+  auto opts = x1.options();
+  at::Tensor none = at::empty({0}, opts);
   at::Tensor y1 = at::empty(shape_with_c(g, a.Co1), opts);
-  at::Tensor y2;
-  if (a.Co1 < a.Cout) y2 = at::empty(shape_with_c(g, a.Cout - a.Co1), opts);
-  at::Tensor stats;
-  a.persist_blocks = (cfg >= 4 ? 1 : 2) * num_cus();   // cfg >= 4: one 8-wave workgroup per CU
-  // small layers: split the input-channel chunks across workgroups so the grid fills the
-  // chip; partial sums go through an fp32 buffer and a deterministic finalize
-  const int nchunks_total = (a.Cin + 31) / 32;
-  a.ksplit = 1;
-  {
-    const int items = a.nTilesM * a.nTilesN;
-    int best = 1;
-    if (items < num_cus() && !grouped)      // (BN groups: group-major rows, no split-K)
-      for (int ks = 2; ks <= 8; ++ks)
-        if (nchunks_total % ks == 0 && nchunks_total / ks >= 2 && items * ks <= 2 * num_cus())
-          best = ks;
-    a.ksplit = best;
-  }
-  at::Tensor part;
+  at::Tensor y2 = a.Co1 < a.Cout ? at::empty(shape_with_c(g, a.Cout - a.Co1), opts) : none;
+  at::Tensor stats = want_stats ? at::empty({(int64_t)p.stat_rows, 2, a.Cout}, opts.dtype(at::kFloat)) : none;
+  at::Tensor part;                // split-K: fp32 partial sums [ksplit][npix][Cout]
   if (a.ksplit > 1) {
     part = at::empty({(int64_t)a.ksplit * a.npix * a.Cout}, opts.dtype(at::kFloat));
     a.part = part.data_ptr<float>();
   }
-  // finalize: ~one pixel group per thread (the split-K layers are the small, latency-bound
-  // ones: a short grid-stride chain per thread beats fewer, longer-running workgroups)
-  const int fin_px_per_block = std::max(1, 256 / (a.Cout / 8));
-  const int fin_grid = (int)std::min<long long>(
-      std::max<long long>(1, (a.npix + fin_px_per_block - 1) / fin_px_per_block), 2048);
-  if (want_stats) {
-    const int grid = a.ksplit > 1 ? fin_grid : conv3_fwd_grid(a);
-    stats = at::empty({(int64_t)grid, 2, a.Cout}, opts.dtype(at::kFloat));
-  }
   a.Y1 = bptr_mut(y1);
-  a.Y2 = y2.defined() ? bptr_mut(y2) : nullptr;
+  a.Y2 = a.Co1 < a.Cout ? bptr_mut(y2) : nullptr;
   a.stats = want_stats ? stats.data_ptr<float>() : nullptr;
-  set_last_path(std::string(g.dims == 3 ? "conv3_fwd:stream3d:cfg" : "conv3_fwd:stream:cfg") +
-                std::to_string(cfg) + ":ks" + std::to_string(a.ksplit) +
-                (a.bnb_y != nullptr ? ":bnb" : ""));
-  conv3_fwd_launch(a, cfg, cur_stream());
-  if (a.ksplit > 1) conv3_splitk_finalize_launch(a, fin_grid, cur_stream());
-  at::Tensor none = at::empty({0}, opts);
-  return {y1, y2.defined() ? y2 : none, stats.defined() ? stats : none};
+  set_last_path(p.path);
+  switch (p.kernel) {
+    case CONV_FWD_DS: conv3d_ds_launch(a, p.grid, p.smem, cur_stream()); break;
+    case CONV_FWD_RES: conv3_res_launch(a, p.variant, p.grid, p.smem, cur_stream()); break;
+    default:
+      conv3_fwd_launch(a, p.variant, cur_stream());
+      if (a.ksplit > 1) conv3_splitk_finalize_launch(a, p.fin_grid, cur_stream());
+  }
+  return {y1, y2, stats};
 }
 
 // ------------------------------------------------------------------------ conv3 wgrad
@@ -420,7 +343,7 @@ at::Tensor conv3_wgrad(const at::Tensor& dy, const at::Tensor& x1,
   ConvWgradArgs a{};
   a.dims = g.dims; a.N = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
   a.C1 = g.C; a.C2 = 0;
-  const bool dual = x2.has_value() && x2->defined();
+  const bool dual = has(x2);
   if (dual) { CHECK_CONTIG(*x2); a.C2 = (int)x2->size(-1); }
   a.Cin = a.C1 + a.C2;
   a.Cout = gy.C;
@@ -448,23 +371,14 @@ at::Tensor conv3_wgrad(const at::Tensor& dy, const at::Tensor& x1,
     a.gstride = pscale->stride(0);
   }
   if (a.pscale2) TORCH_CHECK(dual && a.pshift2 && a.C1 + a.C2 <= 512, "X2 prologue: x2, pscale2/pshift2, C1 + C2 <= 512");
-  int bco = a.Cout <= 32 ? 32 : 64;
-  // v2 / v3 (LDS-DMA pixel tiles 16 wide; narrower images run with masked columns: the 8x8
-  // bottleneck layers are 10% faster there than on the v1 kernel)
-  const bool v2 = g.W >= 8 && (a.C2 == 0 || a.C1 % 32 == 0);
-  // v3 (32x32x16 MFMA, conflict-free transposed reads): whole 32-channel input chunks,
-  // concat layers included (same-process bench A/B at batch 256: -0.8% step time,
-  // profiles/r3s/bench_ab_wgrad3_concat_r3s9.log)
-  const bool v3 = v2 && a.C1 % 32 == 0 && a.C2 % 32 == 0;
-  const bool emit = dy_out.has_value() && dy_out->defined();
-  if (dy_y.has_value() && dy_y->defined()) {
-    // dy holds dA; BN backward applied on load: the v2 kernel, or — with dy_out, where the
-    // formed dY is also stored — the 32-output-channel concat kernel (checked below)
+  const bool emit = has(dy_out);
+  if (has(dy_y)) {
+    // dy holds dA; BN backward applied on load (which kernels can: conv3_wgrad_plan)
     CHECK_CONTIG(*dy_y); CHECK_BF16(*dy_y);
-    TORCH_CHECK(((v2 && !v3) || emit) && g.dims == 2 && dy_y->numel() == dy.numel(),
+    TORCH_CHECK(dy_y->numel() == dy.numel(),
                 "conv3_wgrad: the dY prologue needs the v2 kernel (2-D, C1 % 32 != 0 or a 32-channel "
                 "first layer) or dy_out, and y of dY's shape");
-    TORCH_CHECK(dy_s4.has_value() && dy_s4->numel() == 4 * a.Cout && dy_coefs.has_value() &&
+    TORCH_CHECK(has(dy_s4) && dy_s4->numel() == 4 * a.Cout && has(dy_coefs) &&
                 dy_coefs->numel() == 3 * a.Cout, "conv3_wgrad: dy_s4 [4][Cout] and dy_coefs [3][Cout]");
     CHECK_F32(*dy_s4); CHECK_F32(*dy_coefs);
     a.dyy = bptr(*dy_y);
@@ -477,101 +391,31 @@ at::Tensor conv3_wgrad(const at::Tensor& dy, const at::Tensor& x1,
     }
   }
   TORCH_CHECK(!emit || a.dyy != nullptr, "conv3_wgrad: dy_out needs the dY prologue (dy_y, dy_s4, dy_coefs)");
-  // the image layer: <= 4 real channels (cin_real, from the caller) of an 8-channel padded
-  // input, (tap, channel)-packed kernel
-  // (3-D: per depth tap plane, as the v2 / v3 kernels)
-  const bool img = cin_real > 0 && cin_real <= 4 && a.C1 == 8 && !dual && g.W >= 16 &&
-                   a.pscale == nullptr && a.pscale2 == nullptr;
-  // v3 with 128 output channels per workgroup (every wave a 32-channel quarter, no k-split;
-  // 96-pixel tiles): each staged input halo feeds twice the MFMAs of the 64-channel tiles
-  // (>= 32x32 images: on the 16^2 / 8^2 levels the 96-pixel tiles are mostly masked columns,
-  // measured 3-21% slower there)
-  if (v3 && !img && a.Cout >= 128 && g.H * g.W >= 32 * 32) bco = 128;
-  // v3 with two 32-channel input chunks per 64-output-channel workgroup (each staged dY tile
-  // feeds both halos; 96-pixel tiles) on the >= 64x64 layers with >= 2 input chunks: dec2.a
-  // -13%, enc2.b / dec2.b -5% in isolation; the 8^2 / 16^2 layers lose 3-23% (masked tile
-  // columns): profiles/r3s/wgrad_ab_ciw_b256_r3s21.txt
-  a.ciw = 1;
-  if (v3 && !img && bco == 64 && a.Cin >= 64 && g.H * g.W >= 64 * 64)
-    a.ciw = 2;
-  if (img) { a.TD = 1; a.TW = 16; a.TH = conv3_wgrad_img_pt(bco) / 16; }
-  else if (v3 && (bco == 128 || a.ciw == 2)) { a.TD = 1; a.TW = 16; a.TH = 6; }
-  else if (v3) { a.TD = 1; a.TW = 16; a.TH = bco == 32 ? 16 : 8; }
-  else if (v2) { a.TD = 1; a.TW = 16; a.TH = conv3_wgrad2_pt(bco, a.C2, g.H, g.W) / 16; }
-  else if (g.dims == 2) { a.TD = 1; a.TW = g.W >= 16 ? 16 : 8; a.TH = 128 / a.TW; }
-  else { a.TW = g.W >= 16 ? 16 : 8; a.TH = 4; a.TD = 128 / (a.TW * a.TH); }
-  TORCH_CHECK(v2 || (a.TD + (g.dims == 3 ? 2 : 0)) * (a.TH + 2) * (a.TW + 2) <= conv3_wgrad_halo_cap(g.dims),
-              "wgrad halo exceeds LDS capacity");
-  a.tilesD = (g.D + a.TD - 1) / a.TD;
-  a.tilesH = (g.H + a.TH - 1) / a.TH;
-  a.tilesW = (g.W + a.TW - 1) / a.TW;
-  a.nTiles = g.N * a.tilesD * a.tilesH * a.tilesW;
-  a.coTiles = (a.Cout + bco - 1) / bco;
-  a.ciChunks = (a.Cin + 32 * a.ciw - 1) / (32 * a.ciw);
-  a.planes = g.dims == 2 ? 1 : 3;
-  // split-K over pixel tiles: enough blocks to fill the chip, but every block keeps >= 8
-  // tiles so the fp32 partial slab stays small next to the MFMA work
-  const int base = a.coTiles * a.ciChunks * a.planes;
-  // workgroups per CU to aim for: the weight gradient runs concurrently with the data-
-  // gradient chain, and its resident workgroups decide what else fits on a CU.  Round 2
-  // (other kernels): two, 1 / 3 / 4 -7 / -1.5 / -1.9%; round 5, same box, three interleaved
-  // runs each: 1 / 2 / 3 / 4 -> 7508 / 7610-7613 / 7628 / 7611 img/s, window and 3-D within
-  // noise (profiles/r5/wgrad_wg_per_cu_g71_g72/): three; re-checked at batch 384 (round 6,
-  // bench --ab, two calls): 2 / 4 -> +0.5-0.6% / +0.9-1.0% ms per step (profiles/r6/wgrad_wg_per_cu_b384_r6ac/)
-  constexpr int wg_per_cu = 3;
-  const int target = wg_per_cu * num_cus();
-  int splits = std::max(1, (target + base - 1) / base);
-  splits = std::min(splits, std::max(1, a.nTiles / 8));
-  a.splits = splits;
-  // 3-D, 32 output channels: the depth-streaming kernel (one pass over dY and X for all 27
-  // taps) when eligible
-  int ds_grid = -1, c32_grid = -1;
-  if (g.dims == 3 && !img && a.groups <= 1) {
-    ds_grid = conv3d_wgrad_ds_plan(a, num_cus());
-    if (ds_grid >= 0) splits = a.splits;
-  }
-  // 2-D 32-output-channel concat convs: every input chunk per workgroup (dY read once)
-  if (g.dims == 2 && !img && a.groups <= 1) {
-    c32_grid = conv3_wgrad_c32_plan(a, num_cus());
-    if (c32_grid >= 0) splits = a.splits;
-  }
-  TORCH_CHECK(!emit || c32_grid >= 0, "conv3_wgrad: dy_out only with the 32-output-channel concat "
-              "kernel (2-D, Cout 32, 64..96 input channels in 32-channel chunks, W >= 16, no groups)");
-  auto part = at::empty({(int64_t)splits * a.Cout * a.taps * a.Cin}, dy.options().dtype(at::kFloat));
-  a.partial = part.data_ptr<float>();
-  TORCH_CHECK(a.pscale2 == nullptr || v2, "X2 prologue needs the v2/v3 weight-gradient kernels "
-              "(2-D or 3-D, W >= 16, C1 % 32 == 0)");
-  TORCH_CHECK(a.groups <= 1 || (v3 && !img), "conv3_wgrad groups: the v3 kernel only (W >= 8, C1 % 32 == 0)");
-  {
-    const std::string d3 = g.dims == 3 ? ":3d" : "";
-    if (ds_grid >= 0) set_last_path("conv3_wgrad:ds");
-    else if (c32_grid >= 0) set_last_path(std::string("conv3_wgrad:c32") + (emit ? ":dyout" : ""));
-    else if (img) set_last_path("conv3_wgrad:img" + d3 + (a.dyy != nullptr ? ":dypro" : ""));
-    else if (v3) set_last_path("conv3_wgrad:v3:bco" + std::to_string(bco) + ":ciw" + std::to_string(a.ciw) + d3);
-    else if (v2) set_last_path("conv3_wgrad:v2" + d3 + (a.dyy != nullptr ? ":dypro" : ""));
-    else set_last_path("conv3_wgrad:v1" + d3);
-  }
-  if (ds_grid >= 0) conv3d_wgrad_ds_launch(a, ds_grid, cur_stream());
-  else if (c32_grid >= 0) conv3_wgrad_c32_launch(a, c32_grid, cur_stream());
-  else if (img) conv3_wgrad_img_launch(a, bco, cur_stream());
-  else if (v3) conv3_wgrad3_launch(a, bco, cur_stream());
-  else if (v2) conv3_wgrad2_launch(a, bco, cur_stream());
-  else conv3_wgrad_launch(a, bco, cur_stream());
-  std::vector<int64_t> wshape = {a.Cout, a.Cin, 3, 3};
-  if (g.dims == 3) wshape.push_back(3);
-  const bool into = out.has_value() && out->defined();
+  const bool into = has(out);
   if (into) {
     CHECK_F32(*out); CHECK_CONTIG(*out);
     TORCH_CHECK(out->numel() == (int64_t)a.Cout * a.Cin * a.taps, "dW out size mismatch");
   }
-  at::Tensor dW = into ? *out : at::empty(wshape, dy.options().dtype(at::kFloat));
+  const ConvWgradPlan p = conv3_wgrad_plan(a, num_cus(), (int)std::max<int64_t>(0, std::min<int64_t>(cin_real, INT32_MAX)), emit);
+  TORCH_CHECK(p.error == nullptr, p.error);
+  auto fopts = dy.options().dtype(at::kFloat);
   const long long NW = (long long)a.Cout * a.taps * a.Cin;
-  at::Tensor tmp = splits > 64 ? at::empty({(int64_t)((splits + 63) / 64) * NW},
-                                           dy.options().dtype(at::kDouble))
-                               : at::empty({0}, dy.options().dtype(at::kDouble));
-  reduce_rows_scatter_launch(part.data_ptr<float>(), splits, NW, tmp.data_ptr<double>(),
-                             dW.data_ptr<float>(), 0, a.Cout, a.taps, a.Cin, into, cur_stream());
-  return into ? at::empty({0}, dy.options().dtype(at::kFloat)) : dW;
+  at::Tensor part = at::empty({(int64_t)a.splits * NW}, fopts);
+  a.partial = part.data_ptr<float>();
+  std::vector<int64_t> wshape = {a.Cout, a.Cin, 3, 3};
+  if (g.dims == 3) wshape.push_back(3);
+  at::Tensor dW = into ? *out : at::empty(wshape, fopts);
+  set_last_path(p.path);
+  switch (p.kernel) {
+    case WGRAD_DS: conv3d_wgrad_ds_launch(a, p.grid, cur_stream()); break;
+    case WGRAD_C32: conv3_wgrad_c32_launch(a, p.grid, cur_stream()); break;
+    case WGRAD_IMG: conv3_wgrad_img_launch(a, p.bco, cur_stream()); break;
+    case WGRAD_V3: conv3_wgrad3_launch(a, p.bco, cur_stream()); break;
+    case WGRAD_V2: conv3_wgrad2_launch(a, p.bco, cur_stream()); break;
+    default: conv3_wgrad_launch(a, p.bco, cur_stream());
+  }
+  sum_slab(part, a.splits, NW, dW, 0, a.Cout, a.taps, a.Cin, into);
+  return into ? at::empty({0}, fopts) : dW;
 }
 
 // ------------------------------------------------------------------------ fused 32-channel backward
@@ -607,17 +451,13 @@ std::vector<at::Tensor> conv3_bwd32(const at::Tensor& dy, const at::Tensor& y, c
   a.dA = bptr_mut(dA); a.bnpart = bnpart.data_ptr<float>(); a.wpart = wpart.data_ptr<float>();
   set_last_path(G > 1 ? "conv3_bwd32:groups" : "conv3_bwd32");
   conv3_bwd32_launch(a, grid, cur_stream());
-  const bool into = dw_out.has_value() && dw_out->defined();
+  const bool into = has(dw_out);
   if (into) {
     CHECK_F32(*dw_out); CHECK_CONTIG(*dw_out);
     TORCH_CHECK(dw_out->numel() == 32 * 32 * 9, "dW out size mismatch");
   }
   at::Tensor dW = into ? *dw_out : at::empty({32, 32, 3, 3}, fopts);
-  const long long NW = 32LL * 9 * 32;
-  at::Tensor tmp = grid > 64 ? at::empty({(int64_t)((grid + 63) / 64) * NW}, dy.options().dtype(at::kDouble))
-                             : at::empty({0}, dy.options().dtype(at::kDouble));
-  reduce_rows_scatter_launch(wpart.data_ptr<float>(), grid, NW, tmp.data_ptr<double>(), dW.data_ptr<float>(),
-                             0, 32, 9, 32, into, cur_stream());
+  sum_slab(wpart, grid, 32LL * 9 * 32, dW, 0, 32, 9, 32, into);
   return {dA, bnpart, into ? at::empty({0}, fopts) : dW};
 }
 
@@ -632,7 +472,7 @@ at::Tensor bn_finalize(const at::Tensor& partial, double count, const at::Tensor
   const int C = (int)gamma.numel();
   const int P = (int)(partial.numel() / (2 * C));
   at::Tensor st = at::empty({4, C}, partial.options());
-  int64_t* nbp = (nbt.has_value() && nbt->defined()) ? nbt->data_ptr<int64_t>() : nullptr;
+  int64_t* nbp = has(nbt) ? nbt->data_ptr<int64_t>() : nullptr;
   if (P <= 4096) {
     bn_stats_finalize_rows_launch(partial.data_ptr<float>(), P, C, count, gamma.data_ptr<float>(),
                                   beta.data_ptr<float>(), running_mean.data_ptr<float>(),
@@ -662,7 +502,7 @@ void bn_running_apply(at::Tensor running_mean, at::Tensor running_var, const at:
   c10::DeviceGuard guard(slots.device());
   const int K = (int)slots.size(0);
   if (K == 0) return;
-  int64_t* nbp = (nbt.has_value() && nbt->defined()) ? nbt->data_ptr<int64_t>() : nullptr;
+  int64_t* nbp = has(nbt) ? nbt->data_ptr<int64_t>() : nullptr;
   bn_running_apply_launch(running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
                           slots.data_ptr<float>(), K, C, (long long)slots.stride(0), (float)momentum,
                           nbp, cur_stream());
@@ -693,20 +533,13 @@ std::vector<at::Tensor> bn_relu_apply(const at::Tensor& y, const at::Tensor& sta
   TORCH_CHECK(full || pool, "bn_relu_apply: full=False only with pool (deferred skip)");
   at::Tensor a = full ? at::empty_like(y) : at::empty({0}, y.options());
   at::Tensor p;
-  if (pool) {
-    TORCH_CHECK(g.H % 2 == 0 && g.W % 2 == 0 && (g.dims == 2 || g.D % 2 == 0), "pool needs even dims");
-    std::vector<int64_t> ps = g.dims == 2 ? std::vector<int64_t>{g.N, g.H / 2, g.W / 2, g.C}
-                                          : std::vector<int64_t>{g.N, g.D / 2, g.H / 2, g.W / 2, g.C};
-    p = at::empty(ps, y.options());
-  }
+  if (pool) p = at::empty(pooled_shape(g), y.options());
   const char* variant =
       bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, full ? bptr_mut(a) : nullptr,
                            pool ? bptr_mut(p) : nullptr, g.dims, g.N, g.D, g.H, g.W, g.C, cur_stream());
   set_last_path(std::string("bn_relu_apply:") + variant + (g.dims == 3 ? ":3d" : ""));
   return {a, p.defined() ? p : at::empty({0}, y.options())};
 }
-
-static bool gscale_is_none(const c10::optional<at::Tensor>& g) { return !(g.has_value() && g->defined()); }
 
 // dY, dgamma, dbeta from dA (+ unpool(dP)) through ReLU and BN
 std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
@@ -721,8 +554,8 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
   const Geo g = geo_of(y);
   const int C = g.C;
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
-  const bool hasA = dA.has_value() && dA->defined();
-  const bool hasP = dP.has_value() && dP->defined();
+  const bool hasA = has(dA);
+  const bool hasP = has(dP);
   TORCH_CHECK(hasA || hasP, "bn_backward needs dA or dP");
   if (hasA) { CHECK_CONTIG(*dA); CHECK_BF16(*dA); }
   if (hasP) { CHECK_CONTIG(*dP); CHECK_BF16(*dP); }
@@ -736,11 +569,11 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
   const bf16_t* pP = hasP ? bptr(*dP) : nullptr;
   // partial_in: (sum dyh, sum dyh*xhat) rows [R][2][C] already produced by the kernel that
   // wrote dA (deferred-BN epilogues); otherwise one reduction pass over dA (+dP) and y
-  const bool pre = partial_in.has_value() && partial_in->defined() && partial_in->numel() > 0;
+  const bool pre = has(partial_in) && partial_in->numel() > 0;
   int nb;
   at::Tensor partial;
   if (pre) {
-    TORCH_CHECK(!hasP && gscale_is_none(gscale), "precomputed BN partials: no pool / grad scale");
+    TORCH_CHECK(!hasP && !has(gscale), "precomputed BN partials: no pool / grad scale");
     CHECK_F32(*partial_in); CHECK_CONTIG(*partial_in);
     TORCH_CHECK(partial_in->numel() % (2 * C) == 0, "partial rows must be [R][2][C]");
     partial = *partial_in;
@@ -751,29 +584,15 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
     bn_bwd_reduce_launch(pA, pP, bptr(y), s + 2 * C, s + 3 * C, s, s + C, gs,
                          partial.data_ptr<float>(), nb, g.dims, g.N, g.D, g.H, g.W, C, cur_stream());
   }
-  const bool into = dgamma_out.has_value() && dgamma_out->defined();
-  at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
-  at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
-  at::Tensor coefs = at::empty({3, C}, fopts);
   const double count = (double)g.N * g.D * g.H * g.W;
-  const bool two_pass = nb > 2048;
-  if (!two_pass) {
-    bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, count, gamma.data_ptr<float>(),
-                                 s + C, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                                 coefs.data_ptr<float>(), into, cur_stream());
-  } else {   // many rows (per-tile epilogue partials): coalesced two-pass fp64 reduction
-    at::Tensor sums = reduce_rows(partial, nb, 2 * C);
-    bn_grad_finalize_launch(sums.data_ptr<double>(), C, count, gamma.data_ptr<float>(), s + C,
-                            dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                            coefs.data_ptr<float>(), into, cur_stream());
-  }
+  const BnGrad r = bn_grad_from_rows(partial, nb, C, count, gamma, s + C, dgamma_out, dbeta_out);
   at::Tensor dY = at::empty_like(y);
   const char* variant =
-      bn_bwd_apply_launch(pA, pP, bptr(y), s + 2 * C, s + 3 * C, s, s + C, coefs.data_ptr<float>(), gs,
+      bn_bwd_apply_launch(pA, pP, bptr(y), s + 2 * C, s + 3 * C, s, s + C, r.coefs.data_ptr<float>(), gs,
                           bptr_mut(dY), g.dims, g.N, g.D, g.H, g.W, C, cur_stream());
   set_last_path(std::string("bn_backward:") + variant + (g.dims == 3 ? ":3d" : "") + (pre ? ":rows" : "") +
-                (two_pass ? ":two_pass" : ""));
-  return {dY, dgamma, dbeta};
+                (r.two_pass ? ":two_pass" : ""));
+  return {dY, r.dgamma, r.dbeta};
 }
 
 // BatchNorm backward WITHOUT the apply pass: from precomputed (sum dyh, sum dyh*xhat) rows,
@@ -789,26 +608,11 @@ std::vector<at::Tensor> bn_grad_coefs(const at::Tensor& partial, const at::Tenso
   const int C = g.C;
   TORCH_CHECK(partial.numel() % (2 * C) == 0 && partial.numel() > 0, "partial rows must be [R][2][C]");
   const int nb = (int)(partial.numel() / (2 * C));
-  auto fopts = partial.options();
-  const bool into = dgamma_out.has_value() && dgamma_out->defined();
-  at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
-  at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
-  at::Tensor coefs = at::empty({3, C}, fopts);
-  const float* s = stats4.data_ptr<float>();
   const double count = (double)g.N * g.D * g.H * g.W;
-  if (nb <= 2048) {
-    bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, count, gamma.data_ptr<float>(),
-                                 s + C, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                                 coefs.data_ptr<float>(), into, cur_stream());
-    set_last_path("bn_grad_coefs:rows");
-  } else {
-    at::Tensor sums = reduce_rows(partial, nb, 2 * C);
-    bn_grad_finalize_launch(sums.data_ptr<double>(), C, count, gamma.data_ptr<float>(), s + C,
-                            dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                            coefs.data_ptr<float>(), into, cur_stream());
-    set_last_path("bn_grad_coefs:two_pass");
-  }
-  return {coefs, dgamma, dbeta};
+  const BnGrad r = bn_grad_from_rows(partial, nb, C, count, gamma, stats4.data_ptr<float>() + C,
+                                     dgamma_out, dbeta_out);
+  set_last_path(r.two_pass ? "bn_grad_coefs:two_pass" : "bn_grad_coefs:rows");
+  return {r.coefs, r.dgamma, r.dbeta};
 }
 
 // ------------------------------------------------------------------------ BatchNorm groups
@@ -830,15 +634,7 @@ at::Tensor bn_group_finalize(const at::Tensor& y, int64_t groups, const at::Tens
   auto fopts = y.options().dtype(at::kFloat);
   at::Tensor part = at::empty({groups, nb, 2, g.C}, fopts);
   at::Tensor st = at::empty({groups, 4, g.C}, fopts);
-  float* ap = nullptr;
-  long long astride = 0;
-  if (arena.has_value() && arena->defined()) {
-    CHECK_F32(*arena);
-    TORCH_CHECK(arena->dim() == 2 && arena->size(0) >= groups && arena->stride(1) == 1 &&
-                aoff + 2 * g.C <= arena->size(1), "arena [rows >= groups][>= aoff + 2C]");
-    ap = arena->data_ptr<float>() + aoff;
-    astride = arena->stride(0);
-  }
+  const auto [ap, astride] = arena_slot(arena, groups, aoff, g.C);
   bn_group_stats_finalize_launch(bptr(y), (int)groups, gpix, g.C, gamma.data_ptr<float>(),
                                  beta.data_ptr<float>(), (float)eps, st.data_ptr<float>(), ap,
                                  astride, part.data_ptr<float>(), nb, cur_stream());
@@ -857,15 +653,7 @@ at::Tensor bn_group_finalize_rows(const at::Tensor& partial, int64_t groups, dou
               "bn_group_finalize_rows: partial [groups * nb][2][C]");
   const int nb = (int)(partial.numel() / (groups * 2 * C));
   at::Tensor st = at::empty({groups, 4, C}, partial.options());
-  float* ap = nullptr;
-  long long astride = 0;
-  if (arena.has_value() && arena->defined()) {
-    CHECK_F32(*arena);
-    TORCH_CHECK(arena->dim() == 2 && arena->size(0) >= groups && arena->stride(1) == 1 &&
-                aoff + 2 * C <= arena->size(1), "arena [rows >= groups][>= aoff + 2C]");
-    ap = arena->data_ptr<float>() + aoff;
-    astride = arena->stride(0);
-  }
+  const auto [ap, astride] = arena_slot(arena, groups, aoff, C);
   bn_group_finalize_rows_launch(partial.data_ptr<float>(), nb, (int)groups, (long long)count, (int)C,
                                 gamma.data_ptr<float>(), beta.data_ptr<float>(), (float)eps,
                                 st.data_ptr<float>(), ap, astride, cur_stream());
@@ -882,12 +670,7 @@ std::vector<at::Tensor> bn_group_apply(const at::Tensor& y, const at::Tensor& st
   TORCH_CHECK(g.C % 8 == 0, "C must be a multiple of 8");
   at::Tensor a = at::empty_like(y);
   at::Tensor p;
-  if (pool) {
-    TORCH_CHECK(g.H % 2 == 0 && g.W % 2 == 0 && (g.dims == 2 || g.D % 2 == 0), "pool needs even dims");
-    std::vector<int64_t> ps = g.dims == 2 ? std::vector<int64_t>{g.N, g.H / 2, g.W / 2, g.C}
-                                          : std::vector<int64_t>{g.N, g.D / 2, g.H / 2, g.W / 2, g.C};
-    p = at::empty(ps, y.options());
-  }
+  if (pool) p = at::empty(pooled_shape(g), y.options());
   const float* s = stats4.data_ptr<float>();
   const char* variant =
       bn_relu_apply_launch(bptr(y), s + 2 * g.C, s + 3 * g.C, bptr_mut(a), pool ? bptr_mut(p) : nullptr,
@@ -910,8 +693,8 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
   const int C = g.C;
-  const bool hasA = dA.has_value() && dA->defined();
-  const bool hasP = dP.has_value() && dP->defined();
+  const bool hasA = has(dA);
+  const bool hasP = has(dP);
   TORCH_CHECK(hasA || hasP, "bn_group_backward needs dA or dP");
   if (hasA) { CHECK_CONTIG(*dA); CHECK_BF16(*dA); TORCH_CHECK(dA->numel() == y.numel(), "dA shape"); }
   if (hasP) { CHECK_CONTIG(*dP); CHECK_BF16(*dP); TORCH_CHECK(dP->numel() * (g.dims == 3 ? 8 : 4) == y.numel(), "dP shape"); }
@@ -924,7 +707,7 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
                                                 : (long long)g.D * g.H * g.W);
   // partial: group-major rows [groups * nb][2][C] of (sum dyh, sum dyh * xhat) from the
   // data-gradient conv's BN-backward epilogue (conv3_fwd with bnb_y and groups)
-  const bool have_part = partial.has_value() && partial->defined();
+  const bool have_part = has(partial);
   if (have_part) {
     CHECK_F32(*partial); CHECK_CONTIG(*partial);
     TORCH_CHECK(!hasP && partial->numel() % (groups * 2 * C) == 0,
@@ -934,7 +717,7 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
   auto fopts = y.options().dtype(at::kFloat);
   at::Tensor part = have_part ? *partial : at::empty({groups, nb, 2, C}, fopts);
   at::Tensor coefs = at::empty({groups, 3, C}, fopts);
-  const bool into = dgamma_out.has_value() && dgamma_out->defined();
+  const bool into = has(dgamma_out);
   at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
   at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
   at::Tensor dY = at::empty_like(y);
@@ -950,7 +733,7 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
 }
 
 static const float* bn4_ptr(const c10::optional<at::Tensor>& bn4, int C) {
-  if (!(bn4.has_value() && bn4->defined())) return nullptr;
+  if (!has(bn4)) return nullptr;
   CHECK_F32(*bn4); CHECK_CONTIG(*bn4);
   TORCH_CHECK(bn4->numel() == 4 * C, "bn4 must be [4][C] (mean, invstd, scale, shift)");
   TORCH_CHECK(C <= 512, "deferred BatchNorm supports C <= 512");
@@ -1011,7 +794,7 @@ std::vector<at::Tensor> convt_dgrad(const at::Tensor& dout, const at::Tensor& wd
   at::Tensor bnpart = at::empty({0}, dout.options().dtype(at::kFloat));
   a.bn4 = bn4_ptr(bn4, (int)cin);
   if (a.bn4 != nullptr) {
-    TORCH_CHECK(bny.has_value() && bny->defined() && bny->is_contiguous() &&
+    TORCH_CHECK(has(bny) && bny->is_contiguous() &&
                 bny->numel() == dx.numel() && bny->scalar_type() == at::kBFloat16,
                 "convt_dgrad: bny must be the deferred pre-BN input (shape of dx, bf16)");
     a.bny = bptr(*bny);
@@ -1039,112 +822,22 @@ static at::Tensor convt_bias_grad(const at::Tensor& x, const at::Tensor& dout, c
                                   const c10::optional<at::Tensor>& db_out, bool into) {
   auto fopts = x.options().dtype(at::kFloat);
   at::Tensor db = into ? *db_out : at::empty({go.C}, fopts);
-  if (colsum_rows.has_value() && colsum_rows->defined() && colsum_rows->numel() > 0) {
+  if (has(colsum_rows) && colsum_rows->numel() > 0) {
     const at::Tensor& cr = *colsum_rows;
     TORCH_CHECK(cr.dim() == 3 && cr.size(1) == 2 && cr.size(2) >= go.C, "colsum rows [R][2][C]");
-    const int R = (int)cr.size(0);
-    at::Tensor ctmp = R > 64 ? at::empty({(int64_t)((R + 63) / 64) * go.C}, x.options().dtype(at::kDouble))
-                             : at::empty({0}, x.options().dtype(at::kDouble));
-    reduce_rows_scatter_launch(cr.data_ptr<float>(), R, go.C, ctmp.data_ptr<double>(),
-                               db.data_ptr<float>(), 2, 0, 0, 0, into, cur_stream(), 2 * cr.size(2));
+    sum_slab(cr, (int)cr.size(0), go.C, db, 2, 0, 0, 0, into, 2 * cr.size(2));
   } else {
     const long long P = (long long)go.N * go.D * go.H * go.W;
     const int nb = (int)std::max<long long>(1, std::min<long long>((P + 1023) / 1024, 1024));
     at::Tensor cpart = at::empty({nb, go.C}, fopts);
     channel_sum_launch(bptr(dout), P, go.C, cpart.data_ptr<float>(), nb, cur_stream());
-    at::Tensor ctmp = nb > 64 ? at::empty({(int64_t)((nb + 63) / 64) * go.C},
-                                          x.options().dtype(at::kDouble))
-                              : at::empty({0}, x.options().dtype(at::kDouble));
-    reduce_rows_scatter_launch(cpart.data_ptr<float>(), nb, go.C, ctmp.data_ptr<double>(),
-                               db.data_ptr<float>(), 2, 0, 0, 0, into, cur_stream());
+    sum_slab(cpart, nb, go.C, db, 2, 0, 0, 0, into);
   }
   return db;
 }
 
-// Fused data + weight gradient of a 2-D 64 -> 64-channel transposed conv (dOut read once):
-// returns {dx, bnpart (deferred BN of x: [R][2][64] rows, else empty), dW, db} (dW / db
-// accumulated into the outs when given, empty then).  Other shapes: the separate kernels.
-std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
-                                    const c10::optional<at::Tensor>& dw_out,
-                                    const c10::optional<at::Tensor>& db_out,
-                                    const c10::optional<at::Tensor>& colsum_rows,
-                                    const c10::optional<at::Tensor>& bn4);
-
-// Shapes whose weight gradient takes the 256-column-tile kernel when CONVT_WGRAD_WIDE is
-// unset: the two (M, N) families measured (256 and 128 channels, channels preserved), from the
-// smallest pixel count at which its median beat the 128-column kernel's whole min..max
-// (scripts/conv_micro.py --ab at batch 32 / 128 / 384, docs/PERF.md "Transposed-conv weight
-// gradient: 256-column tiles").  With the deferred BN of x the gain is larger (the wide kernel
-// keeps a lane's scales and shifts in registers) and starts earlier; 128 channels without it
-// tie at every size.  Other shapes keep the 128-column kernel until they are measured.
-static bool convt_wgrad_wide_rule(const GemmArgs& a) {
-  const bool bn = a.bn4 != nullptr;
-  if (a.M == 256 && a.N == 1024) return a.K >= (bn ? 16384 : 65536);
-  if (a.M == 128 && a.N == 512) return bn && a.K >= 131072;
-  return false;
-}
-
-bool convt_bwd_fused_ok(const at::Tensor& x, const at::Tensor& dout) {
-  if (x.dim() != 4 || dout.dim() != 4 || x.size(3) != 64 || dout.size(3) != 64) return false;
-  if (dout.size(1) != 2 * x.size(1) || dout.size(2) != 2 * x.size(2)) return false;
-  const long long K = x.size(0) * x.size(1) * x.size(2);
-  if (K * 4 >= (long long)INT32_MAX) return false;
-  // one buffer descriptor per split over its dOut rows (32-bit offsets)
-  const long long splits = std::max<long long>(1, std::min<long long>(2LL * num_cus(), K / 128));
-  const long long per = (K + splits - 1) / splits + 64;
-  return (4 * per + 8LL * x.size(2)) * 64 * 2 < (1LL << 31);
-}
-
-std::vector<at::Tensor> convt_bwd_fused(const at::Tensor& x, const at::Tensor& dout, const at::Tensor& wd,
-                                        const c10::optional<at::Tensor>& dw_out,
-                                        const c10::optional<at::Tensor>& db_out,
-                                        const c10::optional<at::Tensor>& colsum_rows,
-                                        const c10::optional<at::Tensor>& bn4) {
-  CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x); CHECK_CONTIG(dout); CHECK_BF16(dout);
-  CHECK_BF16(wd); CHECK_CONTIG(wd);
-  c10::DeviceGuard guard(x.device());
-  const bool into = dw_out.has_value() && dw_out->defined();
-  auto fopts = x.options().dtype(at::kFloat);
-  if (!convt_bwd_fused_ok(x, dout)) {
-    const bool has_bn = bn4.has_value() && bn4->defined();
-    auto r = convt_dgrad(dout, wd, x.size(3), has_bn ? c10::optional<at::Tensor>(x) : c10::nullopt, bn4);
-    auto w = convt_wgrad(x, dout, dw_out, db_out, colsum_rows, bn4);
-    set_last_path("convt_bwd_fused:separate");
-    return {r[0], r[1], w[0], w[1]};
-  }
-  TORCH_CHECK(wd.numel() == 64 * 256, "convt_bwd_fused: packed dgrad weights must be [64][256]");
-  const Geo g = geo_of(x);
-  const Geo go = geo_of(dout);
-  GemmArgs a{};
-  a.mode = GEMM_CONVT_WGRAD;
-  a.M = 64; a.N = 256;
-  a.K = g.N * g.H * g.W;
-  a.A = bptr(x);
-  a.B = bptr(dout);
-  a.Wd2 = bptr(wd);
-  a.dims = 2; a.Nimg = g.N; a.D = 1; a.H = g.H; a.W = g.W;
-  a.Cin = 64; a.Cout = 64;
-  a.bn4 = bn4_ptr(bn4, 64);
-  a.splits = convt_bwd_fused_splits(a.K, num_cus());
-  at::Tensor dx = at::empty_like(x);
-  a.C = dx.data_ptr();
-  at::Tensor part = at::empty({(int64_t)a.splits * 64 * 256}, fopts);
-  a.partial = part.data_ptr<float>();
-  at::Tensor bnpart = at::empty({a.bn4 != nullptr ? (int64_t)a.splits : 0, 2, 64}, fopts);
-  if (a.bn4 != nullptr) a.bnpart = bnpart.data_ptr<float>();
-  set_last_path("convt_bwd_fused:fused");
-  convt_bwd_fused_launch(a, cur_stream());
-  at::Tensor dW = into ? *dw_out : at::empty({64, 64, 2, 2}, fopts);
-  const long long NW = 64LL * 256;
-  at::Tensor tmp = a.splits > 64 ? at::empty({(int64_t)((a.splits + 63) / 64) * NW}, x.options().dtype(at::kDouble))
-                                 : at::empty({0}, x.options().dtype(at::kDouble));
-  reduce_rows_scatter_launch(part.data_ptr<float>(), a.splits, NW, tmp.data_ptr<double>(),
-                             dW.data_ptr<float>(), 1, 64, 4, 64, into, cur_stream());
-  at::Tensor db = convt_bias_grad(x, dout, go, colsum_rows, db_out, into);
-  if (into) return {dx, bnpart, at::empty({0}, fopts), at::empty({0}, fopts)};
-  return {dx, bnpart, dW, db};
-}
-
+// weight (+ bias) gradient of a transposed conv: {dW, db} (accumulated into the outs when
+// given, empty then)
 std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
                                     const c10::optional<at::Tensor>& dw_out,
                                     const c10::optional<at::Tensor>& db_out,
@@ -1165,56 +858,70 @@ std::vector<at::Tensor> convt_wgrad(const at::Tensor& x, const at::Tensor& dout,
   a.dims = g.dims; a.Nimg = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
   a.Cin = g.C; a.Cout = go.C;
   a.bn4 = bn4_ptr(bn4, g.C);
-  // v2 kernel (64 x 64 wave tiles, LDS-DMA stages): enough 128 x 128 workgroups for two per
-  // CU, every split >= 4 stages of 64 pixels (other shapes: the v1 kernel)
-  int splits;
-  a.wg2 = g.C % 8 == 0 && go.C % 8 == 0 && g.C <= 512;
-  if (a.wg2) {
-    // the 256-column-tile kernel (one 8-wave workgroup per CU): CONVT_WGRAD_WIDE unset = by
-    // convt_wgrad_wide_rule, 0 = never, 1 = wherever its shape constraints hold
-    const int kw = knob("CONVT_WGRAD_WIDE", -1);
-    // splits of the variant a.wg2 names; false = a split's rows exceed a buffer descriptor.
-    // The kernels address a split's x and dOut rows through one descriptor each (32-bit
-    // offsets): bound the rows a split can span (dOut: up to 2 extra input rows / planes)
-    auto plan = [&]() {
-      const int tiles = convt_wgrad2_tiles(a);
-      splits = a.wg2 == 2 ? std::max(1, num_cus() / tiles)
-                          : std::max(1, (2 * num_cus() + tiles - 1) / tiles);
-      splits = std::min(splits, std::max(1, a.K / 256));
-      const long long per = ((long long)a.K + splits - 1) / splits + 64;
-      const long long span = g.dims == 2 ? 4 * per + 8LL * g.W : 8 * per + 16LL * g.H * g.W;
-      return span * go.C * 2 < (1LL << 31) && (a.wg2 != 2 || per * g.C * 2 < (1LL << 31));
-    };
-    if (kw != 0 && convt_wgrad2w_ok(a) && (kw == 1 || convt_wgrad_wide_rule(a))) {
-      a.wg2 = 2;
-      if (!plan()) a.wg2 = 1;
-    }
-    if (a.wg2 == 1 && !plan()) a.wg2 = 0;
-  }
-  if (!a.wg2) {
-    const int base = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-    splits = std::max(1, (4 * num_cus() + base - 1) / base);
-    splits = std::min(splits, std::max(1, a.K / 256));
-  }
-  a.splits = splits;
+  const char* path = convt_wgrad_plan(a, num_cus());
   auto fopts = x.options().dtype(at::kFloat);
-  at::Tensor part = at::empty({(int64_t)splits * a.M * a.N}, fopts);
+  const long long NW = (long long)a.M * a.N;
+  at::Tensor part = at::empty({(int64_t)a.splits * NW}, fopts);
   a.partial = part.data_ptr<float>();
-  set_last_path(a.wg2 == 2 ? "convt_wgrad:wg2w" : a.wg2 ? "convt_wgrad:wg2" : "convt_wgrad:wg1");
-  gemm_launch(a, cur_stream());
   std::vector<int64_t> ws = {g.C, go.C, 2, 2};
   if (g.dims == 3) ws.push_back(2);
-  const bool into = dw_out.has_value() && dw_out->defined();
+  const bool into = has(dw_out);
   at::Tensor dW = into ? *dw_out : at::empty(ws, fopts);
-  const long long NW = (long long)a.M * a.N;
-  at::Tensor tmp = splits > 64 ? at::empty({(int64_t)((splits + 63) / 64) * NW},
-                                           x.options().dtype(at::kDouble))
-                               : at::empty({0}, x.options().dtype(at::kDouble));
-  reduce_rows_scatter_launch(part.data_ptr<float>(), splits, NW, tmp.data_ptr<double>(),
-                             dW.data_ptr<float>(), 1, g.C, S, go.C, into, cur_stream());
+  set_last_path(path);
+  gemm_launch(a, cur_stream());
+  sum_slab(part, a.splits, NW, dW, 1, g.C, S, go.C, into);
   at::Tensor db = convt_bias_grad(x, dout, go, colsum_rows, db_out, into);
   if (into) return {at::empty({0}, fopts), at::empty({0}, fopts)};
   return {dW, db};
+}
+
+// Fused data + weight gradient of a 2-D 64 -> 64-channel transposed conv (dOut read once):
+// returns {dx, bnpart (deferred BN of x: [R][2][64] rows, else empty), dW, db} (dW / db
+// accumulated into the outs when given, empty then).  Other shapes: the separate kernels.
+std::vector<at::Tensor> convt_bwd_fused(const at::Tensor& x, const at::Tensor& dout, const at::Tensor& wd,
+                                        const c10::optional<at::Tensor>& dw_out,
+                                        const c10::optional<at::Tensor>& db_out,
+                                        const c10::optional<at::Tensor>& colsum_rows,
+                                        const c10::optional<at::Tensor>& bn4) {
+  CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x); CHECK_CONTIG(dout); CHECK_BF16(dout);
+  CHECK_BF16(wd); CHECK_CONTIG(wd);
+  c10::DeviceGuard guard(x.device());
+  const bool into = has(dw_out);
+  auto fopts = x.options().dtype(at::kFloat);
+  if (!convt_bwd_fused_ok(x.sizes().data(), (int)x.dim(), dout.sizes().data(), (int)dout.dim(), num_cus())) {
+    auto r = convt_dgrad(dout, wd, x.size(3), has(bn4) ? c10::optional<at::Tensor>(x) : c10::nullopt, bn4);
+    auto w = convt_wgrad(x, dout, dw_out, db_out, colsum_rows, bn4);
+    set_last_path("convt_bwd_fused:separate");
+    return {r[0], r[1], w[0], w[1]};
+  }
+  TORCH_CHECK(wd.numel() == 64 * 256, "convt_bwd_fused: packed dgrad weights must be [64][256]");
+  const Geo g = geo_of(x);
+  const Geo go = geo_of(dout);
+  GemmArgs a{};
+  a.mode = GEMM_CONVT_WGRAD;
+  a.M = 64; a.N = 256;
+  a.K = g.N * g.H * g.W;
+  a.A = bptr(x);
+  a.B = bptr(dout);
+  a.Wd2 = bptr(wd);
+  a.dims = 2; a.Nimg = g.N; a.D = 1; a.H = g.H; a.W = g.W;
+  a.Cin = 64; a.Cout = 64;
+  a.bn4 = bn4_ptr(bn4, 64);
+  a.splits = convt_bwd_fused_splits(a.K, num_cus());
+  at::Tensor dx = at::empty_like(x);
+  a.C = dx.data_ptr();
+  const long long NW = 64LL * 256;
+  at::Tensor part = at::empty({(int64_t)a.splits * NW}, fopts);
+  a.partial = part.data_ptr<float>();
+  at::Tensor bnpart = at::empty({a.bn4 != nullptr ? (int64_t)a.splits : 0, 2, 64}, fopts);
+  if (a.bn4 != nullptr) a.bnpart = bnpart.data_ptr<float>();
+  at::Tensor dW = into ? *dw_out : at::empty({64, 64, 2, 2}, fopts);
+  set_last_path("convt_bwd_fused:fused");
+  convt_bwd_fused_launch(a, cur_stream());
+  sum_slab(part, a.splits, NW, dW, 1, 64, 4, 64, into);
+  at::Tensor db = convt_bias_grad(x, dout, go, colsum_rows, db_out, into);
+  if (into) return {dx, bnpart, at::empty({0}, fopts), at::empty({0}, fopts)};
+  return {dx, bnpart, dW, db};
 }
 
 // ------------------------------------------------------------------------ head + CE
@@ -1227,7 +934,7 @@ static const char* head_variant(int C) { return C == 32 ? "head32" : "split"; }
 // and loss and gradients are normalised by it; hits stay unweighted; a zero sum gives loss 0
 // and zero gradients (PyTorch: NaN).  The passes of one backward must be given the same tensor.
 static const float* class_weight_ptr(const c10::optional<at::Tensor>& cw, const at::Tensor& a, int K) {
-  if (!cw.has_value() || !cw->defined()) return nullptr;
+  if (!has(cw)) return nullptr;
   CHECK_F32(*cw); CHECK_CONTIG(*cw);
   TORCH_CHECK(cw->dim() == 1 && cw->numel() == K && cw->device() == a.device(),
               "class_weight must be fp32 [K] on the activation's device");
@@ -1284,7 +991,7 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
                      class_weight_ptr(class_weight, a, K));
   set_last_path(std::string("head_ce_bwd:") + head_variant(C) + (pbn != nullptr ? ":defer" : "") +
                 (store_da ? "" : ":stats"));
-  const bool into = dw_out.has_value() && dw_out->defined();
+  const bool into = has(dw_out);
   at::Tensor sums = reduce_rows(part, nb, K * C + K);   // rows are [dW (K*C) | db (K)]
   if (into) {
     TORCH_CHECK(dw_out->is_contiguous() && db_out->is_contiguous(), "grad outs must be contiguous");
@@ -1331,7 +1038,7 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
     TORCH_CHECK(bn4.numel() == groups * 4 * C && partial.numel() % (groups * 2 * C) == 0,
                 "head_ce_bn_bwd groups: bn4 [groups][4][C], partial [groups * R][2][C]");
     auto fopts = a.options().dtype(at::kFloat);
-    const bool into = dgamma_out.has_value() && dgamma_out->defined();
+    const bool into = has(dgamma_out);
     at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
     at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
     at::Tensor coefs = at::empty({groups, 3, C}, fopts);
@@ -1355,28 +1062,13 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
   TORCH_CHECK(partial.numel() % (2 * C) == 0 && partial.numel() > 0, "partial rows must be [R][2][C]");
   const long long P = a.numel() / C;
   const int nb = (int)(partial.numel() / (2 * C));
-  auto fopts = a.options().dtype(at::kFloat);
-  const bool into = dgamma_out.has_value() && dgamma_out->defined();
-  at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
-  at::Tensor dbeta = into ? *dbeta_out : at::empty({C}, fopts);
-  at::Tensor coefs = at::empty({3, C}, fopts);
-  const float* s = pbn;
-  if (nb <= 2048) {
-    bn_grad_finalize_rows_launch(partial.data_ptr<float>(), nb, C, (double)P, gamma.data_ptr<float>(),
-                                 s + C, dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                                 coefs.data_ptr<float>(), into, cur_stream(), ps);
-  } else {
-    at::Tensor sums = reduce_rows(partial, nb, 2 * C);
-    bn_grad_finalize_launch(sums.data_ptr<double>(), C, (double)P, gamma.data_ptr<float>(), s + C,
-                            dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                            coefs.data_ptr<float>(), into, cur_stream(), ps);
-  }
+  const BnGrad r = bn_grad_from_rows(partial, nb, C, (double)P, gamma, pbn + C, dgamma_out, dbeta_out, ps);
   at::Tensor dY = at::empty_like(a);
   head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
-                       fptr_opt(gscale), out3.data_ptr<float>(), pbn, coefs.data_ptr<float>(),
+                       fptr_opt(gscale), out3.data_ptr<float>(), pbn, r.coefs.data_ptr<float>(),
                        bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream(), 1, pcw);
   set_last_path(std::string("head_ce_bn_bwd:") + head_variant(C));
-  return {dY, dgamma, dbeta};
+  return {dY, r.dgamma, r.dbeta};
 }
 
 // Training forward of the head with the deferred BatchNorm, fused with the backward's
@@ -1430,7 +1122,7 @@ std::vector<at::Tensor> head_wgrad_from_rows(const at::Tensor& rows, const at::T
   const int R = (int)rows.size(0);
   at::Tensor sums = reduce_rows(rows, R, K * C + K);
   auto fopts = rows.options();
-  const bool into = dw_out.has_value() && dw_out->defined();
+  const bool into = has(dw_out);
   if (into) {
     TORCH_CHECK(dw_out->is_contiguous() && db_out->is_contiguous(), "grad outs must be contiguous");
     if (db_out->data_ptr<float>() == dw_out->data_ptr<float>() + K * C) {
@@ -1458,7 +1150,7 @@ at::Tensor head_grad_scale(const at::Tensor& out3, const c10::optional<at::Tenso
   TORCH_CHECK(out3.numel() >= 3, "out3 must hold (loss, correct, count)");
   c10::DeviceGuard guard(out3.device());
   const float* pg = nullptr;
-  if (gs.has_value() && gs->defined()) {
+  if (has(gs)) {
     CHECK_F32(*gs); CHECK_CONTIG(*gs);
     TORCH_CHECK(gs->numel() == 1 && gs->device() == out3.device(), "gs must be one float on out3's device");
     pg = gs->data_ptr<float>();
@@ -1719,66 +1411,82 @@ std::vector<at::Tensor> tile_gather(const at::Tensor& src, const at::Tensor& lab
   return {x, y};
 }
 
-// packed scenes (uint8 pixels [P, Cin], uint8 labels [P], int64 table [n, 3] of (offset, H, W))
-// -> tile x tile crops per params (scene, y0, x0, code), mirrored borders, one of the 8
-// symmetries of the square, optional per-sample (gain, bias): {x bf16 [B, T, T, cpad], y int64}
-std::vector<at::Tensor> crop_gather(const at::Tensor& scenes, const at::Tensor& labels,
-                                    const at::Tensor& table, const at::Tensor& params,
-                                    const c10::optional<at::Tensor>& color, int64_t tile,
-                                    int64_t cpad) {
+// the arguments crop_gather and warp_gather share: packed scenes (uint8 pixels [P, Cin], uint8
+// labels [P], int64 table [n, 3] of (offset, H, W)), the op's per-sample rows `params` [B, k]
+// (layout checked by the caller), optional per-sample (gain, bias) -> the colour pointer
+static const float* check_gather_args(const char* op, const at::Tensor& scenes, const at::Tensor& labels,
+                                      const at::Tensor& table, const at::Tensor& params,
+                                      const c10::optional<at::Tensor>& color, int64_t tile) {
   CHECK_DEV(scenes); CHECK_CONTIG(scenes); CHECK_DEV(labels); CHECK_CONTIG(labels);
-  CHECK_DEV(table); CHECK_CONTIG(table); CHECK_DEV(params); CHECK_CONTIG(params);
+  CHECK_DEV(table); CHECK_CONTIG(table);
   TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
   TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
               "labels must be uint8 [pixels]");
   TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
               "table must be int64 [n, 3] (pixel offset, H, W)");
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
-              "params must be int32 [B, 4] (scene, y0, x0, code)");
-  const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0);
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
   TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(n < (1LL << 31), "too many scenes");
+  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
   TORCH_CHECK(labels.device() == scenes.device() && table.device() == scenes.device() &&
-              params.device() == scenes.device(), "crop_gather: tensors on different devices");
-  const bool has_color = color.has_value() && color->defined();
-  if (has_color) {
+              params.device() == scenes.device(), op, ": tensors on different devices");
+  const int64_t B = params.size(0);
+  if (has(color)) {
     CHECK_DEV(*color); CHECK_CONTIG(*color); CHECK_F32(*color);
     TORCH_CHECK(color->dim() == 2 && color->size(0) == B && color->size(1) == 2 &&
                 color->device() == scenes.device(), "color must be fp32 [B, 2] (gain, bias)");
   }
   const int64_t nb = crop_gather_blocks((int)tile);
-  TORCH_CHECK(B * nb * nb < (1LL << 31), "crop_gather: batch too large");
+  TORCH_CHECK(B * nb * nb < (1LL << 31), op, ": batch too large");
+  return fptr_opt(color);
+}
+
+// -> tile x tile crops per params (scene, y0, x0, code), mirrored borders, one of the 8
+// symmetries of the square: {x bf16 [B, T, T, cpad], y int64}
+std::vector<at::Tensor> crop_gather(const at::Tensor& scenes, const at::Tensor& labels,
+                                    const at::Tensor& table, const at::Tensor& params,
+                                    const c10::optional<at::Tensor>& color, int64_t tile,
+                                    int64_t cpad) {
+  CHECK_DEV(params); CHECK_CONTIG(params);
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
+              "params must be int32 [B, 4] (scene, y0, x0, code)");
+  const float* pc = check_gather_args("crop_gather", scenes, labels, table, params, color, tile);
+  const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0);
+  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
   c10::DeviceGuard guard(scenes.device());
   at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
   at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
   if (B > 0)
     crop_gather_launch(scenes.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
-                       (int)n, (long long)labels.size(0), params.data_ptr<int>(),
-                       has_color ? color->data_ptr<float>() : nullptr, (int)B, (int)in_ch, (int)tile,
-                       (int)cpad, knob("CROP_LDS_T", 1) != 0, bptr_mut(x), y.data_ptr<int64_t>(),
+                       (int)n, (long long)labels.size(0), params.data_ptr<int>(), pc, (int)B, (int)in_ch,
+                       (int)tile, (int)cpad, knob("CROP_LDS_T", 1) != 0, bptr_mut(x), y.data_ptr<int64_t>(),
                        cur_stream());
   return {x, y};
 }
 
-// virtual sample numbers -> {params int32 [B, 4], color fp32 [B, 2]} (counter-based: data.hip)
-std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
-                                    int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
-                                    double bias_jitter) {
+// the arguments crop_params and warp_params share: virtual sample numbers idx, the scenes'
+// cumulative sample counts cum [n + 1] and table [n, 3] -> the sample count B
+static int64_t check_params_args(const char* op, const at::Tensor& idx, const at::Tensor& cum,
+                                 const at::Tensor& table, int64_t tile, int64_t mode) {
   CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(cum); CHECK_CONTIG(cum); CHECK_DEV(table); CHECK_CONTIG(table);
   TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
   TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
               "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
   TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
               "cum must be int64 [n + 1]");
-  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device(),
-              "crop_params: tensors on different devices");
+  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device(), op,
+              ": tensors on different devices");
   TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
   TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
   TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  TORCH_CHECK(idx.numel() < (1LL << 31), "too many samples");
+  return idx.numel();
+}
+
+// virtual sample numbers -> {params int32 [B, 4], color fp32 [B, 2]} (counter-based: data.hip)
+std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
+                                    int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
+                                    double bias_jitter) {
+  const int64_t B = check_params_args("crop_params", idx, cum, table, tile, mode);
   c10::DeviceGuard guard(idx.device());
-  const int64_t B = idx.numel();
-  TORCH_CHECK(B < (1LL << 31), "too many samples");
   at::Tensor params = at::empty({B, 4}, idx.options().dtype(at::kInt));
   at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
   if (B > 0)
@@ -1795,38 +1503,20 @@ std::vector<at::Tensor> warp_gather(const at::Tensor& scenes, const at::Tensor& 
                                     const at::Tensor& table, const at::Tensor& wparams,
                                     const c10::optional<at::Tensor>& color, int64_t tile,
                                     int64_t cpad) {
-  CHECK_DEV(scenes); CHECK_CONTIG(scenes); CHECK_DEV(labels); CHECK_CONTIG(labels);
-  CHECK_DEV(table); CHECK_CONTIG(table); CHECK_DEV(wparams); CHECK_CONTIG(wparams);
-  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
-  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
-              "labels must be uint8 [pixels]");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
-              "table must be int64 [n, 3] (pixel offset, H, W)");
+  CHECK_DEV(wparams); CHECK_CONTIG(wparams);
   TORCH_CHECK(wparams.scalar_type() == at::kLong && wparams.dim() == 2 && wparams.size(1) == 6,
               "wparams must be int64 [B, 6] (scene, cy, cx, code, A, Bm)");
+  const float* pc = check_gather_args("warp_gather", scenes, labels, table, wparams, color, tile);
   const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0);
   TORCH_CHECK(cpad == 4 || cpad == 8, "cpad must be 4 or 8");
   TORCH_CHECK(in_ch >= 1 && in_ch <= cpad, "1 <= in_ch <= cpad");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(n < (1LL << 31), "too many scenes");
-  TORCH_CHECK(labels.device() == scenes.device() && table.device() == scenes.device() &&
-              wparams.device() == scenes.device(), "warp_gather: tensors on different devices");
-  const bool has_color = color.has_value() && color->defined();
-  if (has_color) {
-    CHECK_DEV(*color); CHECK_CONTIG(*color); CHECK_F32(*color);
-    TORCH_CHECK(color->dim() == 2 && color->size(0) == B && color->size(1) == 2 &&
-                color->device() == scenes.device(), "color must be fp32 [B, 2] (gain, bias)");
-  }
-  const int64_t nb = crop_gather_blocks((int)tile);
-  TORCH_CHECK(B * nb * nb < (1LL << 31), "warp_gather: batch too large");
   c10::DeviceGuard guard(scenes.device());
   at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
   at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
   if (B > 0)
     warp_gather_launch(scenes.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
-                       (int)n, (long long)labels.size(0), wparams.data_ptr<int64_t>(),
-                       has_color ? color->data_ptr<float>() : nullptr, (int)B, (int)in_ch, (int)tile,
-                       (int)cpad, bptr_mut(x), y.data_ptr<int64_t>(), cur_stream());
+                       (int)n, (long long)labels.size(0), wparams.data_ptr<int64_t>(), pc, (int)B,
+                       (int)in_ch, (int)tile, (int)cpad, bptr_mut(x), y.data_ptr<int64_t>(), cur_stream());
   return {x, y};
 }
 
@@ -1835,26 +1525,15 @@ std::vector<at::Tensor> warp_gather(const at::Tensor& scenes, const at::Tensor& 
 std::vector<at::Tensor> warp_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
                                     const at::Tensor& steps, const at::Tensor& rot, int64_t seed,
                                     int64_t tile, int64_t mode, double gain_jitter, double bias_jitter) {
-  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(cum); CHECK_CONTIG(cum); CHECK_DEV(table); CHECK_CONTIG(table);
   CHECK_DEV(steps); CHECK_CONTIG(steps); CHECK_DEV(rot); CHECK_CONTIG(rot);
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
-              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
-  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
-              "cum must be int64 [n + 1]");
   TORCH_CHECK(steps.scalar_type() == at::kInt && steps.dim() == 1 && steps.size(0) >= 1 &&
               steps.size(0) <= 65536, "steps must be int32 [S], 1 <= S <= 65536");
   TORCH_CHECK(rot.scalar_type() == at::kInt && rot.dim() == 2 && rot.size(1) == 2 && rot.size(0) >= 1 &&
               rot.size(0) <= 65536, "rot must be int32 [T, 2] (cos, sin), 1 <= T <= 65536");
-  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device() &&
-              steps.device() == idx.device() && rot.device() == idx.device(),
+  TORCH_CHECK(steps.device() == idx.device() && rot.device() == idx.device(),
               "warp_params: tensors on different devices");
-  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  const int64_t B = check_params_args("warp_params", idx, cum, table, tile, mode);
   c10::DeviceGuard guard(idx.device());
-  const int64_t B = idx.numel();
-  TORCH_CHECK(B < (1LL << 31), "too many samples");
   at::Tensor wparams = at::empty({B, 6}, idx.options().dtype(at::kLong));
   at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
   if (B > 0)
@@ -1891,7 +1570,7 @@ struct CodesSeen {
 }  // namespace
 static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& like, uint32_t* packed) {
   *packed = 0u;
-  if (!codes.has_value() || !codes->defined()) return 1;
+  if (!has(codes)) return 1;
   TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
   TORCH_CHECK(codes->device() == like.device(), "codes must be on the device of the other tensors");
   const int64_t S = codes->size(0);
@@ -1996,7 +1675,7 @@ std::vector<at::Tensor> scene_finalize(const at::Tensor& acc, int64_t K,
   c10::DeviceGuard guard(acc.device());
   const int64_t H = acc.size(0), W = acc.size(1);
   const uint8_t* lp = nullptr;
-  if (labels.has_value() && labels->defined()) {
+  if (has(labels)) {
     CHECK_DEV(*labels); CHECK_CONTIG(*labels);
     TORCH_CHECK(labels->scalar_type() == at::kByte && labels->dim() == 2 && labels->size(0) == H &&
                 labels->size(1) == W && labels->device() == acc.device(), "labels must be uint8 [H, W]");

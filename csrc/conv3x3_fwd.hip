@@ -36,6 +36,7 @@
 #include "conv_lds.h"
 #include "ops.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 // Timing-decomposition builds only (scripts/build_diag.sh; never the shipped library):
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 4 ? 2 : 1) void conv3_fwd_
   // ---- per-lane fragment geometry (item independent)
   const int g = lane >> 4;
   // tile pixel -> (w, h, d) without integer division: TW is 8 or 16 and TW * TH (2-D) /
-  // TW * TH * TD with TH = 4 (3-D) is the tile (bindings.cpp conv_tile)
+  // TW * TH * TD with TH = 4 (3-D) is the tile (conv_tile below)
   const int tw_sh = p.TW == 16 ? 4 : 3;
   auto pix_geo = [&](int pix, int& pw, int& ph, int& pd) __attribute__((always_inline)) {
     pw = pix & (p.TW - 1);
@@ -1064,6 +1065,136 @@ void conv3_fwd_launch(ConvFwdArgs& a, int cfg, hipStream_t st) {
       default: launch_cfg<3, 1, 4, 4, 2, 384>(a, st); break;
     }
   }
+}
+
+namespace {
+
+// pixel tile for the 3x3 conv kernels: BM pixels as TD x TH x TW
+void conv_tile(int dims, int BM, int W, int& TD, int& TH, int& TW) {
+  if (dims == 2) {
+    TD = 1;
+    TW = W >= 16 ? 16 : 8;
+    TH = BM / TW;
+  } else {
+    TW = W >= 16 ? 16 : 8;
+    TH = 4;
+    TD = BM / (TW * TH);
+  }
+}
+
+}  // namespace
+
+ConvFwdPlan conv3_fwd_plan(ConvFwdArgs& a, int num_cus, bool want_stats) {
+  ConvFwdPlan p{};
+  if (a.dims == 3) {
+    // the 3-D 32-input-channel layers: depth-streaming resident kernel (conv3x3x3_ds.hip;
+    // 32-channel output chunks, outputs split at Co1 for a concat conv's data gradient)
+    if (conv3d_ds_plan(a, num_cus, p.grid, p.smem) >= 0) {
+      p.kernel = CONV_FWD_DS;
+      p.stat_rows = want_stats ? p.grid : 0;
+      std::snprintf(p.path, sizeof(p.path), "conv3_fwd:ds");
+      return p;
+    }
+  }
+  // high-resolution few-channel layers: resident-weight kernel (conv3x3_res.hip)
+  p.variant = conv3_res_plan(a, num_cus, p.grid, p.smem);
+  if (p.variant >= 0) {
+    p.kernel = CONV_FWD_RES;
+    p.stat_rows = want_stats ? p.grid : 0;
+    std::snprintf(p.path, sizeof(p.path), "conv3_fwd:res:v%d%s%s", p.variant,
+                  a.Co1 < a.Cout ? ":split" : "", a.bnb_y != nullptr ? ":bnb" : "");
+    return p;
+  }
+  p.kernel = CONV_FWD_STREAM;
+  p.grid = p.smem = 0;
+  const double pixels = (double)a.N * a.D * a.H * a.W;
+  // tile configuration: channel tile from Cout, pixel tile from the image size; the
+  // 128-channel config drops to a 64-pixel tile when the layer would not fill the chip
+  int cfg = a.Cout <= 32 ? 0 : a.Cout <= 64 ? 1 : 2;
+  auto plan = [&](int c) {
+    const int BM = conv3_fwd_cfg_bm(c);
+    conv_tile(a.dims, BM, a.W, a.TD, a.TH, a.TW);
+    a.tilesD = (a.D + a.TD - 1) / a.TD;
+    a.tilesH = (a.H + a.TH - 1) / a.TH;
+    a.tilesW = (a.W + a.TW - 1) / a.TW;
+    a.nTilesM = a.N * a.tilesD * a.tilesH * a.tilesW;
+    a.nTilesN = (a.Cout + conv3_fwd_cfg_bn(c) - 1) / conv3_fwd_cfg_bn(c);
+  };
+  plan(cfg);
+  if (cfg == 2 && a.dims == 2) {    // 256-pixel tiles on 8 waves if they fill the chip
+    plan(4);
+    if (a.nTilesM * a.nTilesN >= num_cus) cfg = 4;
+    else plan(cfg);
+  }
+  // 512-pixel tiles (cfg 5) wherever they fill the chip without padding.  With the rolling
+  // fragment pipeline (no scratch spills) every eligible layer gains: 128-input-channel layers
+  // 8-10%, K >= 9 x 256 layers 1-2% (same-process A/B at batch 128,
+  // profiles/r3s/conv_ab_cfg5_all_r3s7.txt)
+  if (cfg == 4 && a.bnb_y == nullptr) {
+    plan(5);
+    const double w5 = (double)a.nTilesM * 512 / pixels;
+    if (a.nTilesM * a.nTilesN >= num_cus && w5 <= 1.05) cfg = 5;
+    else plan(cfg);
+  }
+  // 3-D: the 8-wave configurations wherever they fill the chip with little padding (the
+  // 4-wave 3-D tiles need so much halo LDS that one workgroup = one wave per SIMD fits a CU)
+  if (a.dims == 3 && cfg <= 2) {
+    const int c8 = cfg == 0 ? 6 : cfg == 1 ? 7 : a.Cout == 96 ? 9 : 8;
+    plan(c8);
+    const double w8 = (double)a.nTilesM * conv3_fwd_cfg_bm(c8) / pixels;
+    if (a.nTilesM * a.nTilesN >= num_cus && w8 <= 1.15 && a.W >= 16) cfg = c8;
+    else plan(cfg);
+  }
+  if (cfg == 2 && a.nTilesM * a.nTilesN < 2 * num_cus) { cfg = 3; plan(cfg); }
+  // small images: a tile larger than the image computes padding (the 8x8 bottleneck layer
+  // under a 256-pixel tile is 75% padding: 48.6 -> 32.5 us with 64-pixel tiles, batch 128)
+  auto waste = [&](int c) {
+    plan(c);
+    return (double)a.nTilesM * conv3_fwd_cfg_bm(c) / pixels;
+  };
+  while ((cfg == 4 || cfg == 2) && waste(cfg) > 1.3) cfg = cfg == 4 ? 2 : 3;
+  if (cfg == 5 && waste(5) > 1.05) cfg = 4;
+  if (cfg == 5) {
+    plan(5);
+    if (!(a.TW == 16 && a.dims == 2)) { p.error = "cfg 5: 16-wide 2-D tiles"; return p; }
+  }
+  plan(cfg);
+  if (!((a.dims == 3 ? a.TD + 2 : 1) * (a.TH + 2) * (a.TW + 2) <= conv3_fwd_cfg_halo(a.dims, cfg))) {
+    p.error = "halo exceeds LDS capacity";
+    return p;
+  }
+  // the streaming kernel's epilogue: per-image buffer descriptors (32-bit offsets) and one
+  // output per 16-channel tile
+  if (!((long long)a.D * a.H * a.W * a.Cout * 4 < (1LL << 31))) {
+    p.error = "conv3: image too large for 32-bit offsets";
+    return p;
+  }
+  if (!(a.Co1 == a.Cout || a.Co1 % 16 == 0)) { p.error = "split output needs Co1 % 16 == 0"; return p; }
+  a.persist_blocks = (cfg >= 4 ? 1 : 2) * num_cus;   // cfg >= 4: one 8-wave workgroup per CU
+  // small layers: split the input-channel chunks across workgroups so the grid fills the
+  // chip; partial sums go through an fp32 buffer and a deterministic finalize
+  const int nchunks_total = (a.Cin + 31) / 32;
+  a.ksplit = 1;
+  {
+    const int items = a.nTilesM * a.nTilesN;
+    int best = 1;
+    if (items < num_cus && a.groups <= 1)   // (BN groups: group-major rows, no split-K)
+      for (int ks = 2; ks <= 8; ++ks)
+        if (nchunks_total % ks == 0 && nchunks_total / ks >= 2 && items * ks <= 2 * num_cus)
+          best = ks;
+    a.ksplit = best;
+  }
+  // finalize: ~one pixel group per thread (the split-K layers are the small, latency-bound
+  // ones: a short grid-stride chain per thread beats fewer, longer-running workgroups)
+  const int fin_px_per_block = std::max(1, 256 / (a.Cout / 8));
+  p.fin_grid = (int)std::min<long long>(
+      std::max<long long>(1, (a.npix + fin_px_per_block - 1) / fin_px_per_block), 2048);
+  p.variant = cfg;
+  p.grid = conv3_fwd_grid(a);
+  p.stat_rows = !want_stats ? 0 : a.ksplit > 1 ? p.fin_grid : p.grid;
+  std::snprintf(p.path, sizeof(p.path), "conv3_fwd:%s:cfg%d:ks%d%s", a.dims == 3 ? "stream3d" : "stream",
+                cfg, a.ksplit, a.bnb_y != nullptr ? ":bnb" : "");
+  return p;
 }
 
 }  // namespace ddlpc

@@ -19,6 +19,7 @@
 #include "conv_lds.h"
 #include "ops.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 #include <stdexcept>
@@ -1267,5 +1268,116 @@ void conv3_wgrad_launch(ConvWgradArgs& a, int bco, hipStream_t st) {
 }
 
 int conv3_wgrad_halo_cap(int dims) { return dims == 2 ? WgHalo<2>::value : WgHalo<3>::value; }
+
+ConvWgradPlan conv3_wgrad_plan(ConvWgradArgs& a, int num_cus, int cin_real, bool emit_dy) {
+  ConvWgradPlan p{};
+  p.grid = -1;
+  const bool dual = a.X2 != nullptr;
+  int bco = a.Cout <= 32 ? 32 : 64;
+  // v2 / v3 (LDS-DMA pixel tiles 16 wide; narrower images run with masked columns: the 8x8
+  // bottleneck layers are 10% faster there than on the v1 kernel)
+  const bool v2 = a.W >= 8 && (a.C2 == 0 || a.C1 % 32 == 0);
+  // v3 (32x32x16 MFMA, conflict-free transposed reads): whole 32-channel input chunks,
+  // concat layers included (same-process bench A/B at batch 256: -0.8% step time,
+  // profiles/r3s/bench_ab_wgrad3_concat_r3s9.log)
+  const bool v3 = v2 && a.C1 % 32 == 0 && a.C2 % 32 == 0;
+  // dy holds dA; BN backward applied on load: the v2 kernel, or — with dy_out, where the
+  // formed dY is also stored — the 32-output-channel concat kernel (checked below)
+  if (a.dyy != nullptr && !(((v2 && !v3) || emit_dy) && a.dims == 2)) {
+    p.error = "conv3_wgrad: the dY prologue needs the v2 kernel (2-D, C1 % 32 != 0 or a 32-channel "
+              "first layer) or dy_out, and y of dY's shape";
+    return p;
+  }
+  // the image layer: <= 4 real channels (cin_real, from the caller) of an 8-channel padded
+  // input, (tap, channel)-packed kernel
+  // (3-D: per depth tap plane, as the v2 / v3 kernels)
+  const bool img = cin_real > 0 && cin_real <= 4 && a.C1 == 8 && !dual && a.W >= 16 &&
+                   a.pscale == nullptr && a.pscale2 == nullptr;
+  // v3 with 128 output channels per workgroup (every wave a 32-channel quarter, no k-split;
+  // 96-pixel tiles): each staged input halo feeds twice the MFMAs of the 64-channel tiles
+  // (>= 32x32 images: on the 16^2 / 8^2 levels the 96-pixel tiles are mostly masked columns,
+  // measured 3-21% slower there)
+  if (v3 && !img && a.Cout >= 128 && a.H * a.W >= 32 * 32) bco = 128;
+  // v3 with two 32-channel input chunks per 64-output-channel workgroup (each staged dY tile
+  // feeds both halos; 96-pixel tiles) on the >= 64x64 layers with >= 2 input chunks: dec2.a
+  // -13%, enc2.b / dec2.b -5% in isolation; the 8^2 / 16^2 layers lose 3-23% (masked tile
+  // columns): profiles/r3s/wgrad_ab_ciw_b256_r3s21.txt
+  a.ciw = 1;
+  if (v3 && !img && bco == 64 && a.Cin >= 64 && a.H * a.W >= 64 * 64)
+    a.ciw = 2;
+  if (img) { a.TD = 1; a.TW = 16; a.TH = conv3_wgrad_img_pt(bco) / 16; }
+  else if (v3 && (bco == 128 || a.ciw == 2)) { a.TD = 1; a.TW = 16; a.TH = 6; }
+  else if (v3) { a.TD = 1; a.TW = 16; a.TH = bco == 32 ? 16 : 8; }
+  else if (v2) { a.TD = 1; a.TW = 16; a.TH = conv3_wgrad2_pt(bco, a.C2, a.H, a.W) / 16; }
+  else if (a.dims == 2) { a.TD = 1; a.TW = a.W >= 16 ? 16 : 8; a.TH = 128 / a.TW; }
+  else { a.TW = a.W >= 16 ? 16 : 8; a.TH = 4; a.TD = 128 / (a.TW * a.TH); }
+  if (!(v2 || (a.TD + (a.dims == 3 ? 2 : 0)) * (a.TH + 2) * (a.TW + 2) <= conv3_wgrad_halo_cap(a.dims))) {
+    p.error = "wgrad halo exceeds LDS capacity";
+    return p;
+  }
+  a.tilesD = (a.D + a.TD - 1) / a.TD;
+  a.tilesH = (a.H + a.TH - 1) / a.TH;
+  a.tilesW = (a.W + a.TW - 1) / a.TW;
+  a.nTiles = a.N * a.tilesD * a.tilesH * a.tilesW;
+  a.coTiles = (a.Cout + bco - 1) / bco;
+  a.ciChunks = (a.Cin + 32 * a.ciw - 1) / (32 * a.ciw);
+  a.planes = a.dims == 2 ? 1 : 3;
+  // split-K over pixel tiles: enough blocks to fill the chip, but every block keeps >= 8
+  // tiles so the fp32 partial slab stays small next to the MFMA work
+  const int base = a.coTiles * a.ciChunks * a.planes;
+  // workgroups per CU to aim for: the weight gradient runs concurrently with the data-
+  // gradient chain, and its resident workgroups decide what else fits on a CU.  Round 2
+  // (other kernels): two, 1 / 3 / 4 -7 / -1.5 / -1.9%; round 5, same box, three interleaved
+  // runs each: 1 / 2 / 3 / 4 -> 7508 / 7610-7613 / 7628 / 7611 img/s, window and 3-D within
+  // noise (profiles/r5/wgrad_wg_per_cu_g71_g72/): three; re-checked at batch 384 (round 6,
+  // bench --ab, two calls): 2 / 4 -> +0.5-0.6% / +0.9-1.0% ms per step (profiles/r6/wgrad_wg_per_cu_b384_r6ac/)
+  constexpr int wg_per_cu = 3;
+  const int target = wg_per_cu * num_cus;
+  a.splits = std::max(1, (target + base - 1) / base);
+  a.splits = std::min(a.splits, std::max(1, a.nTiles / 8));
+  // 3-D, 32 output channels: the depth-streaming kernel (one pass over dY and X for all 27
+  // taps) when eligible
+  int ds_grid = -1, c32_grid = -1;
+  if (a.dims == 3 && !img && a.groups <= 1) ds_grid = conv3d_wgrad_ds_plan(a, num_cus);
+  // 2-D 32-output-channel concat convs: every input chunk per workgroup (dY read once)
+  if (a.dims == 2 && !img && a.groups <= 1) c32_grid = conv3_wgrad_c32_plan(a, num_cus);
+  if (emit_dy && c32_grid < 0) {
+    p.error = "conv3_wgrad: dy_out only with the 32-output-channel concat "
+              "kernel (2-D, Cout 32, 64..96 input channels in 32-channel chunks, W >= 16, no groups)";
+    return p;
+  }
+  if (!(a.pscale2 == nullptr || v2)) {
+    p.error = "X2 prologue needs the v2/v3 weight-gradient kernels "
+              "(2-D or 3-D, W >= 16, C1 % 32 == 0)";
+    return p;
+  }
+  if (!(a.groups <= 1 || (v3 && !img))) {
+    p.error = "conv3_wgrad groups: the v3 kernel only (W >= 8, C1 % 32 == 0)";
+    return p;
+  }
+  p.bco = bco;
+  const char* d3 = a.dims == 3 ? ":3d" : "";
+  const char* dypro = a.dyy != nullptr ? ":dypro" : "";
+  if (ds_grid >= 0) {
+    p.kernel = WGRAD_DS; p.grid = ds_grid;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:ds");
+  } else if (c32_grid >= 0) {
+    p.kernel = WGRAD_C32; p.grid = c32_grid;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:c32%s", emit_dy ? ":dyout" : "");
+  } else if (img) {
+    p.kernel = WGRAD_IMG;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:img%s%s", d3, dypro);
+  } else if (v3) {
+    p.kernel = WGRAD_V3;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:v3:bco%d:ciw%d%s", bco, a.ciw, d3);
+  } else if (v2) {
+    p.kernel = WGRAD_V2;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:v2%s%s", d3, dypro);
+  } else {
+    p.kernel = WGRAD_V1;
+    std::snprintf(p.path, sizeof(p.path), "conv3_wgrad:v1%s", d3);
+  }
+  return p;
+}
 
 }  // namespace ddlpc

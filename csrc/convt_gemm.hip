@@ -1542,6 +1542,72 @@ int convt_wgrad2_tiles(const GemmArgs& a) {
   return ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
 }
 
+// the fused backward addresses a split's dOut rows through one buffer descriptor (32-bit
+// offsets): up to 2 extra input rows
+bool convt_bwd_fused_ok(const int64_t* x, int xdim, const int64_t* dout, int ddim, int num_cus) {
+  if (xdim != 4 || ddim != 4 || x[3] != 64 || dout[3] != 64) return false;
+  if (dout[1] != 2 * x[1] || dout[2] != 2 * x[2]) return false;
+  const long long K = x[0] * x[1] * x[2];
+  if (K * 4 >= (long long)INT32_MAX) return false;
+  const long long splits = convt_bwd_fused_splits(K, num_cus);
+  const long long per = (K + splits - 1) / splits + 64;
+  return (4 * per + 8LL * x[2]) * 64 * 2 < (1LL << 31);
+}
+
+namespace {
+
+// Shapes whose weight gradient takes the 256-column-tile kernel when CONVT_WGRAD_WIDE is
+// unset: the two (M, N) families measured (256 and 128 channels, channels preserved), from the
+// smallest pixel count at which its median beat the 128-column kernel's whole min..max
+// (scripts/conv_micro.py --ab at batch 32 / 128 / 384, docs/PERF.md "Transposed-conv weight
+// gradient: 256-column tiles").  With the deferred BN of x the gain is larger (the wide kernel
+// keeps a lane's scales and shifts in registers) and starts earlier; 128 channels without it
+// tie at every size.  Other shapes keep the 128-column kernel until they are measured.
+bool convt_wgrad_wide_rule(const GemmArgs& a) {
+  const bool bn = a.bn4 != nullptr;
+  if (a.M == 256 && a.N == 1024) return a.K >= (bn ? 16384 : 65536);
+  if (a.M == 128 && a.N == 512) return bn && a.K >= 131072;
+  return false;
+}
+
+}  // namespace
+
+const char* convt_wgrad_plan(GemmArgs& a, int num_cus) {
+  // v2 kernel (64 x 64 wave tiles, LDS-DMA stages): enough 128 x 128 workgroups for two per
+  // CU, every split >= 4 stages of 64 pixels (other shapes: the v1 kernel)
+  int splits = 1;
+  a.wg2 = a.Cin % 8 == 0 && a.Cout % 8 == 0 && a.Cin <= 512;
+  if (a.wg2) {
+    // the 256-column-tile kernel (one 8-wave workgroup per CU): CONVT_WGRAD_WIDE unset = by
+    // convt_wgrad_wide_rule, 0 = never, 1 = wherever its shape constraints hold
+    const int kw = knob("CONVT_WGRAD_WIDE", -1);
+    // splits of the variant a.wg2 names; false = a split's rows exceed a buffer descriptor.
+    // The kernels address a split's x and dOut rows through one descriptor each (32-bit
+    // offsets): bound the rows a split can span (dOut: up to 2 extra input rows / planes)
+    auto plan = [&]() {
+      const int tiles = convt_wgrad2_tiles(a);
+      splits = a.wg2 == 2 ? std::max(1, num_cus / tiles)
+                          : std::max(1, (2 * num_cus + tiles - 1) / tiles);
+      splits = std::min(splits, std::max(1, a.K / 256));
+      const long long per = ((long long)a.K + splits - 1) / splits + 64;
+      const long long span = a.dims == 2 ? 4 * per + 8LL * a.W : 8 * per + 16LL * a.H * a.W;
+      return span * a.Cout * 2 < (1LL << 31) && (a.wg2 != 2 || per * a.Cin * 2 < (1LL << 31));
+    };
+    if (kw != 0 && convt_wgrad2w_ok(a) && (kw == 1 || convt_wgrad_wide_rule(a))) {
+      a.wg2 = 2;
+      if (!plan()) a.wg2 = 1;
+    }
+    if (a.wg2 == 1 && !plan()) a.wg2 = 0;
+  }
+  if (!a.wg2) {
+    const int base = ((a.M + 63) / 64) * ((a.N + 63) / 64);
+    splits = std::max(1, (4 * num_cus + base - 1) / base);
+    splits = std::min(splits, std::max(1, a.K / 256));
+  }
+  a.splits = splits;
+  return a.wg2 == 2 ? "convt_wgrad:wg2w" : a.wg2 ? "convt_wgrad:wg2" : "convt_wgrad:wg1";
+}
+
 int gemm_nt_bn(const GemmArgs& a) {
   return a.N % 128 == 0 ? 128 : 64;      // 128-wide N tiles (fwd -9%, dgrad -7%: docs/PERF.md)
 }

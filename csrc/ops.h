@@ -74,6 +74,24 @@ void conv3_res_launch(ConvFwdArgs& a, int variant, int grid, int smem, hipStream
 int conv3_fwd_cfg_bn(int cfg);
 int conv3_fwd_cfg_bm(int cfg);
 int conv3_fwd_cfg_halo(int dims, int cfg);
+// Launch planners (here and below: conv3_wgrad_plan, convt_wgrad_plan, convt_bwd_fused_ok):
+// plain host code beside the kernels they plan for — no ATen / c10, no HIP API call — so
+// tools/host_sanitize.cpp sweeps them on a CPU and tests/golden/launch_plans.txt pins their
+// decisions.  error != nullptr: the arguments are rejected with that message (path empty then).
+enum ConvFwdKernel { CONV_FWD_DS = 0, CONV_FWD_RES = 1, CONV_FWD_STREAM = 2 };
+struct ConvFwdPlan {
+  int kernel;                     // ConvFwdKernel
+  int variant;                    // res: conv3_res_plan's variant; stream: the tile configuration
+  int grid, smem;                 // workgroups (smem: ds / res; the streaming cfgs carry their own)
+  int stat_rows;                  // rows of the statistics slab (0 without statistics)
+  int fin_grid;                   // split-K finalize grid (a.ksplit > 1)
+  const char* error;
+  char path[48];                  // last_path() string
+};
+// a: geometry, channels, npix, the pointers' null-ness, groups and bnb_y filled in.  Tries the
+// depth-streaming, then the resident, then the streaming kernel's configurations; fills
+// TD..nTilesN, persist_blocks and ksplit
+ConvFwdPlan conv3_fwd_plan(ConvFwdArgs& a, int num_cus, bool want_stats);
 
 // ---------------------------------------------------------------- fused 32-channel backward
 // data + weight gradient of a 32 -> 32-channel 3x3 conv whose input is relu(bn1(Y)), from one
@@ -153,6 +171,18 @@ void conv3_wgrad_img_launch(ConvWgradArgs& a, int bco, hipStream_t st);
 int conv3_wgrad_img_pt(int bco);
 
 int conv3_wgrad_halo_cap(int dims);
+enum ConvWgradKernel { WGRAD_DS = 0, WGRAD_C32, WGRAD_IMG, WGRAD_V3, WGRAD_V2, WGRAD_V1 };
+struct ConvWgradPlan {
+  int kernel;                     // ConvWgradKernel
+  int bco;                        // output channels per workgroup (img / v3 / v2 / v1)
+  int grid;                       // ds / c32: workgroups (the others: from the tile counts)
+  const char* error;
+  char path[48];
+};
+// a: geometry, channels, the pointers' null-ness (X2, prologues, dyy, dyout) and groups filled
+// in; cin_real: the caller's count of real input channels (image layer), emit_dy: the formed
+// dY is stored (dyout).  Fills the tiles, ciw, coTiles, ciChunks, planes and splits
+ConvWgradPlan conv3_wgrad_plan(ConvWgradArgs& a, int num_cus, int cin_real, bool emit_dy);
 
 // ---------------------------------------------------------------- generic bf16 GEMM (convT)
 // C[M][N] = sum_k A(m, k) * B(n, k)   with k-contiguous operands ("NT"), used by the
@@ -194,6 +224,11 @@ int gemm_nt_bn(const GemmArgs& a);            // N tile of the forward / data-gr
 long long gemm_nt_grid(const GemmArgs& a);     // its workgroup count (= BN-partial rows)
 int convt_wgrad2_tiles(const GemmArgs& a);
 bool convt_wgrad2w_ok(const GemmArgs& a);      // shape constraints of the 256-column-tile kernel
+// the weight gradient's kernel and split count (a: mode, M, N, K, geometry, Cin, Cout, bn4):
+// sets a.wg2 and a.splits, returns the last_path() string
+const char* convt_wgrad_plan(GemmArgs& a, int num_cus);
+// shapes the fused 64 -> 64-channel backward covers (x / dOut: the tensors' sizes)
+bool convt_bwd_fused_ok(const int64_t* x, int xdim, const int64_t* dout, int ddim, int num_cus);
 // fused data + weight gradient of a 2-D 64 -> 64-channel transposed conv (convt_gemm.hip):
 // A = x [px][64], B = dOut, C = dx [px][64] (bf16), Wd2 = packed dgrad weights, partial =
 // [splits][64][256] weight-gradient slab, bn4/bnpart = deferred BN of x and its partial rows
@@ -356,6 +391,7 @@ void bn_grad_finalize_rows_launch(const float* partial, int P, int C, double cou
 void reduce_rows_scatter_launch(const float* in, int R, long long N, double* tmp, float* dst,
                                 int mode, int A, int T, int B, bool accumulate, hipStream_t st,
                                 long long ld = -1);
+long long reduce_rows_scatter_tmp(int R, long long N);   // doubles it needs in `tmp`
 void scatter_sums_launch(const double* sums, long long N, float* dst, int mode, int A, int T,
                          int B, float scale, bool accumulate, hipStream_t st);
 

@@ -331,6 +331,12 @@ void reduce_rows_scatter_launch(const float* in, int R, long long N, double* tmp
                      mode, A, T, B, accumulate ? 1 : 0, N);
 }
 
+// the caller's scratch for reduce_rows_scatter_launch: one fp64 row per RB-row chunk, read
+// only by the two-pass form above kWideMaxRows rows (0 below: tmp is never touched)
+long long reduce_rows_scatter_tmp(int R, long long N) {
+  return R > kWideMaxRows ? (long long)((R + RB - 1) / RB) * N : 0;
+}
+
 int reduce_rows_chunks(int R) { return (R + RB - 1) / RB; }
 
 // sums[N] (fp64) = sum over R rows of in[R][N]; tmp must hold reduce_rows_chunks(R) * N doubles

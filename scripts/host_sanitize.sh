@@ -8,7 +8,7 @@ out=${OUT:-build/host_sanitize}
 mkdir -p "$out"
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer"
 objs=()
-for f in csrc/conv3x3_res.hip csrc/conv3x3_fwd.hip csrc/conv3x3_wgrad.hip csrc/bn.hip csrc/reduce.hip csrc/head_ce.hip csrc/misc.hip csrc/convt_gemm.hip; do
+for f in csrc/conv3x3_res.hip csrc/conv3x3_fwd.hip csrc/conv3x3x3_ds.hip csrc/conv3x3_wgrad.hip csrc/conv3x3_wgrad_c32.hip csrc/conv3x3x3_wgrad_ds.hip csrc/bn.hip csrc/reduce.hip csrc/head_ce.hip csrc/misc.hip csrc/convt_gemm.hip; do
   o="$out/$(basename "$f" .hip).o"
   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g $SAN -Icsrc -c "$f" -o "$o" &
   objs+=("$o")
