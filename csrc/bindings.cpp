@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ops.h"
+#include "optim_math.h"
 
 namespace ddlpc {
 
@@ -1229,6 +1230,35 @@ void adam_step_dev(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v
               scal.data_ptr<float>());
 }
 
+// graph-capturable step with a learning-rate schedule, gradient-norm clipping and coupled or
+// decoupled weight decay (optim.hip): scal = device float[8] (the table of optim_math.h,
+// scal[0] = steps taken, advanced here), partial = device double[>= grad_sqnorm_blocks(n)]
+void adam_step_sched(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor scal,
+                     at::Tensor partial, double lr, double b1, double b2, double eps, double wd,
+                     bool decoupled, double max_norm, int64_t sched_kind, int64_t warmup,
+                     int64_t total, double lr_min, double power) {
+  check_adam_buffers(p, g, m, v);
+  CHECK_F32(scal);
+  TORCH_CHECK(scal.numel() == 8 && scal.is_contiguous() && scal.device() == p.device(),
+              "scal must be float[8] on p's device");
+  const long long n = p.numel();
+  TORCH_CHECK(partial.scalar_type() == at::kDouble && partial.is_contiguous() &&
+                  partial.device() == p.device() && partial.numel() >= grad_sqnorm_blocks(n),
+              "partial must be double[>= grad_sqnorm_blocks(n)] on p's device");
+  TORCH_CHECK(sched_kind >= 0 && sched_kind <= 2, "sched_kind: 0 constant, 1 poly, 2 cosine");
+  TORCH_CHECK(warmup >= 0 && total >= 0, "warmup and total must be >= 0");
+  c10::DeviceGuard guard(p.device());
+  SchedArgs a{lr, b1, b2, wd, max_norm, lr_min, power, warmup, total, (int)sched_kind,
+              decoupled ? 1 : 0};
+  const int nb = max_norm > 0.0 ? grad_sqnorm_blocks(n) : 0;
+  if (nb > 0) grad_sqnorm_launch(g.data_ptr<float>(), n, partial.data_ptr<double>(), cur_stream());
+  sched_scalars_launch(scal.data_ptr<float>(), partial.data_ptr<double>(), nb, a, cur_stream());
+  if (n == 0) return;                   // (the step counter advances, as in adam_step_dev)
+  adam_sched_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                    v.data_ptr<float>(), n, (float)b1, (float)b2, (float)eps, (float)wd, decoupled,
+                    scal.data_ptr<float>(), cur_stream());
+}
+
 void weight_pack(const at::Tensor& entries, int64_t n, int64_t max_elems) {
   CHECK_DEV(entries); CHECK_CONTIG(entries);
   TORCH_CHECK(entries.scalar_type() == at::kLong && n >= 0 && entries.numel() == n * 6,
@@ -1767,6 +1797,10 @@ TORCH_LIBRARY(ddlpc, m) {
         "float wd, float step_size, float inv_sqrt_bc2) -> ()");
   m.def("adam_step_dev(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) scal, "
         "float lr, float b1, float b2, float eps, float wd) -> ()");
+  // sched_kind: 0 constant, 1 poly, 2 cosine (the schedule of csrc/optim_math.h)
+  m.def("adam_step_sched(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) scal, "
+        "Tensor(e!) partial, float lr, float b1, float b2, float eps, float wd, bool decoupled, "
+        "float max_norm, int sched_kind, int warmup, int total, float lr_min, float power) -> ()");
   m.def("weight_pack(Tensor entries, int n, int max_elems) -> ()");
   m.def("codec_absmax(Tensor x, Tensor seg) -> Tensor");
   m.def("codec_encode(Tensor x, Tensor seg, Tensor scales, int codec) -> Tensor");
@@ -1821,6 +1855,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("head_logits", &ddlpc::head_logits);
   m.impl("adam_step", &ddlpc::adam_step);
   m.impl("adam_step_dev", &ddlpc::adam_step_dev);
+  m.impl("adam_step_sched", &ddlpc::adam_step_sched);
   m.impl("weight_pack", &ddlpc::weight_pack);
   m.impl("codec_absmax", &ddlpc::codec_absmax);
   m.impl("codec_encode", &ddlpc::codec_encode);

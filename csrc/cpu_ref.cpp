@@ -23,8 +23,11 @@
 #include <string>
 #include <vector>
 
+#include "optim_math.h"
+
 namespace ddlpc {
 void set_last_path(const std::string& path);    // bindings.cpp: torch.ops.ddlpc.last_path
+int grad_sqnorm_blocks(long long n);            // optim.hip: the norm's partial sums (planner)
 }
 
 namespace ddlpc_cpu {
@@ -775,6 +778,60 @@ void adam_step_dev(Tensor p, const Tensor& g, Tensor m, Tensor v, Tensor scal, d
   adam_math(p, g, m, v, b1, b2, eps, wd, s[1], s[2]);
 }
 
+// the scheduled step of csrc/optim.hip: the same partials (workgroup b owns the float4s of
+// index i with (i / 256) % nb == b, block 0 the tail; here each summed in index order, then
+// the partials in order), the scalars of optim_math.h and the update of adam_sched_kernel
+void adam_step_sched(Tensor p, const Tensor& g, Tensor m, Tensor v, Tensor scal, Tensor partial, double lr,
+                     double b1, double b2, double eps, double wd, bool decoupled, double max_norm,
+                     int64_t sched_kind, int64_t warmup, int64_t total, double lr_min, double power) {
+  for (const Tensor* t : std::array<const Tensor*, 4>{&p, &g, &m, &v})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == p.numel(),
+                "adam: p, g, m, v must be contiguous fp32 buffers of one size");
+  TORCH_CHECK(scal.scalar_type() == at::kFloat && scal.numel() == 8 && scal.is_contiguous(),
+              "scal must be float[8]");
+  const int64_t n = p.numel();
+  const int nblk = ddlpc::grad_sqnorm_blocks(n);
+  TORCH_CHECK(partial.scalar_type() == at::kDouble && partial.is_contiguous() && partial.numel() >= nblk,
+              "partial must be double[>= grad_sqnorm_blocks(n)]");
+  TORCH_CHECK(sched_kind >= 0 && sched_kind <= 2, "sched_kind: 0 constant, 1 poly, 2 cosine");
+  TORCH_CHECK(warmup >= 0 && total >= 0, "warmup and total must be >= 0");
+  const float* G = g.data_ptr<float>();
+  double sq = 0.0;
+  if (max_norm > 0.0 && nblk > 0) {
+    double* part = partial.data_ptr<double>();
+    for (int b = 0; b < nblk; ++b) part[b] = 0.0;
+    const int64_t n4 = n / 4;
+    for (int64_t i = 0; i < n4; ++i) {
+      double& acc = part[(i / 256) % nblk];
+      for (int j = 0; j < 4; ++j) acc += (double)G[4 * i + j] * (double)G[4 * i + j];
+    }
+    for (int64_t i = n4 * 4; i < n; ++i) part[0] += (double)G[i] * (double)G[i];
+    for (int b = 0; b < nblk; ++b) sq += part[b];
+  }
+  float* s = scal.data_ptr<float>();
+  const ddlpc::SchedArgs a{lr, b1, b2, wd, max_norm, lr_min, power, warmup, total, (int)sched_kind,
+                           decoupled ? 1 : 0};
+  ddlpc::sched_scalars(s, a, sq);
+  if (n == 0) return;
+  float* P = p.data_ptr<float>();
+  float* M = m.data_ptr<float>();
+  float* V = v.data_ptr<float>();
+  const float fb1 = (float)b1, fb2 = (float)b2, feps = (float)eps, fwd = (float)wd;
+  const float step_size = s[1], inv_sqrt_bc2 = s[2], coef = s[5], keep = 1.f - s[6];
+  at::parallel_for(0, n, 16384, [&](int64_t lo, int64_t hi) {
+#pragma clang fp contract(off)
+    for (int64_t i = lo; i < hi; ++i) {
+      const float gc = G[i] * coef;
+      float gr, p0 = P[i];
+      if (decoupled) { gr = gc; p0 = p0 * keep; }
+      else gr = fwd != 0.f ? gc + fwd * p0 : gc;
+      M[i] = M[i] + (1.f - fb1) * (gr - M[i]);
+      V[i] = fb2 * V[i] + (1.f - fb2) * gr * gr;
+      P[i] = p0 - step_size * M[i] / (std::sqrt(V[i]) * inv_sqrt_bc2 + feps);
+    }
+  });
+}
+
 // fp32 OIHW / IOHW parameters -> bf16 kernel layouts (see csrc/misc.hip weight_pack_kernel):
 // entries [n][6] = (src*, fwd*, dgrad* | 0, kind | Cout << 32, Cin | taps << 32, CinW | CoutW << 32)
 void weight_pack(const Tensor& entries, int64_t n, int64_t max_elems) {
@@ -1421,6 +1478,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("head_logits", &head_logits);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_dev", &adam_step_dev);
+  m.impl("adam_step_sched", &adam_step_sched);
   m.impl("weight_pack", &weight_pack);
   m.impl("codec_absmax", &codec_absmax);
   m.impl("codec_encode", &codec_encode);

@@ -344,6 +344,18 @@ void adam_launch(float* p, const float* g, float* m, float* v, long long n, floa
                  float eps, float wd, float step_size, float inv_sqrt_bc2, hipStream_t st,
                  const float* dscal = nullptr);
 void adam_scalars_launch(float* s, double lr, double b1, double b2, hipStream_t st);
+// the scheduled step (optim.hip): LR schedule, gradient-norm clipping, coupled / decoupled decay.
+// grad_sqnorm_blocks: torch-free planner, a function of n alone (workgroups = fp64 partials)
+int grad_sqnorm_blocks(long long n);
+void grad_sqnorm_launch(const float* g, long long n, double* partial, hipStream_t st);
+struct SchedArgs;                  // optim_math.h
+// scal float[8] = t, lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), lr_t, norm, coef, lr_t wd | 0, 0;
+// nb = partials to sum (0: clipping off, norm 0 and coef 1)
+void sched_scalars_launch(float* scal, const double* partial, int nb, const SchedArgs& a,
+                          hipStream_t st);
+void adam_sched_launch(float* p, const float* g, float* m, float* v, long long n, float b1,
+                       float b2, float eps, float wd, bool decoupled, const float* scal,
+                       hipStream_t st);
 struct PackEntry {                 // one conv weight to pack into bf16 kernel layouts
   const float* src;                // OIHW fp32  (or IOHW for transposed conv)
   bf16_t* fwd;                     // conv: [co][tap][CinW]; convT: [(sub, co)][Cin]

@@ -28,6 +28,7 @@ UP_MODES = ("conv_transpose", "bilinear")
 DATA_KINDS = ("synthetic", "vaihingen_dir", "scene_dir")
 AUGMENT_MODES = ("none", "flip", "d4")
 CLASS_WEIGHT_MODES = ("median_freq",)
+LR_SCHEDULES = ("constant", "poly", "cosine")
 
 
 def parse_class_weights(spec: Union[None, str, Sequence[float]], classes: int):
@@ -129,6 +130,16 @@ class TrainConfig:
     betas: tuple = (0.9, 0.999)
     eps: float = 1e-8
     weight_decay: float = 0.0
+    # schedule, clipping and AdamW, all on the device inside the optimizer step (ops/adam.py,
+    # csrc/optim.hip); every field at its default = plain Adam at a constant lr, as the reference
+    lr_schedule: str = "constant"        # constant | poly | cosine (after the warm-up)
+    lr_warmup_steps: int = 0             # linear warm-up: lr (s + 1) / W over the first W steps
+    lr_total_steps: int = 0              # the decay ends here; 0 = auto: max_steps, else epochs x
+                                         # optimizer steps per epoch
+    lr_min: float = 0.0                  # the decay's floor (held after lr_total_steps)
+    lr_poly_power: float = 0.9           # poly: (1 - u)^power
+    max_grad_norm: float = 0.0           # > 0: clip the global gradient norm (clip_grad_norm_)
+    decoupled_weight_decay: bool = False  # True = AdamW (p *= 1 - lr_t wd), False = L2 into g
     dtype: str = "bf16"                  # compute dtype on GPU (fp32 master weights); "fp32"
                                          # (the reference's precision) = stock ops, no autocast
     seed: int = 0
@@ -212,6 +223,15 @@ class TrainConfig:
             raise ValueError("accum_steps and batch_per_gpu must be >= 1")
         if self.crops_per_epoch < 0:
             raise ValueError("crops_per_epoch must be >= 0")
+        if self.lr_schedule not in LR_SCHEDULES:
+            raise ValueError(f"lr_schedule={self.lr_schedule!r} not in {LR_SCHEDULES}")
+        for name in ("lr_warmup_steps", "lr_total_steps", "lr_min", "max_grad_norm"):
+            if not getattr(self, name) >= 0:
+                raise ValueError(f"{name} must be >= 0")
+        if self.lr_min > self.lr:
+            raise ValueError("lr_min must not exceed lr")
+        if not self.lr_poly_power > 0:
+            raise ValueError("lr_poly_power must be > 0")
         for name in ("gain_jitter", "bias_jitter"):
             if not 0.0 <= getattr(self, name) <= 1.0:
                 raise ValueError(f"{name} must be in [0, 1]")
@@ -235,6 +255,12 @@ class TrainConfig:
             raise ValueError("scene_dir, crops_per_epoch, augment, the colour jitters, zoom and rotation "
                              "are 2-D only (model.dims == 2)")
         return self
+
+    @property
+    def scheduled(self) -> bool:
+        """The optimizer runs the scheduled step (a schedule, clipping or AdamW is set)."""
+        return self.lr_schedule != "constant" or self.lr_warmup_steps > 0 or self.lr_min != 0.0 or \
+            self.max_grad_norm > 0.0 or self.decoupled_weight_decay
 
     @property
     def augmented(self) -> bool:

@@ -26,9 +26,66 @@ import torch
 from . import _ext
 
 
+LR_SCHEDULES = ("constant", "poly", "cosine")       # sched_kind of adam_step_sched: the index
+
+
+def grad_sqnorm_blocks(n: int) -> int:
+    """Python twin of ``grad_sqnorm_blocks`` (csrc/optim.hip): the fp64 partial sums of the
+    gradient norm, a function of ``n`` alone (``adam_step_sched`` refuses a shorter buffer)."""
+    return 0 if n <= 0 else min(max((n // 4 + 255) // 256, 1), 1024)
+
+
+def schedule_lr(t: int, lr: float, schedule: str = "constant", warmup: int = 0, total: int = 0,
+                lr_min: float = 0.0, power: float = 0.9) -> float:
+    """The learning rate of optimizer step ``t`` (1-based): the Python-double twin of ``sched_lr``
+    (csrc/optim_math.h), operation for operation.  With ``s = t - 1`` steps taken: ``lr (s + 1) /
+    warmup`` while ``s < warmup``; then ``u = clamp((s - warmup) / max(1, total - warmup), 0, 1)``
+    and ``lr_min + (lr - lr_min) f(u)``, ``f`` = 1 (constant), ``(1 - u)^power`` (poly) or
+    ``0.5 (1 + cos(pi u))`` (cosine); poly and cosine stay at ``lr_min`` after step ``total``."""
+    s, W, T = float(t - 1), float(warmup), float(total)
+    if s < W:
+        return lr * (s + 1.0) / W
+    u = min(max((s - W) / max(1.0, T - W), 0.0), 1.0)
+    f = 1.0
+    if schedule == "poly":
+        f = 1.0 - u if power == 1.0 else (1.0 - u) ** power
+    elif schedule == "cosine":
+        f = 0.5 * (1.0 + math.cos(math.pi * u))
+    if schedule != "constant" and u >= 1.0:
+        f = 0.0
+    return lr_min + (lr - lr_min) * f
+
+
 class FlatAdam(torch.optim.Optimizer):
+    """Flat Adam / AdamW.  With every scheduling argument at its default, ``step()`` is the plain
+    Adam of ``adam_step_dev`` / ``adam_step``.  Otherwise it is ``adam_step_sched``
+    (csrc/optim.hip, CPU twin in csrc/cpu_ref.cpp), all on the device and capturable:
+
+    * ``lr_schedule`` ``constant | poly | cosine`` with ``warmup_steps`` of linear warm-up,
+      ``total_steps``, ``lr_min`` and ``poly_power`` (``lr_at`` is the formula);
+    * ``max_grad_norm > 0``: the flat gradient is scaled by ``min(max_norm / (norm + 1e-6), 1)``
+      (``torch.nn.utils.clip_grad_norm_``) inside the update; the gradient buffer is not written;
+    * ``decoupled=True``: ``p *= 1 - lr_t * weight_decay`` before the update (``torch.optim.AdamW``)
+      in place of ``g += weight_decay * p``.
+
+    A NaN / Inf gradient norm is not skipped: it propagates into every parameter, as in PyTorch.
+    The schedule is a function of the step count alone, which ``load_state_dict`` restores, so a
+    resumed run continues it; nothing else goes into the optimizer state."""
+
     def __init__(self, flat, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, use_hip: Optional[bool] = None):
+                 weight_decay: float = 0.0, use_hip: Optional[bool] = None, *,
+                 decoupled: bool = False, max_grad_norm: float = 0.0,
+                 lr_schedule: str = "constant", warmup_steps: int = 0, total_steps: int = 0,
+                 lr_min: float = 0.0, poly_power: float = 0.9):
+        if lr_schedule not in LR_SCHEDULES:
+            raise ValueError(f"lr_schedule={lr_schedule!r} not in {LR_SCHEDULES}")
+        if warmup_steps < 0 or total_steps < 0 or lr_min < 0 or max_grad_norm < 0:
+            raise ValueError("warmup_steps, total_steps, lr_min and max_grad_norm must be >= 0")
+        if lr_min > lr:
+            raise ValueError("lr_min must not exceed lr")
+        if poly_power <= 0:
+            raise ValueError("poly_power must be > 0")
+        # (total_steps may be set after construction — the Trainer derives it from its sampler)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
                         amsgrad=False, maximize=False, foreach=None, capturable=False,
                         differentiable=False, fused=None)
@@ -42,7 +99,21 @@ class FlatAdam(torch.optim.Optimizer):
         self.weight_pack = None          # set by ops.fused_unet (bf16 conv-weight copies)
         self._dev_scal = None            # device [t, step_size, inv_sqrt_bc2] (hipGraph mode)
         self._use_hip = (dev.type == "cuda") if use_hip is None else use_hip
-        if self._use_hip:
+        self.decoupled, self.max_grad_norm = bool(decoupled), float(max_grad_norm)
+        self.lr_schedule, self.warmup_steps = lr_schedule, int(warmup_steps)
+        self.total_steps, self.lr_min, self.poly_power = int(total_steps), float(lr_min), float(poly_power)
+        # any scheduling argument off its default: the adam_step_sched path on either device
+        self.scheduled = bool(self.decoupled or self.max_grad_norm > 0 or lr_schedule != "constant"
+                              or self.warmup_steps or self.total_steps or self.lr_min
+                              or self.poly_power != 0.9)
+        self._partial = None
+        if self.scheduled:
+            _ext.ops()                   # both devices run the kernel library's operator
+            # the float[8] table of csrc/optim_math.h; [0] = steps taken (what _dev_scal[0] is)
+            self._dev_scal = torch.zeros(8, dtype=torch.float32, device=dev)
+            self._partial = torch.zeros(grad_sqnorm_blocks(flat.param_buf.numel()),
+                                        dtype=torch.float64, device=dev)
+        elif self._use_hip:
             _ext.ops()                   # fail loudly if the kernel library is missing
             # bias corrections on the device: identical arithmetic for eager and hipGraph
             # steps, and nothing step-dependent is baked into a captured graph
@@ -61,6 +132,8 @@ class FlatAdam(torch.optim.Optimizer):
         replays correctly: no host scalar is baked into the graph."""
         if not self._use_hip:
             raise RuntimeError("device-side Adam scalars need the HIP kernel library")
+        if self.scheduled:
+            return                       # (the scheduled step keeps all its scalars on the device)
         self._dev_scal = torch.tensor([float(self.step_count), 0.0, 0.0],
                                       dtype=torch.float32, device=self.flat.param_buf.device)
 
@@ -78,6 +151,15 @@ class FlatAdam(torch.optim.Optimizer):
         lr, (b1, b2), eps, wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
         self.step_count += 1
         P, G = self.flat.param_buf, self.flat.grad_buf
+        if self.scheduled:
+            _ext.ops().adam_step_sched(P, G, self.exp_avg, self.exp_avg_sq, self._dev_scal,
+                                       self._partial, float(lr), float(b1), float(b2), float(eps),
+                                       float(wd), self.decoupled, self.max_grad_norm,
+                                       LR_SCHEDULES.index(self.lr_schedule), self.warmup_steps,
+                                       self.total_steps, self.lr_min, self.poly_power)
+            if self.weight_pack is not None:
+                self.weight_pack()
+            return loss
         if self._dev_scal is not None:
             _ext.ops().adam_step_dev(P, G, self.exp_avg, self.exp_avg_sq, self._dev_scal,
                                      float(lr), float(b1), float(b2), float(eps), float(wd))
@@ -101,6 +183,19 @@ class FlatAdam(torch.optim.Optimizer):
             denom = (self.exp_avg_sq.sqrt() * inv_sqrt_bc2).add_(eps)
             P.addcdiv_(self.exp_avg, denom, value=-step_size)
         return loss
+
+    def lr_at(self, t: int) -> float:
+        """The learning rate of optimizer step ``t`` (1-based), as the device computes it."""
+        return schedule_lr(t, float(self.param_groups[0]["lr"]), self.lr_schedule, self.warmup_steps,
+                           self.total_steps, self.lr_min, self.poly_power)
+
+    def last_stats(self):
+        """``{lr, grad_norm, clip_coef}`` of the last scheduled step, read from the device table
+        (synchronises; ``grad_norm`` is 0 with clipping off)."""
+        if not self.scheduled:
+            raise RuntimeError("last_stats: no schedule, clipping or decoupled decay is configured")
+        s = self._dev_scal.tolist()
+        return {"lr": s[3], "grad_norm": s[4], "clip_coef": s[5]}
 
     def _sync_steps(self):
         for p in self.flat.params:

@@ -78,7 +78,7 @@ class Trainer:
             model._engine.recompute = int(cfg.recompute)
         self.optimizer = FlatAdam(self.flat, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps,
                                   weight_decay=cfg.weight_decay,
-                                  use_hip=(self.impl == "hip"))
+                                  use_hip=(self.impl == "hip"), **self._schedule_args())
         if self.impl == "hip":
             self.optimizer.weight_pack = model._engine.pack_weights
         # optional CU reservation for collectives (persistent grids sized to num_cus - k).
@@ -144,6 +144,7 @@ class Trainer:
             self.logger.log({"class_weights": [float(v) for v in self.class_weight.tolist()]})
         self.sampler = ShardedSampler(len(self.train_set), self.rank, self.world,
                                       shard=cfg.shard_data, shuffle=cfg.shuffle, seed=cfg.seed)
+        self._resolve_total_steps()
         if cfg.resume:
             path = latest_checkpoint(cfg.ckpt_dir) if cfg.resume == "auto" else cfg.resume
             exists = bool(path) and os.path.exists(path)
@@ -242,6 +243,28 @@ class Trainer:
         if self.impl == "hip":
             self.model._engine.enable_direct_grads(self.reducer.mark_ready)
         return len(self.reducer.buckets)
+
+    def _schedule_args(self) -> dict:
+        """FlatAdam's scheduling arguments; empty (plain Adam, today's launches) when no
+        schedule, clipping or decoupled decay is configured."""
+        c = self.cfg
+        if not c.scheduled:
+            return {}
+        return dict(decoupled=c.decoupled_weight_decay, max_grad_norm=c.max_grad_norm,
+                    lr_schedule=c.lr_schedule, warmup_steps=c.lr_warmup_steps,
+                    total_steps=c.lr_total_steps, lr_min=c.lr_min, poly_power=c.lr_poly_power)
+
+    def _resolve_total_steps(self):
+        """lr_total_steps = 0: max_steps, else epochs x optimizer steps per epoch (known once
+        the sampler is)."""
+        c, opt = self.cfg, self.optimizer
+        if not opt.scheduled or c.lr_total_steps > 0:
+            return
+        per_epoch = len(list(self.sampler.batches(c.batch_per_gpu))) // c.accum_steps
+        opt.total_steps = int(c.max_steps or c.epochs * per_epoch)
+        if opt.lr_schedule != "constant" and opt.total_steps <= opt.warmup_steps:
+            raise ValueError(f"lr_schedule={opt.lr_schedule!r}: {opt.total_steps} total steps do not "
+                             f"exceed lr_warmup_steps={opt.warmup_steps}")
 
     def _broadcast_state(self):
         """Rank 0's parameters, buffers, Adam moments and step counters -> every rank."""
@@ -870,6 +893,8 @@ class Trainer:
                            "elapsed_s": now - t_start}
                     if self.phases is not None:
                         rec.update(self.phases.read())
+                    if self.optimizer.scheduled:
+                        rec.update(self.optimizer.last_stats())
                     log_t, log_step = now, self.step_count
                     self.logger.log(rec)
                 if c.ckpt_dir and c.ckpt_every and self.step_count % c.ckpt_every == 0:
