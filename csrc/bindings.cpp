@@ -156,6 +156,9 @@ int num_cus() { return std::max(8, phys_cus() - g_cu_reserve); }
 
 // fp64 column sums of an fp32 [R][N] partial slab (deterministic two-pass reduction)
 at::Tensor reduce_rows(const at::Tensor& partial, int64_t R, int64_t N) {
+  // reduce_rows_launch's multi-level loop has one scratch region for its intermediate passes:
+  // above 64^3 rows a second intermediate pass would read and write it at once
+  TORCH_CHECK(R >= 0 && R <= 262144, "reduce_rows: at most 262144 rows");
   auto dopts = partial.options().dtype(at::kDouble);
   at::Tensor sums = at::empty({N}, dopts);
   const int RC = reduce_rows_chunks((int)R);
@@ -172,6 +175,32 @@ void sum_slab(const at::Tensor& slab, int R, long long N, at::Tensor& dst, int m
   at::Tensor tmp = at::empty({(int64_t)reduce_rows_scatter_tmp(R, N)}, slab.options().dtype(at::kDouble));
   reduce_rows_scatter_launch(slab.data_ptr<float>(), R, N, tmp.data_ptr<double>(), dst.data_ptr<float>(),
                              mode, A, T, B, accumulate, cur_stream(), ld);
+}
+
+// sum_slab as an operator (the exact tests of the gradient tail drive every row-count regime
+// and layout mode of reduce_rows_scatter_launch through it; the operators call sum_slab).
+// Rows of N columns at a row stride of ld floats (-1: N); mode 0 / 1: N = A * T * B with
+// A = N / (T * B)
+void reduce_rows_scatter(const at::Tensor& slab, int64_t R, int64_t N, at::Tensor& dst, int64_t mode,
+                         int64_t T, int64_t B, bool accumulate, int64_t ld) {
+  CHECK_DEV(slab); CHECK_F32(slab); CHECK_CONTIG(slab);
+  CHECK_F32(dst); CHECK_CONTIG(dst);
+  TORCH_CHECK(slab.device() == dst.device(), "reduce_rows_scatter: slab and dst on different devices");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "reduce_rows_scatter: mode must be 0, 1 or 2");
+  TORCH_CHECK(R >= 0 && R <= INT32_MAX && N >= 0, "reduce_rows_scatter: bad R / N");
+  TORCH_CHECK(ld == -1 || ld >= N, "reduce_rows_scatter: ld must be -1 or at least N");
+  TORCH_CHECK(dst.numel() == N, "reduce_rows_scatter: dst must hold exactly N elements");
+  int64_t A = 0;
+  if (mode != 2) {
+    TORCH_CHECK(T > 0 && B > 0 && T <= INT32_MAX && B <= INT32_MAX && N % (T * B) == 0,
+                "reduce_rows_scatter: N must be A * T * B");
+    A = N / (T * B);
+  }
+  if (R == 0 || N == 0) return;
+  const int64_t stride = ld < 0 ? N : ld;
+  TORCH_CHECK(slab.numel() >= (R - 1) * stride + N, "reduce_rows_scatter: slab shorter than (R - 1) * ld + N");
+  c10::DeviceGuard guard(slab.device());
+  sum_slab(slab, (int)R, N, dst, (int)mode, (int)A, (int)T, (int)B, accumulate, ld);
 }
 
 // BatchNorm-backward coefficients [k|m1|m2] x C and dgamma / dbeta (accumulated into the outs
@@ -1754,6 +1783,8 @@ TORCH_LIBRARY(ddlpc, m) {
         "Tensor? dy_coefs=None, int cin_real=0, int groups=0, Tensor(b!)? dy_out=None) -> Tensor");
   m.def("conv3_bwd32(Tensor dy, Tensor y, Tensor s4, Tensor wd, Tensor(a!)? dw_out=None, int groups=0) -> Tensor[]");
   m.def("reduce_rows(Tensor partial, int R, int N) -> Tensor");
+  m.def("reduce_rows_scatter(Tensor slab, int R, int N, Tensor(a!) dst, int mode, int T, int B, "
+        "bool accumulate, int ld=-1) -> ()");
   m.def("bn_finalize(Tensor partial, float count, Tensor gamma, Tensor beta, Tensor(a!) running_mean, "
         "Tensor(b!) running_var, float momentum, float eps, bool update_running, Tensor(c!)? nbt) -> Tensor");
   m.def("bn_relu_apply(Tensor y, Tensor stats4, bool pool, bool full=True) -> Tensor[]");
@@ -1831,6 +1862,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("conv3_wgrad", &ddlpc::conv3_wgrad);
   m.impl("bn_finalize", &ddlpc::bn_finalize);
   m.impl("reduce_rows", &ddlpc::reduce_rows);
+  m.impl("reduce_rows_scatter", &ddlpc::reduce_rows_scatter);
   m.impl("bn_relu_apply", &ddlpc::bn_relu_apply);
   m.impl("bn_running_apply", &ddlpc::bn_running_apply);
   m.impl("bn_grad_coefs", &ddlpc::bn_grad_coefs);

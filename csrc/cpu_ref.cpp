@@ -302,6 +302,51 @@ Tensor reduce_rows(const Tensor& partial, int64_t R, int64_t N) {
   return partial.reshape({R, N}).to(at::kDouble).sum(0);
 }
 
+// dst[perm(j)] (+)= float(fp64 sum over R rows of slab[r * ld + j]): the three row-count
+// regimes of reduce_rows_scatter_launch (csrc/reduce.hip) in their summation orders, and its
+// layouts: mode 0 [co][tap][ci] -> [co][ci][tap], mode 1 [ci][(sub, co)] -> [ci][co][sub],
+// mode 2 identity
+void reduce_rows_scatter(const Tensor& slab, int64_t R, int64_t N, Tensor& dst, int64_t mode, int64_t T,
+                         int64_t B, bool accumulate, int64_t ld) {
+  TORCH_CHECK(slab.scalar_type() == at::kFloat && slab.is_contiguous(), "slab must be contiguous fp32");
+  TORCH_CHECK(dst.scalar_type() == at::kFloat && dst.is_contiguous() && dst.numel() == N,
+              "dst must be N contiguous fp32 elements");
+  TORCH_CHECK(mode >= 0 && mode <= 2 && R >= 0 && N >= 0 && (ld == -1 || ld >= N), "bad mode / R / N / ld");
+  TORCH_CHECK(mode == 2 || (T > 0 && B > 0 && N % (T * B) == 0), "N must be A * T * B");
+  if (R == 0 || N == 0) return;
+  if (ld < 0) ld = N;
+  TORCH_CHECK(slab.numel() >= (R - 1) * ld + N, "slab shorter than (R - 1) * ld + N");
+  const float* in = slab.data_ptr<float>();
+  float* out = dst.data_ptr<float>();
+  for (int64_t j = 0; j < N; ++j) {
+    double s = 0.0;
+    if (R <= 64) {                         // one pass
+      for (int64_t r = 0; r < R; ++r) s += (double)in[r * ld + j];
+    } else if (R <= 1024) {                // wide: four interleaved row sets, added in order
+      double w[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int64_t k = 0; k < 4; ++k)
+        for (int64_t r = k; r < R; r += 4) w[k] += (double)in[r * ld + j];
+      for (int64_t k = 0; k < 4; ++k) s += w[k];
+    } else {                               // two passes: chunks of 64 rows, then the chunk sums
+      for (int64_t r0 = 0; r0 < R; r0 += 64) {
+        double c = 0.0;
+        for (int64_t r = r0; r < std::min(R, r0 + 64); ++r) c += (double)in[r * ld + j];
+        s += c;
+      }
+    }
+    int64_t d = j;
+    if (mode == 0) {                       // T = taps, B = Cin ; j = (co*T + tap)*B + ci
+      const int64_t ci = j % B, tap = (j / B) % T, co = j / (B * T);
+      d = (co * B + ci) * T + tap;
+    } else if (mode == 1) {                // T = subs, B = Cout ; j = ci*(T*B) + sub*B + co
+      const int64_t co = j % B, sub = (j / B) % T, ci = j / (B * T);
+      d = (ci * B + co) * T + sub;
+    }
+    const float v = (float)s;
+    out[d] = accumulate ? out[d] + v : v;
+  }
+}
+
 // ------------------------------------------------------------------------ BatchNorm
 float mom_update(float running, float x, float m) { return m * x + (1.f - m) * running; }
 
@@ -1454,6 +1499,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("conv3_wgrad", &conv3_wgrad);
   m.impl("conv3_bwd32", &conv3_bwd32);
   m.impl("reduce_rows", &reduce_rows);
+  m.impl("reduce_rows_scatter", &reduce_rows_scatter);
   m.impl("bn_finalize", &bn_finalize);
   m.impl("bn_relu_apply", &bn_relu_apply);
   m.impl("bn_running_apply", &bn_running_apply);

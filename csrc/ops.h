@@ -30,8 +30,10 @@ struct ConvFwdArgs {
   bf16_t* Y2;
   float* stats;                   // optional [grid][2][Cout] per-workgroup (sum, sum^2) of the fp32
                                   // outputs (before the bf16 store: the statistics an fp32
-                                  // BatchNorm would see); rows of channels outside a
-                                  // workgroup's n tile are not written.  (The resident
+                                  // BatchNorm would see); every workgroup writes its full
+                                  // row, zeros for the channels outside its n tile, so the
+                                  // slab needs no zero fill and every row can be summed
+                                  // (bn_finalize, colsum_rows).  (The resident
                                   // 96-channel variant — the concat data gradient: one input,
                                   // no prologue, no bias — writes sum^2 rows of zeros: its
                                   // sums are the up-conv's bias gradient)

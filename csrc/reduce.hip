@@ -356,7 +356,10 @@ void reduce_rows_launch(const float* in, int R, long long N, double* tmp, double
   hipLaunchKernelGGL(rows_chunk_sum_kernel<float>, dim3(gx, RC), dim3(256), 0, st, in, R, N, tmp, -1LL);
   int R2 = RC;
   const double* cur = tmp;
-  while (reduce_rows_chunks(R2) > 1) {       // (only for > 4096 rows)
+  // (only for > 4096 rows; at most ONE trip: every trip writes the same second half of tmp, so
+  // a second one, R > 64^3 = 262144 rows, would read and write it at once from different
+  // workgroups — the reduce_rows binding refuses such a row count)
+  while (reduce_rows_chunks(R2) > 1) {
     const int RC2 = reduce_rows_chunks(R2);
     double* nxt = tmp + (long long)RC * N;   // second half of tmp is free scratch
     hipLaunchKernelGGL(rows_chunk_sum_kernel<double>, dim3(gx, RC2), dim3(256), 0, st, cur, R2, N, nxt, -1LL);
