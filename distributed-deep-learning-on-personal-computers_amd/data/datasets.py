@@ -132,6 +132,20 @@ def cat_adjacent(ts: List[torch.Tensor]) -> torch.Tensor:
     return out
 
 
+def join_batches(mbs: List[Tuple[torch.Tensor, torch.Tensor]]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Equal-shaped micro-batches as one batch (engine-layout inputs stay in that layout);
+    the back-to-back views ``split_batch`` hands out are joined without a copy."""
+    shapes = {(tuple(x.shape), tuple(y.shape)) for x, y in mbs}
+    if len(shapes) != 1:
+        raise ValueError(f"batched BN window: micro-batches of unequal shapes {sorted(shapes)}")
+    xps = [getattr(x, "_ddlpc_nhwc", None) for x, _ in mbs]
+    if all(xp is not None for xp in xps):
+        x = engine_input(cat_adjacent(xps), mbs[0][0].shape[1])
+    else:
+        x = cat_adjacent([x for x, _ in mbs])
+    return x, cat_adjacent([y for _, y in mbs])
+
+
 class DevicePrefetcher:
     """Device-side input pipeline: ``get(k)`` returns batch k (``make(k)``) and starts
     rendering batch k + 1 on a side HIP stream, so the generator / gather kernels of the next
@@ -303,11 +317,6 @@ class SyntheticTiles:
 
     def __len__(self):
         return self.length
-
-    @property
-    def on_device(self) -> bool:
-        """Batches are rendered by a device kernel (``Trainer.fit`` prefetches them)."""
-        return self.device.type == "cuda"
 
     def get(self, idx) -> Tuple[torch.Tensor, torch.Tensor]:
         if self.layout == "engine":

@@ -404,10 +404,6 @@ class SceneCropDataset:
         return self
 
     @property
-    def on_device(self) -> bool:
-        return self.device.type == "cuda"
-
-    @property
     def resident(self) -> bool:
         return True
 

@@ -21,6 +21,7 @@ every rank applies identical gradients — with the MI355X machinery underneath:
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 import time
 from typing import Dict, List, Optional, Tuple
@@ -30,7 +31,7 @@ import torch
 import torch.distributed as dist
 
 from ..config import TrainConfig, median_freq_weights, parse_class_weights
-from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset
+from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset, join_batches
 from ..models.unet import UNet
 from ..ops import _ext
 from ..ops.adam import FlatAdam
@@ -38,6 +39,7 @@ from ..parallel import (GradBucketReducer, assert_replicas_identical, broadcast_
                         broadcast_module, broadcast_tensors, flatten_module, init_distributed)
 from ..utils.metrics import DeviceMeter, RunLogger, dump_pngs
 from ..utils.tracing import PhaseTimer, StepProfiler, enable_ranges, trace_range
+from .capture import CapturedMicro, StaticInputs, capture_graph, on_fresh_stream
 from .checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 
 
@@ -121,14 +123,13 @@ class Trainer:
         self._mstreams: List[torch.cuda.Stream] = []     # concurrent micro-batch streams
         self.ms_graph = True                               # ... each replaying its own graph
         self._ms_meters: List[DeviceMeter] = []
-        self._ms_graphs, self._ms_warm, self._ms_static = [], [], []
+        self._ms_captured: List[CapturedMicro] = []        # (own static inputs per stream)
         self.ms_host_s = 0.0
         self._mbufs: List[torch.Tensor] = []               # their extra gradient buffers
         self._mviews: List[list] = []
         self._flat_views = None
-        self._graphs: Dict[str, "torch.cuda.CUDAGraph"] = {}   # hipGraphs (cfg.hip_graph)
-        self._graph_warm: Dict[str, int] = {}
-        self._static = None
+        self._captured: Dict[str, CapturedMicro] = {}      # "acc" / "last" (cfg.hip_graph) ...
+        self._static = StaticInputs()                      # ... over one shared pair of inputs
         self.epoch = 0
         self.epoch_step = 0              # optimizer steps done in the current epoch
         self._train_label_counts = None
@@ -222,10 +223,7 @@ class Trainer:
                                world, gbps, lat_us, c.bucket_mb * (1 << 20) * wire / 4.0)
         plan.calibrated = True
         self.bucket_plan = plan
-        r.remove_hooks()
-        self.reducer = self._make_reducer(c.bucket_mb, cuts=plan.cuts)
-        if self.impl == "hip":
-            self.model._engine.enable_direct_grads(self.reducer.mark_ready)
+        self._swap_reducer(c.bucket_mb, cuts=plan.cuts)
         return {"backward_ms": round(bwd_ms, 3), "buckets": len(plan.cuts) - 1,
                 "bucket_mb": [round(sum(nbytes[a:b]) / 2**20, 2)
                               for a, b in zip(plan.cuts[:-1], plan.cuts[1:])],
@@ -237,12 +235,19 @@ class Trainer:
         returns the number of buckets."""
         if self.reducer is None:
             return 0
-        self.reducer.remove_hooks()
         self.cfg.bucket_mb = bucket_mb
-        self.reducer = self._make_reducer(bucket_mb)
+        self._swap_reducer(bucket_mb)
+        return len(self.reducer.buckets)
+
+    def _swap_reducer(self, bucket_mb: float, cuts: Optional[List[int]] = None):
+        """Replace the reducer between steps.  Captured micro-batches stay: they run with the
+        reducer disarmed (``prepare(sync=False)`` is called on the host around them, never
+        inside), so they hold no reducer work, and a re-capture would land in whatever the
+        caller times next."""
+        self.reducer.remove_hooks()
+        self.reducer = self._make_reducer(bucket_mb, cuts=cuts)
         if self.impl == "hip":
             self.model._engine.enable_direct_grads(self.reducer.mark_ready)
-        return len(self.reducer.buckets)
 
     def _schedule_args(self) -> dict:
         """FlatAdam's scheduling arguments; empty (plain Adam, today's launches) when no
@@ -354,17 +359,31 @@ class Trainer:
         return x, y
 
     # ------------------------------------------------------------------ step
-    def _micro(self, x, y, sync: bool):
-        if self.reducer is not None:
-            self.reducer.prepare(sync=sync)
+    def _fwd_bwd(self, x, y, meter: DeviceMeter, groups: int = 1, before_backward=None):
+        """Every schedule's micro-batch body, eager or captured: forward, backward, ``meter``.
+        ``groups`` > 1: a window pass of that many micro-batches (its loss is their mean, so
+        the gradient is scaled back to their sum).  No reducer call in here (a replay would
+        skip it): the caller arms the reducer (``_arm``) and passes ``before_backward``."""
         ctx = (torch.autocast("cuda", dtype=torch.bfloat16) if self.autocast
                else contextlib.nullcontext())
         with ctx:
             loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
-        if sync and self.reducer is not None:
-            self.reducer.mark_backward_start()
-        loss.backward()
-        self.meter.add(loss, correct, y.numel())
+        if before_backward is not None:
+            before_backward()
+        (loss * float(groups) if groups > 1 else loss).backward()
+        meter.add(loss, correct, y.numel(), n=groups)
+        return loss
+
+    def _arm(self, sync: bool):
+        """Arm (``sync``: the window's last backward launches the bucket collectives) or
+        disarm the reducer for the next micro-batch -> the ``before_backward`` of its body."""
+        if self.reducer is None:
+            return None
+        self.reducer.prepare(sync=sync)
+        return self.reducer.mark_backward_start if sync else None
+
+    def _micro(self, x, y, sync: bool):
+        loss = self._fwd_bwd(x, y, self.meter, before_backward=self._arm(sync))
         self.micro_count += 1
         return loss
 
@@ -394,54 +413,6 @@ class Trainer:
         f = self.flat
         return [FlatParams._view(buf, f.offsets[id(p)], p) for p in f.order]
 
-    def _ms_streams(self, K: int, cur) -> List[torch.cuda.Stream]:
-        """K plain HIP micro-batch streams.  (CU-masked streams, one chip slice each, were
-        measured 2-3x slower than plain ones: 171 vs 515 images/s at K = 4, docs/PERF.md.)"""
-        if len(self._mstreams) != K:
-            self._mstreams = [torch.cuda.Stream(self.device) for _ in range(K)]
-            self._ms_graphs, self._ms_warm, self._ms_static = [None] * K, [0] * K, [None] * K
-        return self._mstreams
-
-    def _ms_buffers(self, K: int):
-        while len(self._mbufs) < K - 1:
-            self._mbufs.append(torch.zeros_like(self.flat.grad_buf))
-            self._mviews.append(self._grad_views(self._mbufs[-1]))
-        if self._flat_views is None:
-            self._flat_views = self._grad_views(self.flat.grad_buf)
-        while len(self._ms_meters) < K:
-            self._ms_meters.append(DeviceMeter(self.device))
-        return [self._flat_views] + self._mviews[:K - 1]
-
-    def _ms_enter(self, K: int):
-        """Per-window setup: the weight-gradient side stream off (returns its state)."""
-        eng = self.model._engine
-        state = eng.side is not None
-        eng.set_side_stream(False)
-        return state
-
-    def _ms_exit(self, state):
-        eng = self.model._engine
-        eng.bn_defer_j = None
-        for p, g in zip(self.flat.order, self._flat_views):
-            p.grad = g
-        eng.set_side_stream(state)
-
-    def _ms_finish(self, K: int, n: int):
-        """After the streams joined: extra gradient buffers into the flat one (stream
-        order), per-stream meters into the trainer's."""
-        for b in self._mbufs[:K - 1]:
-            self.flat.grad_buf.add_(b)
-            b.zero_()
-        for m in self._ms_meters[:K]:
-            self.meter.buf += m.buf
-            m.buf.zero_()
-        self.micro_count += n
-
-    def _ms_body(self, k: int, x, y):
-        loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
-        loss.backward()
-        self._ms_meters[k].add(loss, correct, y.numel())
-
     def _concurrent_micros(self, mbs: List[Tuple[torch.Tensor, torch.Tensor]]):
         """Accumulation micro-batches on ``micro_streams`` HIP streams at once.
 
@@ -467,18 +438,30 @@ class Trainer:
         the same weights as in the one-by-one loop.  The final micro-batch of the window
         runs on the caller's stream as usual (it triggers the gradient exchange)."""
         eng = self.model._engine
-        if self.reducer is not None:
-            # accumulation micro-batches: no collective (the readiness callbacks of their
-            # backwards must not launch bucket all-reduces on a partial gradient)
-            self.reducer.prepare(sync=False)
+        # accumulation micro-batches: no collective (the readiness callbacks of their
+        # backwards must not launch bucket all-reduces on a partial gradient)
+        self._arm(sync=False)
         K = self.micro_streams
         cur = torch.cuda.current_stream(self.device)
-        streams = self._ms_streams(K, cur)
-        views = self._ms_buffers(K)
-        # per-stream graphs by default: without them the host's ~230 launches per
-        # micro-batch become the limit once the streams overlap (ms_graph = False: eager)
-        use_graph = self.ms_graph
-        state = self._ms_enter(K)
+        while len(self._mbufs) < K - 1:
+            self._mbufs.append(torch.zeros_like(self.flat.grad_buf))
+            self._mviews.append(self._grad_views(self._mbufs[-1]))
+        if self._flat_views is None:
+            self._flat_views = self._grad_views(self.flat.grad_buf)
+        while len(self._ms_meters) < K:
+            self._ms_meters.append(DeviceMeter(self.device))
+        if len(self._mstreams) != K:
+            # K plain HIP streams (CU-masked streams, one chip slice each, were measured 2-3x
+            # slower than plain ones: 171 vs 515 images/s at K = 4, docs/PERF.md), each with
+            # its own captured micro-batch: warmed up and captured on the stream itself
+            self._mstreams = [torch.cuda.Stream(self.device) for _ in range(K)]
+            self._ms_captured = [
+                CapturedMicro(StaticInputs(), functools.partial(self._fwd_bwd, meter=m),
+                              self.GRAPH_WARMUP, capture=functools.partial(capture_graph, stream=st))
+                for st, m in zip(self._mstreams, self._ms_meters)]
+        streams, views = self._mstreams, [self._flat_views] + self._mviews[:K - 1]
+        side = eng.side is not None
+        eng.set_side_stream(False)                 # the weight-gradient side stream off
         eng.bn_defer_prepare(K, len(mbs))
         order = self.flat.order
         t_host = time.perf_counter()
@@ -492,159 +475,74 @@ class Trainer:
                     p.grad = g
                 eng.bn_defer_j = k
                 with torch.cuda.stream(st):
-                    if use_graph:
-                        self._ms_graph_micro(k, st, x, y)
+                    # per-stream graphs by default (the batch is staged on stream k): without
+                    # them the host's ~230 launches per micro-batch become the limit once
+                    # the streams overlap (ms_graph = False: eager)
+                    if self.ms_graph:
+                        self._ms_captured[k](x, y)
                     else:
-                        self._ms_body(k, x, y)
+                        self._fwd_bwd(x, y, self._ms_meters[k])
                     eng.bn_defer_stash(k, j)       # its running-stat slot -> arena row j
                 for t in (x, getattr(x, "_ddlpc_nhwc", None), y):
                     if t is not None and t.is_cuda:
                         t.record_stream(st)        # allocated on the caller's stream
         finally:
-            self._ms_exit(state)
+            eng.bn_defer_j = None
+            for p, g in zip(order, self._flat_views):
+                p.grad = g
+            eng.set_side_stream(side)
         self.ms_host_s += time.perf_counter() - t_host     # host enqueue time (diagnostic)
         for st in streams:
             cur.wait_stream(st)
         eng.bn_defer_apply(len(mbs))               # running statistics, in micro-batch order
-        self._ms_finish(K, len(mbs))
+        for b in self._mbufs[:K - 1]:              # extra gradient buffers into the flat one
+            self.flat.grad_buf.add_(b)             # (stream order), per-stream meters into
+            b.zero_()                              # the trainer's
+        for m in self._ms_meters[:K]:
+            self.meter.buf += m.buf
+            m.buf.zero_()
+        self.micro_count += len(mbs)
 
-    def _ms_graph_micro(self, k: int, st, x, y):
-        """Stream k's micro-batch as a replay of its own graph (eager for the first
-        GRAPH_WARMUP uses, then captured): the batch is copied into stream k's static
-        buffers on stream k."""
-        from ..data.datasets import engine_input
-        xp = getattr(x, "_ddlpc_nhwc", None)
-        sk = self._ms_static[k]
-        if sk is None or sk[1].shape != y.shape:
-            if xp is not None:
-                sp = torch.empty_like(xp)
-                sk = (engine_input(sp, x.shape[1]), torch.empty_like(y), sp)
-            else:
-                sk = (torch.empty_like(x), torch.empty_like(y), None)
-            self._ms_static[k] = sk
-            self._ms_graphs[k], self._ms_warm[k] = None, 0
-        sx, sy, sp = sk
-        if sp is not None and xp is not None:
-            sp.copy_(xp)
-        else:
-            sx.copy_(x)
-        sy.copy_(y)
-        g = self._ms_graphs[k]
-        if g is not None:
-            g.replay()
-            return
-        self._ms_body(k, sx, sy)
-        self._ms_warm[k] += 1
-        if self._ms_warm[k] >= self.GRAPH_WARMUP:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=st):
-                self._ms_body(k, sx, sy)
-            self._ms_graphs[k] = g
-
-    # ------------------------------------------------------------------ hipGraph step
+    # ------------------------------------------------------------------ hipGraph micro-batches
     def _graph_ok(self, n_micro: int) -> bool:
         return (self.cfg.hip_graph and self.impl == "hip" and self.device.type == "cuda"
                 and not self.cfg.broadcast_buffers and not self.cfg.check_consistency_every
                 and (self.reducer is None or n_micro > 1))
 
-    def _static_in(self, x: torch.Tensor, y: torch.Tensor):
-        """Copy a micro-batch into the graphs' static input buffers (one pair shared by every
-        graph: replays are sequential on one stream).  A device-pipeline batch (padded
-        channel-last bf16, ``data.engine_input``) is copied in that layout, so the captured
-        forward reads it with no layout pass."""
-        from ..data.datasets import engine_input
-        xp = getattr(x, "_ddlpc_nhwc", None)
-        if self._static is None or self._static[1].shape != y.shape:
-            if xp is not None:
-                sp = torch.empty_like(xp)
-                self._static = (engine_input(sp, x.shape[1]), torch.empty_like(y), sp)
-            else:
-                self._static = (torch.empty_like(x), torch.empty_like(y), None)
-        sx, sy, sp = self._static
-        if sp is not None and xp is not None:
-            sp.copy_(xp)
-        else:
-            sx.copy_(x)
-        sy.copy_(y)
-
-    def _graph_body(self, kind: str):
-        x, y = self._static[0], self._static[1]
-        if self.reducer is not None:
-            self.reducer.prepare(sync=False)        # "acc": never a collective in a graph
-        loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
-        loss.backward()
-        self.meter.add(loss, correct, y.numel())
+    def _graph_body(self, kind: str, x, y):
+        self._fwd_bwd(x, y, self.meter)
         if kind == "last":                          # single GPU: the optimizer step too
             self.optimizer.step()
             self.optimizer.zero_grad()
 
-    def _graph_run(self, kind: str):
-        """Run one captured micro-batch (``kind`` "acc": forward + backward accumulating into
-        the gradient buffer; "last": that + Adam (device-side bias corrections) + zero_grad +
-        weight re-pack).  The first ``GRAPH_WARMUP`` calls per kind run eagerly on a side
-        stream (allocator + lazy state warm-up); the next eager call is followed by the
-        capture (which executes nothing), later calls replay."""
-        g = self._graphs.get(kind)
-        if g is not None:
-            g.replay()
-            if kind == "last":
-                self.optimizer.note_replayed_step()
-            return
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._graph_body(kind)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self._graph_warm[kind] = self._graph_warm.get(kind, 0) + 1
-        if self._graph_warm[kind] >= self.GRAPH_WARMUP:
-            self.model._engine.join()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._graph_body(kind)
-            if kind == "last":
-                self.optimizer.step_count -= 1       # the capture ran step() once in Python
-            self._graphs[kind] = g
+    def _graph_micro(self, kind: str, x, y):
+        """One captured micro-batch (~220 kernel launches -> one replay; the reference's
+        regime — batch 1 per GPU, 50 accumulated micro-batches per exchange, ref.py:685-687,
+        750-766 — is launch-bound).  ``kind`` "acc": forward + backward accumulating into the
+        gradient buffer; "last" (single GPU only): that + Adam (device-side bias corrections)
+        + zero_grad + weight re-pack.  Both read one pair of static inputs (replays follow
+        each other on one stream); their warm-up runs on a fresh side stream (allocator +
+        lazy state) and the engine's streams are joined before the capture."""
+        c = self._captured.get(kind)
+        if c is None:
+            c = self._captured[kind] = CapturedMicro(
+                self._static, functools.partial(self._graph_body, kind), self.GRAPH_WARMUP,
+                eager=functools.partial(on_fresh_stream, device=self.device),
+                capture=functools.partial(capture_graph, before=self.model._engine.join))
+        did = c(x, y)
+        if kind == "last" and did == "capture":
+            self.optimizer.step_count -= 1           # the capture ran step() once in Python
+        elif kind == "last" and did == "replay":
+            self.optimizer.note_replayed_step()      # host mirror of the replayed step
+        self.micro_count += 1
 
-    def _graph_step(self, micro_batches: List[Tuple[torch.Tensor, torch.Tensor]]):
-        """One optimizer step with hipGraph-captured micro-batches (~220 kernel launches per
-        micro-batch -> one replay): the reference's regime — batch 1 per GPU, 50
-        accumulated micro-batches per exchange (ref.py:685-687,750-766) — is launch-bound.
-        Accumulation micro-batches replay the "acc" graph; the last one replays "last"
-        (single GPU) or, under data parallelism, runs eagerly so the bucketed collectives
-        launch from backward as usual, followed by the exchange and Adam."""
-        self.model.train()
-        ph = self.phases
-        if ph is not None:
-            ph.mark("start")
-        if self._concurrent_ok(len(micro_batches)):
-            # accumulation micro-batches: K streams, each replaying its own graph
-            self._concurrent_micros(micro_batches[:-1])
-            micro_batches = micro_batches[-1:]
-        n = len(micro_batches)
-        for i, (x, y) in enumerate(micro_batches):
-            last = i == n - 1
-            if last and self.reducer is not None:
-                self._micro(x, y, sync=True)
-                break
-            self._static_in(x, y)
-            self._graph_run("last" if last else "acc")
-            self.micro_count += 1
-        if self.reducer is not None:
-            if ph is not None:
-                ph.mark("fwd_bwd")
-            with trace_range("ddlpc.grad_sync"):
-                self.reducer.finish()
-            if ph is not None:
-                ph.mark("comm_wait")
-            with trace_range("ddlpc.optimizer"):
-                self.optimizer.step()
-                self.optimizer.zero_grad()
-            if ph is not None:
-                ph.mark("optimizer")
-        if ph is not None:
-            ph.end_step()
-        self.step_count += 1
-        self.profiler.step()
+    @property
+    def _graphs(self) -> dict:                 # the single-stream graphs captured so far
+        return {k: c.graph for k, c in self._captured.items() if c.graph is not None}
+
+    @property
+    def _ms_graphs(self) -> list:              # every stream's graph (None: not captured yet)
+        return [c.graph for c in self._ms_captured]
 
     GRAPH_WARMUP = 3
 
@@ -723,24 +621,10 @@ class Trainer:
         return float(free + torch.cuda.memory_reserved(self.device) -
                      torch.cuda.memory_allocated(self.device))
 
-    @staticmethod
-    def _cat_window(mbs: List[Tuple[torch.Tensor, torch.Tensor]]):
-        """The window's micro-batches as one batch (engine-layout inputs stay in that layout).
-        The micro-batches must have equal shapes: each is one BatchNorm group of batch / G
-        samples, and the window's mean loss x G is the sum of the micro-batch losses only
-        when every micro-batch has the same pixel count."""
-        from ..data.datasets import cat_adjacent, engine_input
-        shapes = {(tuple(x.shape), tuple(y.shape)) for x, y in mbs}
-        if len(shapes) != 1:
-            raise ValueError(f"batched BN window: micro-batches of unequal shapes {sorted(shapes)}")
-        # (micro-batches that are back-to-back views of one rendered window — data.split_batch
-        # — are joined without a copy)
-        xps = [getattr(x, "_ddlpc_nhwc", None) for x, _ in mbs]
-        if all(xp is not None for xp in xps):
-            x = engine_input(cat_adjacent(xps), mbs[0][0].shape[1])
-        else:
-            x = cat_adjacent([x for x, _ in mbs])
-        return x, cat_adjacent([y for _, y in mbs])
+    # the window's micro-batches as one batch: each is one BatchNorm group of batch / G samples,
+    # and the window's mean loss x G is the sum of the micro-batch losses only when every
+    # micro-batch has the same pixel count (unequal shapes raise)
+    _cat_window = staticmethod(join_batches)
 
     def _window_step(self, micro_batches: List[Tuple[torch.Tensor, torch.Tensor]], W: int):
         """The accumulation window as batched passes of up to W micro-batches, each micro-batch
@@ -755,51 +639,59 @@ class Trainer:
         chunks = [micro_batches[i:i + W] for i in range(0, n, W)]
         for ci, ch in enumerate(chunks):
             x, y = self._cat_window(ch) if len(ch) > 1 else ch[0]
-            if self.reducer is not None:
-                self.reducer.prepare(sync=ci == len(chunks) - 1)
+            before_backward = self._arm(sync=ci == len(chunks) - 1)
             eng.bn_groups = len(ch) if len(ch) > 1 else 0
             try:
-                loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
-                if self.reducer is not None and ci == len(chunks) - 1:
-                    self.reducer.mark_backward_start()
-                (loss * float(len(ch)) if len(ch) > 1 else loss).backward()
+                self._fwd_bwd(x, y, self.meter, groups=len(ch), before_backward=before_backward)
             finally:
                 eng.bn_groups = 0
-            self.meter.add(loss, correct, y.numel(), n=len(ch))
             self.micro_count += len(ch)
 
     def _train_step(self, micro_batches: List[Tuple[torch.Tensor, torch.Tensor]]):
-        W = self._window_size(len(micro_batches))
+        """Pick how the micro-batches run — batched windows, else hipGraph replays, else
+        concurrent streams plus the last one, else one by one — then the one step tail."""
+        n = len(micro_batches)
+        W = self._window_size(n)
         if W and len({tuple(x.shape) for x, _ in micro_batches}) != 1:
             W = 0                        # unequal micro-batches (a short last one): one by one
-        if W == 0 and self._graph_ok(len(micro_batches)):
-            return self._graph_step(micro_batches)
+        graph = W == 0 and self._graph_ok(n)
+        # single-GPU graph schedule: Adam, zero_grad and the weight re-pack are inside "last"
+        opt_in_graph = graph and self.reducer is None
         self.model.train()
-        n = len(micro_batches)
         ph = self.phases
         if ph is not None:
             ph.mark("start")
         with trace_range("ddlpc.fwd_bwd"):
             if W:
                 self._window_step(micro_batches, W)
+                micro_batches = []
             elif self._concurrent_ok(n):
+                # accumulation micro-batches: K streams (each replaying its own graph)
                 self._concurrent_micros(micro_batches[:-1])
-                self._micro(*micro_batches[-1], sync=True)
-            else:
-                for i, (x, y) in enumerate(micro_batches):
-                    self._micro(x, y, sync=(i == n - 1))
-        if ph is not None:
-            ph.mark("fwd_bwd")
-        if self.reducer is not None:
-            with trace_range("ddlpc.grad_sync"):
-                self.reducer.finish()
+                micro_batches = micro_batches[-1:]
+            for i, (x, y) in enumerate(micro_batches):
+                last = i == len(micro_batches) - 1
+                if graph and not (last and self.reducer is not None):
+                    self._arm(sync=False)             # "acc": never a collective in a graph
+                    self._graph_micro("last" if last else "acc", x, y)
+                else:
+                    # (under data parallelism the last micro-batch is always eager, so the
+                    # bucketed collectives launch from its backward)
+                    self._micro(x, y, sync=last)
+        if not opt_in_graph:
             if ph is not None:
-                ph.mark("comm_wait")          # exposed (non-overlapped) all-reduce time
-        with trace_range("ddlpc.optimizer"):
-            self.optimizer.step()
-            self.optimizer.zero_grad()
+                ph.mark("fwd_bwd")
+            if self.reducer is not None:
+                with trace_range("ddlpc.grad_sync"):
+                    self.reducer.finish()
+                if ph is not None:
+                    ph.mark("comm_wait")      # exposed (non-overlapped) all-reduce time
+            with trace_range("ddlpc.optimizer"):
+                self.optimizer.step()
+                self.optimizer.zero_grad()
+            if ph is not None:
+                ph.mark("optimizer")
         if ph is not None:
-            ph.mark("optimizer")
             ph.end_step()
         self.profiler.step()
         if self.cfg.broadcast_buffers:
@@ -1020,10 +912,6 @@ class _Subset:
 
     def __len__(self):
         return self.end - self.start
-
-    @property
-    def on_device(self) -> bool:
-        return getattr(self.base, "on_device", False)
 
     def get(self, idx):
         if torch.is_tensor(idx):         # device indices stay on the device (no host sync)

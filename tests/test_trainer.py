@@ -92,6 +92,55 @@ def test_phase_timer_on_cpu_uses_the_host_clock():
     assert pt.read() == {}                     # reset after a read
 
 
+def _phase_keys(rank, world):
+    cfg = TrainConfig(model=ModelConfig(out_classes=2, depth=3, width_divisor=16), tile=32,
+                      dtype="fp32", impl="torch", num_samples=8, test_holdout=0, batch_per_gpu=2,
+                      accum_steps=2, phase_timers=True, log_every=0, timeout_s=60)
+    tr = Trainer(cfg, device="cpu")
+    assert (tr.reducer is not None) == (world > 1)
+    mbs = [tr._to_device(*tr.train_set.get([0, 1])), tr._to_device(*tr.train_set.get([2, 3]))]
+    for _ in range(2):
+        tr.train_step(mbs)
+    keys = sorted(tr.phases.read())
+    tr.close()
+    return keys
+
+
+def test_phase_marks_per_schedule_cpu():
+    """The eager schedule's phase marks (start, fwd_bwd, [comm_wait,] optimizer): comm_wait
+    only with a gradient reducer, here a gloo world of two.  (The single-GPU graph schedule's
+    marks: tests/test_unet_gpu.py.)"""
+    from dist_utils import run
+    eager = {"fwd_bwd_ms", "optimizer_ms", "step_ms"}
+    assert set(_phase_keys(0, 1)) == eager
+    res = run(_phase_keys, 2)
+    assert set(res[0]) == set(res[1]) == eager | {"comm_wait_ms"}
+
+
+def test_captured_micro_drops_its_graph_with_its_static_inputs():
+    """``train.capture``'s rule, with a counting fake in place of the capture: eager for three
+    uses, the third followed by the capture, then replays; a new label shape replaces the
+    static inputs, so every graph captured over them (two share them here, as "acc" and
+    "last" do) is dropped and warms up again, and so once more back on the old shape."""
+    from ddlpc.train.capture import CapturedMicro, StaticInputs
+    log, static = [], StaticInputs()
+    fake = type("G", (), {"replay": lambda self: log.append("replay")})
+
+    def capture(fn):
+        log.append("capture")
+        return fake()
+    a, b = (CapturedMicro(static, lambda x, y: log.append("eager"), 3, capture=capture)
+            for _ in range(2))
+    full = (torch.zeros(4, 3, 8, 8), torch.zeros(4, 8, 8))
+    short = (torch.ones(2, 3, 8, 8), torch.ones(2, 8, 8))
+    warm = ["eager", "eager", "eager", "capture"]
+    for batch, n, want in ((full, 5, warm + ["replay"] * 2), (short, 3, warm), (full, 3, warm)):
+        for c in (a, b):
+            del log[:]
+            assert [c(*batch) for _ in range(n)] == (["eager", "eager", "capture"] + ["replay"] * 2)[:n]
+            assert log == want and torch.equal(static.bufs[0], batch[0])
+
+
 def test_bench_cpu_json_contract():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--impl", "torch",

@@ -210,6 +210,84 @@ def test_trainer_hip_graph_accumulation_matches_eager(accum):
         assert torch.equal(b0[k], b1[k]), k
 
 
+def _short_batch_run(graph, accum, steps):
+    """``steps``: per train_step call, the batch sizes of its micro-batches.  Every micro-batch
+    is its own seeded batch.  -> parameters, second moments, running statistics, step losses."""
+    from ddlpc.config import ModelConfig, TrainConfig
+    from ddlpc.data import device_random_batch
+    from ddlpc.train.trainer import Trainer
+    cfg = TrainConfig(model=ModelConfig(out_classes=6), tile=64, batch_per_gpu=4, num_samples=1,
+                      test_holdout=0, impl="hip", hip_graph=graph, accum_steps=accum,
+                      micro_streams=1, bn_window=0)
+    tr = Trainer(cfg, device=DEV)
+    tr.model._engine.set_side_stream(False)
+    losses, seed = [], 0
+    for sizes in steps:
+        mbs = []
+        for b in sizes:
+            mbs.append(device_random_batch(b, 64, 6, tr.device, seed=seed))
+            seed += 1
+        tr.train_step(mbs)
+        losses.append(tr.meter.reduce()["loss"])
+        tr.meter.reset()
+    assert tr.optimizer.step_count == tr.step_count == len(steps)
+    assert tr.micro_count == sum(len(s) for s in steps)
+    if graph:
+        assert set(tr._graphs) == ({"last"} if accum == 1 else {"acc", "last"})
+    _sync()
+    out = (tr.flat.param_buf.clone(), tr.optimizer.exp_avg_sq.clone(),
+           {k: v.clone() for k, v in tr.model.state_dict().items() if "running" in k}, losses)
+    tr.close()
+    return out
+
+
+def _assert_runs_equal(eager, graph):
+    (p0, v0, b0, l0), (p1, v1, b1, l1) = eager, graph
+    assert torch.equal(p0, p1), float((p0 - p1).abs().max())
+    assert torch.equal(v0, v1)
+    assert l0 == l1, (l0, l1)
+    for k in b0:
+        assert torch.equal(b0[k], b1[k]), k
+
+
+def test_hip_graph_short_batch_matches_eager():
+    """A short batch (``ShardedSampler.batches`` without drop_last ends an epoch on one) replaces
+    the graphs' static inputs, so the "last" graph captured over the old ones is dropped and
+    warms up again: calls 1-5 run a batch of 4 (the fifth replays), call 6 a batch of 2, calls
+    7-9 batches of 4 (re-captured on call 9).  Bit-identical to the eager schedule: every kernel
+    on this path is deterministic."""
+    steps = [[4]] * 5 + [[2]] + [[4]] * 3
+    _assert_runs_equal(_short_batch_run(False, 1, steps), _short_batch_run(True, 1, steps))
+
+
+def test_hip_graph_short_micro_batch_in_window_matches_eager():
+    """The same with accumulation: the short micro-batch sits in the middle of one window, so
+    the "acc" graph stages it and both graphs lose the static inputs they share.  Parameters,
+    moments, running statistics and losses equal the eager schedule's."""
+    steps = [[4, 4, 4]] * 5 + [[4, 2, 4]] + [[4, 4, 4]] * 3
+    _assert_runs_equal(_short_batch_run(False, 3, steps), _short_batch_run(True, 3, steps))
+
+
+def test_phase_marks_per_schedule():
+    """The phase marks of a step, by schedule (``PhaseTimer.read()`` stays comparable with
+    recorded runs): eager start / fwd_bwd / optimizer; single-GPU graph start only, since
+    the optimizer runs inside the "last" graph.  (With a reducer: tests/test_trainer.py.)"""
+    from ddlpc.config import ModelConfig, TrainConfig
+    from ddlpc.data import device_random_batch
+    from ddlpc.train.trainer import Trainer
+    for graph, want in ((False, {"fwd_bwd_ms", "optimizer_ms", "step_ms"}), (True, {"step_ms"})):
+        cfg = TrainConfig(model=ModelConfig(out_classes=6), tile=64, batch_per_gpu=2, num_samples=1,
+                          test_holdout=0, impl="hip", hip_graph=graph, phase_timers=True)
+        tr = Trainer(cfg, device=DEV)
+        batch = device_random_batch(2, 64, 6, tr.device)
+        for _ in range(5):                       # the fifth is a replay
+            tr.train_step([batch])
+        _sync()
+        assert ("last" in tr._graphs) == graph
+        assert set(tr.phases.read()) == want, graph
+        tr.close()
+
+
 def test_wgrad_side_stream_matches_serial(monkeypatch):
     """Weight gradients on the side HIP stream (default) give bit-identical training to the
     fully serial schedule (DDLPC_WGRAD_STREAM=0): same kernels, only the overlap differs."""
