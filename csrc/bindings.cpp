@@ -17,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "data_checks.h"
 #include "ops.h"
 #include "optim_math.h"
 
@@ -1421,14 +1422,8 @@ std::vector<int64_t> batch_shape(int64_t B, int64_t tile, int64_t dims) {
 std::vector<at::Tensor> synth_tiles(const at::Tensor& idx, int64_t seed, int64_t classes,
                                     int64_t in_ch, int64_t tile, int64_t dims, int64_t grid,
                                     double k, const at::Tensor& palette, int64_t cpad) {
-  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(palette); CHECK_F32(palette); CHECK_CONTIG(palette);
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  TORCH_CHECK(dims == 2 || dims == 3, "dims must be 2 or 3");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  TORCH_CHECK(classes >= 1 && palette.numel() == classes * in_ch, "palette must be [classes][in_ch]");
-  TORCH_CHECK(grid >= 1 && grid <= tile && tile >= 1, "1 <= grid <= tile");
-  TORCH_CHECK((int64_t)tile * tile * (dims == 3 ? tile : 1) * 8 < (int64_t)UINT32_MAX,
-              "tile too large for the 32-bit per-pixel hash counter");
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(palette); CHECK_CONTIG(palette);
+  checks::synth_tiles(idx, classes, in_ch, tile, dims, grid, palette, cpad);
   c10::DeviceGuard guard(idx.device());
   const int64_t B = idx.numel();
   std::vector<int64_t> xs = batch_shape(B, tile, dims);
@@ -1448,12 +1443,8 @@ std::vector<at::Tensor> tile_gather(const at::Tensor& src, const at::Tensor& lab
                                     const at::Tensor& idx, int64_t cpad) {
   CHECK_DEV(src); CHECK_CONTIG(src); CHECK_DEV(lab); CHECK_CONTIG(lab); CHECK_DEV(idx);
   CHECK_CONTIG(idx);
-  TORCH_CHECK(src.scalar_type() == at::kByte && lab.scalar_type() == at::kByte, "uint8 dataset");
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  TORCH_CHECK(src.dim() == lab.dim() + 1 && src.size(0) == lab.size(0), "images [N,...,C] / labels [N,...]");
+  checks::tile_gather(src, lab, idx, cpad);
   const int64_t in_ch = src.size(-1);
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  for (int64_t i = 1; i < lab.dim(); ++i) TORCH_CHECK(src.size(i) == lab.size(i), "spatial mismatch");
   c10::DeviceGuard guard(src.device());
   const int64_t B = idx.numel();
   const long long S = lab.numel() / std::max<int64_t>(1, lab.size(0));
@@ -1470,31 +1461,15 @@ std::vector<at::Tensor> tile_gather(const at::Tensor& src, const at::Tensor& lab
   return {x, y};
 }
 
-// the arguments crop_gather and warp_gather share: packed scenes (uint8 pixels [P, Cin], uint8
-// labels [P], int64 table [n, 3] of (offset, H, W)), the op's per-sample rows `params` [B, k]
-// (layout checked by the caller), optional per-sample (gain, bias) -> the colour pointer
-static const float* check_gather_args(const char* op, const at::Tensor& scenes, const at::Tensor& labels,
-                                      const at::Tensor& table, const at::Tensor& params,
-                                      const c10::optional<at::Tensor>& color, int64_t tile) {
+// crop_gather / warp_gather, after checks::*: contiguous device tensors, a grid that fits -> colour
+static const float* gather_device_args(const char* op, const at::Tensor& scenes, const at::Tensor& labels,
+                                       const at::Tensor& table, const at::Tensor& params,
+                                       const c10::optional<at::Tensor>& color, int64_t tile) {
   CHECK_DEV(scenes); CHECK_CONTIG(scenes); CHECK_DEV(labels); CHECK_CONTIG(labels);
-  CHECK_DEV(table); CHECK_CONTIG(table);
-  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
-  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
-              "labels must be uint8 [pixels]");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
-              "table must be int64 [n, 3] (pixel offset, H, W)");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
-  TORCH_CHECK(labels.device() == scenes.device() && table.device() == scenes.device() &&
-              params.device() == scenes.device(), op, ": tensors on different devices");
-  const int64_t B = params.size(0);
-  if (has(color)) {
-    CHECK_DEV(*color); CHECK_CONTIG(*color); CHECK_F32(*color);
-    TORCH_CHECK(color->dim() == 2 && color->size(0) == B && color->size(1) == 2 &&
-                color->device() == scenes.device(), "color must be fp32 [B, 2] (gain, bias)");
-  }
+  CHECK_DEV(table); CHECK_CONTIG(table); CHECK_DEV(params); CHECK_CONTIG(params);
+  if (has(color)) { CHECK_DEV(*color); CHECK_CONTIG(*color); }
   const int64_t nb = crop_gather_blocks((int)tile);
-  TORCH_CHECK(B * nb * nb < (1LL << 31), op, ": batch too large");
+  TORCH_CHECK(params.size(0) * nb * nb < (1LL << 31), op, ": batch too large");
   return fptr_opt(color);
 }
 
@@ -1504,12 +1479,9 @@ std::vector<at::Tensor> crop_gather(const at::Tensor& scenes, const at::Tensor& 
                                     const at::Tensor& table, const at::Tensor& params,
                                     const c10::optional<at::Tensor>& color, int64_t tile,
                                     int64_t cpad) {
-  CHECK_DEV(params); CHECK_CONTIG(params);
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
-              "params must be int32 [B, 4] (scene, y0, x0, code)");
-  const float* pc = check_gather_args("crop_gather", scenes, labels, table, params, color, tile);
+  checks::crop_gather(scenes, labels, table, params, color, tile, cpad);
+  const float* pc = gather_device_args("crop_gather", scenes, labels, table, params, color, tile);
   const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0);
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
   c10::DeviceGuard guard(scenes.device());
   at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
   at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
@@ -1521,30 +1493,17 @@ std::vector<at::Tensor> crop_gather(const at::Tensor& scenes, const at::Tensor& 
   return {x, y};
 }
 
-// the arguments crop_params and warp_params share: virtual sample numbers idx, the scenes'
-// cumulative sample counts cum [n + 1] and table [n, 3] -> the sample count B
-static int64_t check_params_args(const char* op, const at::Tensor& idx, const at::Tensor& cum,
-                                 const at::Tensor& table, int64_t tile, int64_t mode) {
+static void params_device_args(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table) {
   CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_DEV(cum); CHECK_CONTIG(cum); CHECK_DEV(table); CHECK_CONTIG(table);
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
-              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
-  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
-              "cum must be int64 [n + 1]");
-  TORCH_CHECK(cum.device() == idx.device() && table.device() == idx.device(), op,
-              ": tensors on different devices");
-  TORCH_CHECK(table.size(0) < (1LL << 31), "too many scenes");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
-  TORCH_CHECK(idx.numel() < (1LL << 31), "too many samples");
-  return idx.numel();
 }
 
-// virtual sample numbers -> {params int32 [B, 4], color fp32 [B, 2]} (counter-based: data.hip)
+// virtual sample numbers -> {params int32 [B, 4], color fp32 [B, 2]} (counter-based: data_math.h)
 std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
                                     int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
                                     double bias_jitter) {
-  const int64_t B = check_params_args("crop_params", idx, cum, table, tile, mode);
+  checks::params_args("crop_params", idx, cum, table, tile, mode);
+  params_device_args(idx, cum, table);
+  const int64_t B = idx.numel();
   c10::DeviceGuard guard(idx.device());
   at::Tensor params = at::empty({B, 4}, idx.options().dtype(at::kInt));
   at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
@@ -1557,18 +1516,14 @@ std::vector<at::Tensor> crop_params(const at::Tensor& idx, const at::Tensor& cum
 }
 
 // crop_gather under a zoom and a rotation: wparams int64 [B, 6] of (scene, cy, cx, code, A, Bm)
-// rows, 16.16 fixed point (the recipe: data.hip) -> {x bf16 [B, T, T, cpad], y int64}
+// rows, 16.16 fixed point (the recipe: data_math.h) -> {x bf16 [B, T, T, cpad], y int64}
 std::vector<at::Tensor> warp_gather(const at::Tensor& scenes, const at::Tensor& labels,
                                     const at::Tensor& table, const at::Tensor& wparams,
                                     const c10::optional<at::Tensor>& color, int64_t tile,
                                     int64_t cpad) {
-  CHECK_DEV(wparams); CHECK_CONTIG(wparams);
-  TORCH_CHECK(wparams.scalar_type() == at::kLong && wparams.dim() == 2 && wparams.size(1) == 6,
-              "wparams must be int64 [B, 6] (scene, cy, cx, code, A, Bm)");
-  const float* pc = check_gather_args("warp_gather", scenes, labels, table, wparams, color, tile);
+  checks::warp_gather(scenes, labels, table, wparams, color, tile, cpad);
+  const float* pc = gather_device_args("warp_gather", scenes, labels, table, wparams, color, tile);
   const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0);
-  TORCH_CHECK(cpad == 4 || cpad == 8, "cpad must be 4 or 8");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= cpad, "1 <= in_ch <= cpad");
   c10::DeviceGuard guard(scenes.device());
   at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
   at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
@@ -1580,18 +1535,14 @@ std::vector<at::Tensor> warp_gather(const at::Tensor& scenes, const at::Tensor& 
 }
 
 // virtual sample numbers -> {wparams int64 [B, 6], color fp32 [B, 2]}: crop_params with a zoom
-// step and a rotation drawn from the int32 tables steps [S] and rot [T, 2] (data.hip)
+// step and a rotation drawn from the int32 tables steps [S] and rot [T, 2] (data_math.h)
 std::vector<at::Tensor> warp_params(const at::Tensor& idx, const at::Tensor& cum, const at::Tensor& table,
                                     const at::Tensor& steps, const at::Tensor& rot, int64_t seed,
                                     int64_t tile, int64_t mode, double gain_jitter, double bias_jitter) {
+  checks::warp_params(idx, cum, table, steps, rot, tile, mode);
   CHECK_DEV(steps); CHECK_CONTIG(steps); CHECK_DEV(rot); CHECK_CONTIG(rot);
-  TORCH_CHECK(steps.scalar_type() == at::kInt && steps.dim() == 1 && steps.size(0) >= 1 &&
-              steps.size(0) <= 65536, "steps must be int32 [S], 1 <= S <= 65536");
-  TORCH_CHECK(rot.scalar_type() == at::kInt && rot.dim() == 2 && rot.size(1) == 2 && rot.size(0) >= 1 &&
-              rot.size(0) <= 65536, "rot must be int32 [T, 2] (cos, sin), 1 <= T <= 65536");
-  TORCH_CHECK(steps.device() == idx.device() && rot.device() == idx.device(),
-              "warp_params: tensors on different devices");
-  const int64_t B = check_params_args("warp_params", idx, cum, table, tile, mode);
+  params_device_args(idx, cum, table);
+  const int64_t B = idx.numel();
   c10::DeviceGuard guard(idx.device());
   at::Tensor wparams = at::empty({B, 6}, idx.options().dtype(at::kLong));
   at::Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
@@ -1605,21 +1556,12 @@ std::vector<at::Tensor> warp_params(const at::Tensor& idx, const at::Tensor& cum
 }
 
 // ------------------------------------------------------------------------ scene prediction
-static void check_origins(const at::Tensor& origins, const at::Tensor& like) {
-  CHECK_DEV(origins); CHECK_CONTIG(origins);
-  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(1) == 2,
-              "origins must be int32 [B, 2] (y0, x0)");
-  TORCH_CHECK(origins.device() == like.device(), "origins must be on the scene's device");
-}
-
 // test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
-// in 0..7) -> S and the codes packed 3 bits each, code j at bits 3 j (without codes: S = 1, code
-// 0 — the plain window — with no device read).  The
-// values are checked on the host and reach the kernels as a launch argument: the list is read
-// back with one small blocking copy, once per tensor — the last checked list of a thread is
-// remembered (the tensor itself, so its memory cannot be handed out again, and its version
-// counter, which every in-place write moves), and a predictor that passes the same codes tensor
-// to every call pays the copy and the stall of the launch queue once per scene, not per pass
+// in 0..7; checks::codes) -> S and the codes packed 3 bits each (without codes: S = 1, code 0, no
+// device read).  The values reach the kernels as a launch argument: the list is read
+// back with one small blocking copy, once per tensor — a thread's last checked list is remembered
+// (the tensor itself, so its memory cannot be handed out again, and its version counter, which
+// every in-place write moves): a predictor pays the copy and the stall once per scene, not per pass
 namespace {
 struct CodesSeen {
   at::Tensor t;
@@ -1629,11 +1571,8 @@ struct CodesSeen {
 }  // namespace
 static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& like, uint32_t* packed) {
   *packed = 0u;
+  const int64_t S = checks::codes(codes, like);
   if (!has(codes)) return 1;
-  TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
-  TORCH_CHECK(codes->device() == like.device(), "codes must be on the device of the other tensors");
-  const int64_t S = codes->size(0);
-  TORCH_CHECK(S >= 1 && S <= 8, "codes: 1 <= S <= 8");
   // (never freed: a device tensor must not be destroyed while the process exits)
   thread_local CodesSeen* seen_last = new CodesSeen();
   const bool versioned = !codes->is_inference();
@@ -1643,14 +1582,7 @@ static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& 
     return (int)S;
   }
   const at::Tensor host = codes->contiguous().cpu();
-  const int* c = host.data_ptr<int>();
-  uint32_t seen = 0u;
-  for (int64_t j = 0; j < S; ++j) {
-    TORCH_CHECK(c[j] >= 0 && c[j] <= 7, "codes: values must lie in 0..7");
-    TORCH_CHECK(!(seen & (1u << c[j])), "codes: values must be distinct");
-    seen |= 1u << c[j];
-    *packed |= (uint32_t)c[j] << (3 * j);
-  }
+  *packed = checks::pack_code_values(host.data_ptr<int>(), S);
   if (versioned) {
     seen_last->t = *codes;
     seen_last->S = S;
@@ -1664,16 +1596,11 @@ static int pack_codes(const c10::optional<at::Tensor>& codes, const at::Tensor& 
 // with codes [S]: [B * S, tile, tile, cpad], row b * S + j = window b under symmetry codes[j]
 at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int64_t tile,
                          int64_t cpad, const c10::optional<at::Tensor>& codes) {
-  CHECK_DEV(scene); CHECK_CONTIG(scene);
-  TORCH_CHECK(scene.scalar_type() == at::kByte && scene.dim() == 3, "scene must be uint8 [H, W, Cin]");
-  check_origins(origins, scene);
+  checks::window_gather(scene, origins, tile, cpad);
+  CHECK_DEV(scene); CHECK_CONTIG(scene); CHECK_DEV(origins); CHECK_CONTIG(origins);
   const int64_t H = scene.size(0), W = scene.size(1), in_ch = scene.size(2);
-  TORCH_CHECK(H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30), "scene size out of range");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
   c10::DeviceGuard guard(scene.device());
   const int64_t B = origins.size(0);
-  TORCH_CHECK(B < (1 << 30), "too many windows");
   uint32_t packed = 0u;
   const int S = pack_codes(codes, scene, &packed);
   const int64_t nb = window_gather_blocks((int)tile);
@@ -1692,33 +1619,19 @@ at::Tensor window_gather(const at::Tensor& scene, const at::Tensor& origins, int
 void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                         const at::Tensor& origins, const at::Tensor& win, at::Tensor& acc,
                         const c10::optional<at::Tensor>& bn4, const c10::optional<at::Tensor>& codes) {
-  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
-  TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2), "a must be [B, tile, tile, C]");
+  CHECK_DEV(a); CHECK_CONTIG(a);
   uint32_t packed = 0u;
   const int S = pack_codes(codes, a, &packed);
-  TORCH_CHECK(a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
+  checks::head_predict_accum(a, Wh, bh, origins, win, acc, S);
   const int64_t B = a.size(0) / S, tile = a.size(1);
-  const int C = (int)a.size(3);
+  const int C = (int)a.size(3), K = (int)Wh.size(0);
   CHECK_DEV(Wh); CHECK_F32(Wh); CHECK_CONTIG(Wh); CHECK_DEV(bh); CHECK_F32(bh); CHECK_CONTIG(bh);
-  TORCH_CHECK(Wh.dim() == 2 && Wh.size(1) == C && bh.numel() == Wh.size(0), "Wh [K, C] / bh [K]");
-  const int K = (int)Wh.size(0);
   TORCH_CHECK(head_supported(C, K), "head kernel: unsupported (C, K)");
-  check_origins(origins, a);
-  TORCH_CHECK(origins.size(0) == B, "one origin per window");
-  CHECK_DEV(win); CHECK_F32(win); CHECK_CONTIG(win);
-  TORCH_CHECK(win.dim() == 1 && win.size(0) == tile, "win must be fp32 [tile]");
-  CHECK_DEV(acc); CHECK_F32(acc); CHECK_CONTIG(acc);
-  TORCH_CHECK(acc.dim() == 3 && acc.size(2) == 4 * ((K + 4) / 4),
-              "acc must be fp32 [H, W, 4 * ceil((K + 1) / 4)]");
+  CHECK_DEV(origins); CHECK_CONTIG(origins); CHECK_DEV(win); CHECK_CONTIG(win); CHECK_DEV(acc); CHECK_CONTIG(acc);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(acc.data_ptr()) % 16 == 0, "acc must be 16-byte aligned");
-  TORCH_CHECK(acc.size(0) < (1 << 30) && acc.size(1) < (1 << 30) && tile <= 32768 && B < (1 << 30),
-              "scene / window size out of range");
-  TORCH_CHECK(Wh.device() == a.device() && bh.device() == a.device() && win.device() == a.device() &&
-              acc.device() == a.device(), "device mismatch");
   c10::DeviceGuard guard(a.device());
   const float* pbn = bn4_ptr(bn4, C);
   if (B == 0) return;
-  TORCH_CHECK(B * S < (1 << 30), "scene / window size out of range");
   head_predict_accum_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), origins.data_ptr<int>(),
                             win.data_ptr<float>(), acc.data_ptr<float>(), (int)B, S, packed, (int)tile,
                             (int)acc.size(0), (int)acc.size(1), (int)acc.size(2), C, K, pbn, cur_stream());
@@ -1727,17 +1640,14 @@ void head_predict_accum(const at::Tensor& a, const at::Tensor& Wh, const at::Ten
 // accumulator [H, W, KA] -> {class map uint8 [H, W], confusion matrix int64 [K, K]}
 std::vector<at::Tensor> scene_finalize(const at::Tensor& acc, int64_t K,
                                        const c10::optional<at::Tensor>& labels, int64_t ignore_index) {
-  CHECK_DEV(acc); CHECK_F32(acc); CHECK_CONTIG(acc);
-  TORCH_CHECK(acc.dim() == 3 && acc.size(2) % 4 == 0, "acc must be fp32 [H, W, KA], KA % 4 == 0");
-  TORCH_CHECK(K >= 1 && K <= 16 && K <= acc.size(2), "1 <= K <= min(16, KA)");
+  checks::scene_finalize(acc, K, labels);
+  CHECK_DEV(acc); CHECK_CONTIG(acc);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(acc.data_ptr()) % 16 == 0, "acc must be 16-byte aligned");
   c10::DeviceGuard guard(acc.device());
   const int64_t H = acc.size(0), W = acc.size(1);
   const uint8_t* lp = nullptr;
   if (has(labels)) {
     CHECK_DEV(*labels); CHECK_CONTIG(*labels);
-    TORCH_CHECK(labels->scalar_type() == at::kByte && labels->dim() == 2 && labels->size(0) == H &&
-                labels->size(1) == W && labels->device() == acc.device(), "labels must be uint8 [H, W]");
     lp = labels->data_ptr<uint8_t>();
   }
   at::Tensor pred = at::empty({H, W}, acc.options().dtype(at::kByte));

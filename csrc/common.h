@@ -154,14 +154,4 @@ DDLPC_DEVICE int opaque_zero() {
   return z;
 }
 
-// mirror index i into [0, n): period 2 (n - 1), edge pixel not repeated; a window may wrap
-// several times over a scene smaller than itself
-DDLPC_DEVICE int reflect_index(int i, int n) {
-  if (n == 1) return 0;
-  const int p = 2 * (n - 1);
-  i %= p;
-  if (i < 0) i += p;
-  return i >= n ? p - i : i;
-}
-
 inline int ceil_div(long a, long b) { return static_cast<int>((a + b - 1) / b); }

@@ -23,6 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "data_checks.h"
+#include "data_math.h"
 #include "optim_math.h"
 
 namespace ddlpc {
@@ -34,6 +36,7 @@ namespace ddlpc_cpu {
 
 using at::Tensor;
 using c10::optional;
+using namespace ddlpc;      // data_math.h, data_checks.h, optim_math.h
 
 namespace {
 
@@ -995,140 +998,105 @@ Tensor to_nhwc_bf16(const Tensor& x, int64_t cpad) {
   return y.contiguous();
 }
 
-uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-float u24(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
+// ------------------------------------------------------------------------ input pipeline
+// The CPU twins of data.hip / scene.hip: loops around the recipe of data_math.h behind the checks
+// of data_checks.h (synth_tiles spells its recipe as synth_tiles_kernel does, line for line).
 
-// the synthetic Vaihingen-shape batch (csrc/data.hip synth_tiles_kernel), bit for bit: every
-// float operation rounds on its own (no contraction on this path)
+// 8 channel values -> cpad bf16 (channels at and above in_ch are zero)
+void store_px(c10::BFloat16* o, const float* f, int64_t cpad) {
+  for (int64_t c = 0; c < cpad; ++c) o[c] = c10::BFloat16(f[c]);
+}
+
 std::vector<Tensor> synth_tiles(const Tensor& idx, int64_t seed, int64_t classes, int64_t in_ch, int64_t tile,
                                 int64_t dims, int64_t grid, double k, const Tensor& palette, int64_t cpad) {
-  TORCH_CHECK(dims == 2 || dims == 3, "dims must be 2 or 3");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  TORCH_CHECK(classes >= 1 && palette.numel() == classes * in_ch, "palette must be [classes][in_ch]");
-  const Tensor ix = idx.to(at::kLong).contiguous();
+  checks::synth_tiles(idx, classes, in_ch, tile, dims, grid, palette, cpad);
+  const Tensor ix = idx.contiguous(), pal = palette.contiguous();
   const int64_t B = ix.numel();
   const int64_t S = dims == 3 ? tile * tile * tile : tile * tile;
   std::vector<int64_t> ys = {B};
   for (int i = 0; i < dims; ++i) ys.push_back(tile);
-  Tensor y = at::empty(ys, idx.options().dtype(at::kLong));
+  Tensor y = at::empty(ys, idx.options());
   std::vector<int64_t> xs = ys;
   xs.push_back(cpad);
   Tensor x = at::empty(xs, idx.options().dtype(at::kBFloat16));
-  const Tensor pal = palette.to(at::kFloat).contiguous();
   const float* pp = pal.data_ptr<float>();
   const int64_t* ip = ix.data_ptr<int64_t>();
   int64_t* yp = y.data_ptr<int64_t>();
   auto* xp = x.data_ptr<c10::BFloat16>();
   const uint32_t skey = mix32((uint32_t)(seed & 0xffffffff) ^ 0x9E3779B9u);
   const float kf = (float)k;
+  const int64_t g = grid;
   at::parallel_for(0, B * S, 4096, [&](int64_t s0, int64_t s1) {
     for (int64_t e = s0; e < s1; ++e) {
       const int64_t b = e / S, p = e - b * S;
-      const int w = (int)(p % tile), h = (int)((p / tile) % tile), d = dims == 3 ? (int)(p / tile / tile) : 0;
-      const int cw = (int)((w * grid) / tile), ch = (int)((h * grid) / tile), cd = (int)((d * grid) / tile);
+      const int64_t w = p % tile, h = (p / tile) % tile, d = dims == 3 ? p / tile / tile : 0;
       const uint32_t key = mix32(skey ^ (uint32_t)ip[b]);
-      const uint32_t cell = (uint32_t)((cd * grid + ch) * grid + cw);
+      const uint32_t cell = (uint32_t)((d * g / tile * g + h * g / tile) * g + w * g / tile);
       const int lab = (int)(mix32(key ^ mix32(cell + 0x632BE5ABu)) % (uint32_t)classes);
       yp[e] = lab;
-      for (int c = 0; c < cpad; ++c) {
-        float v = 0.f;
-        if (c < in_ch) {
-          const uint32_t base = key ^ mix32((uint32_t)(p * 8 + c) + 0x1B873593u);
-          volatile float s = u24(mix32(base));
-          s = s + u24(mix32(base + 0x9E3779B9u));
-          s = s + u24(mix32(base + 2u * 0x9E3779B9u));
-          s = s + u24(mix32(base + 3u * 0x9E3779B9u));
-          volatile float t = s + -2.0f;
-          volatile float n = t * kf;
-          volatile float q = pp[lab * in_ch + c] + n;
-          v = std::fmin(std::fmax((float)q, 0.f), 1.f);
-        }
-        xp[e * cpad + c] = c10::BFloat16(v);
+      float f[8] = {};
+      for (int c = 0; c < in_ch; ++c) {
+        const uint32_t base = key ^ mix32((uint32_t)(p * 8 + c) + 0x1B873593u);
+        float s = u24(mix32(base));
+        s = add_rn(s, u24(mix32(base + 0x9E3779B9u)));
+        s = add_rn(s, u24(mix32(base + 2u * 0x9E3779B9u)));
+        s = add_rn(s, u24(mix32(base + 3u * 0x9E3779B9u)));
+        f[c] = fminf(fmaxf(add_rn(pp[lab * in_ch + c], mul_rn(add_rn(s, -2.0f), kf)), 0.f), 1.f);
       }
+      store_px(xp + e * cpad, f, cpad);
     }
   });
   return {x, y};
 }
 
 std::vector<Tensor> tile_gather(const Tensor& src, const Tensor& lab, const Tensor& idx, int64_t cpad) {
-  TORCH_CHECK(src.scalar_type() == at::kByte && lab.scalar_type() == at::kByte, "uint8 dataset");
+  checks::tile_gather(src, lab, idx, cpad);
   const int64_t in_ch = src.size(-1), N = lab.size(0);
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  const Tensor ix = idx.to(at::kLong).contiguous();
+  const Tensor ix = idx.contiguous();
   const int64_t B = ix.numel();
   const int64_t S = lab.numel() / std::max<int64_t>(1, N);
   std::vector<int64_t> ys = {B};
   for (int64_t i = 1; i < lab.dim(); ++i) ys.push_back(lab.size(i));
-  Tensor y = at::empty(ys, idx.options().dtype(at::kLong));
+  Tensor y = at::empty(ys, idx.options());
   std::vector<int64_t> xs = ys;
   xs.push_back(cpad);
   Tensor x = at::empty(xs, src.options().dtype(at::kBFloat16));
   const Tensor sc = src.contiguous(), lc = lab.contiguous();
-  const uint8_t* sp = sc.data_ptr<uint8_t>();
-  const uint8_t* lp = lc.data_ptr<uint8_t>();
+  const uint8_t *sp = sc.data_ptr<uint8_t>(), *lp = lc.data_ptr<uint8_t>();
   const int64_t* ip = ix.data_ptr<int64_t>();
   int64_t* yp = y.data_ptr<int64_t>();
   auto* xp = x.data_ptr<c10::BFloat16>();
   for (int64_t e = 0; e < B * S; ++e) {
     const int64_t b = e / S, p = e - b * S, n = ip[b];
-    const bool in_range = n >= 0 && n < N;
+    const bool in_range = n >= 0 && n < N;      // out of range reads nothing: zero image, label -100
     const int64_t q = in_range ? n * S + p : 0;
     yp[e] = in_range ? (int64_t)lp[q] : (int64_t)-100;
-    for (int c = 0; c < cpad; ++c)
-      xp[e * cpad + c] = c10::BFloat16((c < in_ch && in_range) ? (float)sp[q * in_ch + c] / 255.0f : 0.f);
+    float f[8] = {};
+    for (int c = 0; c < in_ch && in_range; ++c) f[c] = u8_unit(sp[q * in_ch + c]);
+    store_px(xp + e * cpad, f, cpad);
   }
   return {x, y};
 }
 
 // ------------------------------------------------------------------------ scene prediction
-int64_t reflect_index(int64_t i, int64_t n) {
-  if (n == 1) return 0;
-  const int64_t p = 2 * (n - 1);
-  i %= p;
-  if (i < 0) i += p;
-  return i >= n ? p - i : i;
-}
-
-// test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
-// in 0..7; the convention of crop_gather) -> the list, {0} (the plain window) without codes
-std::vector<int> codes_of(const optional<Tensor>& codes) {
-  std::vector<int> out;
+// test-time augmentation: the symmetry codes of a call -> the list, {0} (the plain window) without
+std::vector<int> codes_of(const optional<Tensor>& codes, const Tensor& like) {
+  const int64_t S = checks::codes(codes, like);
   if (!has(codes)) return {0};
-  TORCH_CHECK(codes->scalar_type() == at::kInt && codes->dim() == 1, "codes must be int32 [S]");
-  TORCH_CHECK(codes->device().is_cpu(), "codes must be on the device of the other tensors");
-  const int64_t S = codes->size(0);
-  TORCH_CHECK(S >= 1 && S <= 8, "codes: 1 <= S <= 8");
-  const Tensor cc = codes->contiguous();
-  const int* c = cc.data_ptr<int>();
-  unsigned seen = 0u;
-  for (int64_t j = 0; j < S; ++j) {
-    TORCH_CHECK(c[j] >= 0 && c[j] <= 7, "codes: values must lie in 0..7");
-    TORCH_CHECK(!(seen & (1u << c[j])), "codes: values must be distinct");
-    seen |= 1u << c[j];
-    out.push_back(c[j]);
-  }
+  const uint32_t packed = checks::pack_code_values(codes->contiguous().data_ptr<int>(), S);
+  std::vector<int> out(S);
+  for (int64_t j = 0; j < S; ++j) out[j] = (int)((packed >> (3 * j)) & 7u);
   return out;
 }
 
 Tensor window_gather(const Tensor& scene, const Tensor& origins, int64_t tile, int64_t cpad,
                      const optional<Tensor>& codes) {
-  TORCH_CHECK(scene.scalar_type() == at::kByte && scene.dim() == 3, "scene must be uint8 [H, W, Cin]");
-  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(1) == 2,
-              "origins must be int32 [B, 2] (y0, x0)");
+  checks::window_gather(scene, origins, tile, cpad);
   const int64_t H = scene.size(0), W = scene.size(1), in_ch = scene.size(2), B = origins.size(0);
-  TORCH_CHECK(H >= 1 && W >= 1 && tile >= 1, "empty scene / window");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
   const Tensor sc = scene.contiguous(), oc = origins.contiguous();
   const uint8_t* sp = sc.data_ptr<uint8_t>();
   const int* op = oc.data_ptr<int>();
-  const std::vector<int> cs = codes_of(codes);
+  const std::vector<int> cs = codes_of(codes, scene);
   const int64_t S = (int64_t)cs.size();
   Tensor x = at::empty({B * S, tile, tile, cpad}, scene.options().dtype(at::kBFloat16));
   auto* xp = x.data_ptr<c10::BFloat16>();
@@ -1137,288 +1105,154 @@ Tensor window_gather(const Tensor& scene, const Tensor& origins, int64_t tile, i
     const int code = cs[v - b * S];
     for (int64_t oy = 0; oy < tile; ++oy)
       for (int64_t ox = 0; ox < tile; ++ox) {
-        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
-        if (code & 2) a = tile - 1 - a;
-        if (code & 1) c = tile - 1 - c;
-        const uint8_t* q = sp + (reflect_index(op[2 * b] + a, H) * W + reflect_index(op[2 * b + 1] + c, W)) * in_ch;
-        c10::BFloat16* o = xp + ((v * tile + oy) * tile + ox) * cpad;
-        for (int64_t ch = 0; ch < cpad; ++ch) o[ch] = c10::BFloat16(ch < in_ch ? (float)q[ch] / 255.0f : 0.f);
+        const Index2<int64_t> s = d4_forward(code, tile, oy, ox);
+        const uint8_t* q = sp + (reflect_fast(op[2 * b] + s.a, H) * W + reflect_fast(op[2 * b + 1] + s.b, W)) * in_ch;
+        float f[8] = {};
+        for (int64_t ch = 0; ch < in_ch; ++ch) f[ch] = u8_unit(q[ch]);
+        store_px(xp + ((v * tile + oy) * tile + ox) * cpad, f, cpad);
       }
   }
   return x;
 }
 
 // ------------------------------------------------------------------------ augmented crops
-// csrc/data.hip crop_gather_kernel / crop_params_kernel, bit for bit (every float operation
-// rounds on its own)
-std::vector<Tensor> crop_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
-                                const Tensor& params, const optional<Tensor>& color, int64_t tile,
-                                int64_t cpad) {
-  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
-  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
-              "labels must be uint8 [pixels]");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
-              "table must be int64 [n, 3] (pixel offset, H, W)");
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4,
-              "params must be int32 [B, 4] (scene, y0, x0, code)");
-  const int64_t in_ch = scenes.size(1), B = params.size(0), n = table.size(0), P = labels.size(0);
-  TORCH_CHECK(in_ch >= 1 && in_ch <= 8 && cpad >= in_ch && cpad <= 8, "1 <= in_ch <= cpad <= 8");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  const bool has_color = has(color);
-  Tensor cc;
-  if (has_color) {
-    TORCH_CHECK(color->scalar_type() == at::kFloat && color->dim() == 2 && color->size(0) == B &&
-                color->size(1) == 2, "color must be fp32 [B, 2] (gain, bias)");
-    cc = color->contiguous();
-  }
-  const Tensor sc = scenes.contiguous(), lc = labels.contiguous(), tc = table.contiguous(),
-               pc = params.contiguous();
-  const uint8_t* sp = sc.data_ptr<uint8_t>();
-  const uint8_t* lp = lc.data_ptr<uint8_t>();
-  const int64_t* tp = tc.data_ptr<int64_t>();
-  const int* pp = pc.data_ptr<int>();
-  const float* cp = has_color ? cc.data_ptr<float>() : nullptr;
-  Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
-  Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
-  int64_t* yp = y.data_ptr<int64_t>();
-  auto* xp = x.data_ptr<c10::BFloat16>();
-  at::parallel_for(0, B * tile, 16, [&](int64_t r0, int64_t r1) {
-    for (int64_t row = r0; row < r1; ++row) {
-      const int64_t b = row / tile, oy = row - b * tile;
-      const int64_t s = pp[4 * b], y0 = pp[4 * b + 1], x0 = pp[4 * b + 2];
-      const int code = pp[4 * b + 3] & 7;
-      const bool listed = s >= 0 && s < n;
-      const int64_t off = listed ? tp[3 * s] : 0, H = listed ? tp[3 * s + 1] : 1, W = listed ? tp[3 * s + 2] : 1;
-      const bool valid = listed && H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30) && off >= 0 &&
-                         off <= P && H * W <= P - off;
-      const float gain = has_color ? cp[2 * b] : 1.f, bias = has_color ? cp[2 * b + 1] : 0.f;
-      for (int64_t ox = 0; ox < tile; ++ox) {
-        const int64_t e = row * tile + ox;
-        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
-        if (code & 2) a = tile - 1 - a;
-        if (code & 1) c = tile - 1 - c;
-        const int64_t q = valid ? off + reflect_index(y0 + a, H) * W + reflect_index(x0 + c, W) : 0;
-        yp[e] = valid ? (int64_t)lp[q] : (int64_t)-100;
-        for (int64_t ch = 0; ch < cpad; ++ch) {
-          float v = 0.f;
-          if (ch < in_ch && valid) {
-            v = (float)sp[q * in_ch + ch] / 255.0f;
-            if (has_color) {
-              volatile float m = v * gain;
-              volatile float t = m + bias;
-              v = std::fmin(std::fmax((float)t, 0.f), 1.f);
-            }
-          }
-          xp[e * cpad + ch] = c10::BFloat16(v);
-        }
-      }
-    }
-  });
-  return {x, y};
-}
-
 std::vector<Tensor> crop_params(const Tensor& idx, const Tensor& cum, const Tensor& table, int64_t seed,
                                 int64_t tile, int64_t mode, double gain_jitter, double bias_jitter) {
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3 && table.size(0) >= 1,
-              "table must be int64 [n >= 1, 3] (pixel offset, H, W)");
-  TORCH_CHECK(cum.scalar_type() == at::kLong && cum.dim() == 1 && cum.size(0) == table.size(0) + 1,
-              "cum must be int64 [n + 1]");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (none), 1 (flip) or 2 (d4)");
+  checks::params_args("crop_params", idx, cum, table, tile, mode);
   const Tensor ix = idx.contiguous(), cc = cum.contiguous(), tc = table.contiguous();
-  const int64_t B = ix.numel(), n = table.size(0);
-  const int64_t* ip = ix.data_ptr<int64_t>();
-  const int64_t* cp = cc.data_ptr<int64_t>();
-  const int64_t* tp = tc.data_ptr<int64_t>();
+  const int64_t B = ix.numel();
+  const int n = (int)table.size(0);
+  const int64_t *ip = ix.data_ptr<int64_t>(), *cp = cc.data_ptr<int64_t>(), *tp = tc.data_ptr<int64_t>();
   Tensor params = at::empty({B, 4}, idx.options().dtype(at::kInt));
   Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
   int* pp = params.data_ptr<int>();
   float* op = color.data_ptr<float>();
-  const uint32_t skey = mix32((uint32_t)(seed & 0xffffffff) ^ 0xC2B2AE35u);
-  const float gj = (float)gain_jitter, bj = (float)bias_jitter;
   for (int64_t i = 0; i < B; ++i) {
-    const uint64_t s = (uint64_t)ip[i];
-    const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
-    uint32_t r[6];
-    for (int j = 0; j < 6; ++j) r[j] = mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u);
-    const uint64_t t = ((uint64_t)r[0] * (uint64_t)cp[n]) >> 32;
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((uint64_t)cp[mid] <= t) lo = mid; else hi = mid;
-    }
-    const int64_t H = tp[3 * lo + 1], W = tp[3 * lo + 2];
-    const uint64_t ny = (uint64_t)(H > tile ? H - tile : 0) + 1u, nx = (uint64_t)(W > tile ? W - tile : 0) + 1u;
-    pp[4 * i] = (int)lo;
-    pp[4 * i + 1] = (int)(((uint64_t)r[1] * ny) >> 32);
-    pp[4 * i + 2] = (int)(((uint64_t)r[2] * nx) >> 32);
-    pp[4 * i + 3] = mode == 0 ? 0 : (int)(r[3] & (mode == 1 ? 3u : 7u));
-    for (int k = 0; k < 2; ++k) {
-      volatile float u2 = 2.0f * u24(r[4 + k]);
-      volatile float d = u2 + -1.0f;
-      volatile float m = (k == 0 ? gj : bj) * d;
-      volatile float g = 1.0f + m;
-      op[2 * i + k] = k == 0 ? (float)g : (float)m;
-    }
+    const uint32_t key = sample_key((uint32_t)(seed & 0xffffffff), (uint64_t)ip[i]);
+    const int lo = pick_scene(cp, n, draw(key, 0));
+    pp[4 * i] = lo;
+    pp[4 * i + 1] = (int)scale_draw(draw(key, 1), origin_count(tp[3 * lo + 1], tile));
+    pp[4 * i + 2] = (int)scale_draw(draw(key, 2), origin_count(tp[3 * lo + 2], tile));
+    pp[4 * i + 3] = symmetry_code(draw(key, 3), (int)mode);
+    color_jitter(draw(key, 4), draw(key, 5), (float)gain_jitter, (float)bias_jitter, op + 2 * i);
   }
   return {params, color};
 }
 
-// csrc/data.hip warp_params_kernel / warp_gather_kernel, bit for bit: 16.16 fixed-point affine
-// coordinates, bilinear image taps (every float operation rounds on its own), nearest labels
-std::vector<Tensor> warp_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+// the rows of warp_gather (arguments checked by the caller); bounded: a row must pass warp_row_valid
+std::vector<Tensor> gather_rows(const Tensor& scenes, const Tensor& labels, const Tensor& table,
                                 const Tensor& wparams, const optional<Tensor>& color, int64_t tile,
-                                int64_t cpad) {
-  TORCH_CHECK(scenes.scalar_type() == at::kByte && scenes.dim() == 2, "scenes must be uint8 [pixels, Cin]");
-  TORCH_CHECK(labels.scalar_type() == at::kByte && labels.dim() == 1 && labels.size(0) == scenes.size(0),
-              "labels must be uint8 [pixels]");
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
-              "table must be int64 [n, 3] (pixel offset, H, W)");
-  TORCH_CHECK(wparams.scalar_type() == at::kLong && wparams.dim() == 2 && wparams.size(1) == 6,
-              "wparams must be int64 [B, 6] (scene, cy, cx, code, A, Bm)");
+                                int64_t cpad, bool bounded) {
   const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0), P = labels.size(0);
-  TORCH_CHECK(cpad == 4 || cpad == 8, "cpad must be 4 or 8");
-  TORCH_CHECK(in_ch >= 1 && in_ch <= cpad, "1 <= in_ch <= cpad");
-  TORCH_CHECK(tile >= 1 && tile <= 32768, "tile out of range");
   const bool has_color = has(color);
-  Tensor cc;
-  if (has_color) {
-    TORCH_CHECK(color->scalar_type() == at::kFloat && color->dim() == 2 && color->size(0) == B &&
-                color->size(1) == 2, "color must be fp32 [B, 2] (gain, bias)");
-    cc = color->contiguous();
-  }
+  const Tensor cc = has_color ? color->contiguous() : Tensor();
   const Tensor sc = scenes.contiguous(), lc = labels.contiguous(), tc = table.contiguous(),
                wc = wparams.contiguous();
-  const uint8_t* sp = sc.data_ptr<uint8_t>();
-  const uint8_t* lp = lc.data_ptr<uint8_t>();
-  const int64_t* tp = tc.data_ptr<int64_t>();
-  const int64_t* wp = wc.data_ptr<int64_t>();
+  const uint8_t *sp = sc.data_ptr<uint8_t>(), *lp = lc.data_ptr<uint8_t>();
+  const int64_t *tp = tc.data_ptr<int64_t>(), *wp = wc.data_ptr<int64_t>();
   const float* cp = has_color ? cc.data_ptr<float>() : nullptr;
   Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
   Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
   int64_t* yp = y.data_ptr<int64_t>();
   auto* xp = x.data_ptr<c10::BFloat16>();
-  constexpr int64_t kCoef = 1LL << 20, kCentre = 1LL << 46;
   at::parallel_for(0, B * tile, 16, [&](int64_t row0, int64_t row1) {
     for (int64_t row = row0; row < row1; ++row) {
-      const int64_t b = row / tile, oy = row - b * tile;
-      const int64_t s = wp[6 * b], cy = wp[6 * b + 1], cx = wp[6 * b + 2], A = wp[6 * b + 4], Bm = wp[6 * b + 5];
-      const int code = (int)wp[6 * b + 3] & 7;
-      const bool listed = s >= 0 && s < n;
-      const int64_t off = listed ? tp[3 * s] : 0, H = listed ? tp[3 * s + 1] : 1, W = listed ? tp[3 * s + 2] : 1;
-      const bool valid = listed && H >= 1 && W >= 1 && H < (1 << 30) && W < (1 << 30) && off >= 0 &&
-                         off <= P && H * W <= P - off && A >= -kCoef && A <= kCoef && Bm >= -kCoef &&
-                         Bm <= kCoef && cy > -kCentre && cy < kCentre && cx > -kCentre && cx < kCentre;
+      const int64_t b = row / tile;
+      const int oy = (int)(row - b * tile);
+      const int64_t* w = wp + 6 * b;
+      const int64_t cy = w[1], cx = w[2];
+      const int code = (int)w[3] & 7;
+      const bool listed = w[0] >= 0 && w[0] < n;
+      const int64_t* t = tp + (listed ? 3 * w[0] : 0);
+      const int64_t off = listed ? t[0] : 0, H = listed ? t[1] : 1, W = listed ? t[2] : 1;
+      const bool valid = scene_row_valid(listed, off, H, W, P) && (!bounded || warp_row_valid(w[4], w[5], cy, cx));
+      const int A = valid ? (int)w[4] : 0, Bm = valid ? (int)w[5] : 0;
       const float gain = has_color ? cp[2 * b] : 1.f, bias = has_color ? cp[2 * b + 1] : 0.f;
-      for (int64_t ox = 0; ox < tile; ++ox) {
+      for (int ox = 0; ox < tile; ++ox) {
         const int64_t e = row * tile + ox;
-        c10::BFloat16* o = xp + e * cpad;
-        if (!valid) {
-          yp[e] = -100;
-          for (int64_t ch = 0; ch < cpad; ++ch) o[ch] = c10::BFloat16(0.f);
-          continue;
-        }
-        int64_t a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
-        if (code & 2) a = tile - 1 - a;
-        if (code & 1) c = tile - 1 - c;
-        const int64_t v2 = 2 * a - (tile - 1), u2 = 2 * c - (tile - 1);
-        const int64_t py = cy + ((Bm * u2 + A * v2) >> 1), px = cx + ((A * u2 - Bm * v2) >> 1);
-        const int64_t iy = py >> 16, ix = px >> 16;
-        const float wy = (float)(py & 65535) * (1.0f / 65536.0f), wx = (float)(px & 65535) * (1.0f / 65536.0f);
-        const int64_t r0 = off + reflect_index(iy, H) * W, r1 = off + reflect_index(iy + 1, H) * W;
-        const int64_t c0 = reflect_index(ix, W), c1 = reflect_index(ix + 1, W);
-        yp[e] = (int64_t)lp[off + reflect_index((py + 32768) >> 16, H) * W + reflect_index((px + 32768) >> 16, W)];
-        for (int64_t ch = 0; ch < cpad; ++ch) {
-          float v = 0.f;
-          if (ch < in_ch) {
+        float f[8] = {};
+        yp[e] = -100;
+        if (valid) {
+          const Index2<int> s = d4_forward(code, (int)tile, oy, ox);
+          const Index2<long long> p = warp_coord(cy, cx, A, Bm, (int)tile, s.a, s.b);
+          const int64_t iy = warp_tap(p.a), ix = warp_tap(p.b);
+          const float wy = warp_weight(p.a), wx = warp_weight(p.b);
+          const int64_t r0 = off + reflect_fast(iy, H) * W, r1 = off + reflect_fast(iy + 1, H) * W;
+          const int64_t c0 = reflect_fast(ix, W), c1 = reflect_fast(ix + 1, W);
+          for (int64_t ch = 0; ch < in_ch; ++ch) {
             const float p00 = (float)sp[(r0 + c0) * in_ch + ch], p01 = (float)sp[(r0 + c1) * in_ch + ch];
             const float p10 = (float)sp[(r1 + c0) * in_ch + ch], p11 = (float)sp[(r1 + c1) * in_ch + ch];
-            volatile float mt = (p01 - p00) * wx;
-            volatile float top = p00 + mt;
-            volatile float mb = (p11 - p10) * wx;
-            volatile float bot = p10 + mb;
-            volatile float d = bot - top;
-            volatile float mv = d * wy;
-            volatile float val = top + mv;
-            v = (float)val / 255.0f;
-            if (has_color) {
-              volatile float m = v * gain;
-              volatile float t = m + bias;
-              v = std::fmin(std::fmax((float)t, 0.f), 1.f);
-            }
+            f[ch] = div_rn(bilinear(p00, p01, p10, p11, wx, wy), 255.0f);
+            if (has_color) f[ch] = color_clamp(f[ch], gain, bias);
           }
-          o[ch] = c10::BFloat16(v);
+          yp[e] = (int64_t)lp[off + reflect_fast<int64_t>(warp_nearest(p.a), H) * W +
+                              reflect_fast<int64_t>(warp_nearest(p.b), W)];
         }
+        store_px(xp + e * cpad, f, cpad);
       }
     }
   });
   return {x, y};
+}
+
+std::vector<Tensor> warp_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+                                const Tensor& wparams, const optional<Tensor>& color, int64_t tile,
+                                int64_t cpad) {
+  checks::warp_gather(scenes, labels, table, wparams, color, tile, cpad);
+  return gather_rows(scenes, labels, table, wparams, color, tile, cpad, true);
+}
+
+// (A, Bm) = (ONE, 0), cy = (2 y0 + tile - 1) * 32768: the (y0, x0) crop bit for bit, any int32 origin
+std::vector<Tensor> crop_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+                                const Tensor& params, const optional<Tensor>& color, int64_t tile,
+                                int64_t cpad) {
+  checks::crop_gather(scenes, labels, table, params, color, tile, cpad);
+  const Tensor p = params.to(at::kLong), one = at::full_like(p.slice(1, 0, 1), 65536);
+  const Tensor w = at::cat({p.slice(1, 0, 1), (2 * p.slice(1, 1, 3) + (tile - 1)) * 32768, p.slice(1, 3, 4), one,
+                            at::zeros_like(one)}, 1);
+  return gather_rows(scenes, labels, table, w, color, tile, cpad, false);
 }
 
 std::vector<Tensor> warp_params(const Tensor& idx, const Tensor& cum, const Tensor& table, const Tensor& steps,
                                 const Tensor& rot, int64_t seed, int64_t tile, int64_t mode, double gain_jitter,
                                 double bias_jitter) {
-  TORCH_CHECK(steps.scalar_type() == at::kInt && steps.dim() == 1 && steps.size(0) >= 1 &&
-              steps.size(0) <= 65536, "steps must be int32 [S], 1 <= S <= 65536");
-  TORCH_CHECK(rot.scalar_type() == at::kInt && rot.dim() == 2 && rot.size(1) == 2 && rot.size(0) >= 1 &&
-              rot.size(0) <= 65536, "rot must be int32 [T, 2] (cos, sin), 1 <= T <= 65536");
-  // scene, code and colour are crop_params's (the same draws r0, r3, r4, r5)
-  const std::vector<Tensor> crop = crop_params(idx, cum, table, seed, tile, mode, gain_jitter, bias_jitter);
-  const Tensor ix = idx.contiguous(), tc = table.contiguous(), stc = steps.contiguous(), rc = rot.contiguous();
+  checks::warp_params(idx, cum, table, steps, rot, tile, mode);
+  const Tensor ix = idx.contiguous(), cc = cum.contiguous(), tc = table.contiguous(), stc = steps.contiguous(),
+               rc = rot.contiguous();
   const int64_t B = ix.numel(), S = steps.size(0), T = rot.size(0);
-  const int64_t* ip = ix.data_ptr<int64_t>();
-  const int64_t* tp = tc.data_ptr<int64_t>();
-  const int* stp = stc.data_ptr<int>();
-  const int* rp = rc.data_ptr<int>();
-  const int* pp = crop[0].data_ptr<int>();
+  const int n = (int)table.size(0);
+  const int64_t *ip = ix.data_ptr<int64_t>(), *cp = cc.data_ptr<int64_t>(), *tp = tc.data_ptr<int64_t>();
+  const int *stp = stc.data_ptr<int>(), *rp = rc.data_ptr<int>();
   Tensor wparams = at::empty({B, 6}, idx.options().dtype(at::kLong));
-  int64_t* wp = wparams.data_ptr<int64_t>();
-  const uint32_t skey = mix32((uint32_t)(seed & 0xffffffff) ^ 0xC2B2AE35u);
-  // 16.16 centre of an F-pixel footprint drawn from max(size - F, 0) + 1 origins (unsigned: a
-  // wild table entry wraps, as on the GPU)
-  auto centre = [](uint32_t r, int64_t size, int64_t F) {
-    const uint64_t cnt = (size > F ? (uint64_t)size - (uint64_t)F : 0u) + 1u;
-    const uint64_t o = ((uint64_t)r * cnt) >> 32;
-    return (int64_t)((2u * o + (uint64_t)F - 1u) * 32768u);
-  };
+  Tensor color = at::empty({B, 2}, idx.options().dtype(at::kFloat));
+  float* op = color.data_ptr<float>();
   for (int64_t i = 0; i < B; ++i) {
-    const uint64_t s = (uint64_t)ip[i];
-    const uint32_t key = mix32(mix32(skey ^ (uint32_t)s) ^ mix32((uint32_t)(s >> 32) + 0x85EBCA6Bu));
-    auto draw = [key](int j) { return mix32(key + (uint32_t)(j + 1) * 0x9E3779B9u); };
-    const int64_t lo = pp[4 * i], H = tp[3 * lo + 1], W = tp[3 * lo + 2];
-    const int64_t step = stp[((uint64_t)draw(6) * (uint64_t)S) >> 32];
-    const int64_t k = (int64_t)(((uint64_t)draw(7) * (uint64_t)T) >> 32);
-    const int64_t c = rp[2 * k], sn = rp[2 * k + 1];
-    const int64_t F = (tile * step + 65535) >> 16;
-    wp[6 * i] = lo;
-    wp[6 * i + 1] = centre(draw(1), H, F);
-    wp[6 * i + 2] = centre(draw(2), W, F);
-    wp[6 * i + 3] = pp[4 * i + 3];
-    wp[6 * i + 4] = (step * c + 32768) >> 16;
-    wp[6 * i + 5] = (step * sn + 32768) >> 16;
+    const uint32_t key = sample_key((uint32_t)(seed & 0xffffffff), (uint64_t)ip[i]);
+    const int lo = pick_scene(cp, n, draw(key, 0));
+    const long long step = stp[scale_draw(draw(key, 6), (uint64_t)S)];
+    const uint64_t k = scale_draw(draw(key, 7), (uint64_t)T);
+    const long long F = footprint((int)tile, step);
+    int64_t* w = wparams.data_ptr<int64_t>() + 6 * i;
+    w[0] = lo;
+    w[1] = footprint_centre(draw(key, 1), tp[3 * lo + 1], F);
+    w[2] = footprint_centre(draw(key, 2), tp[3 * lo + 2], F);
+    w[3] = symmetry_code(draw(key, 3), (int)mode);
+    w[4] = matrix_entry(step, rp[2 * k]);
+    w[5] = matrix_entry(step, rp[2 * k + 1]);
+    color_jitter(draw(key, 4), draw(key, 5), (float)gain_jitter, (float)bias_jitter, op + 2 * i);
   }
-  return {wparams, crop[1]};
+  return {wparams, color};
 }
 
 void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& origins,
                         const Tensor& win, Tensor& acc, const optional<Tensor>& bn4,
                         const optional<Tensor>& codes) {
-  TORCH_CHECK(a.dim() == 4 && a.size(1) == a.size(2) && a.scalar_type() == at::kBFloat16,
-              "a must be bf16 [B, tile, tile, C]");
-  const std::vector<int> cs = codes_of(codes);
+  const std::vector<int> cs = codes_of(codes, a);
   const int64_t S = (int64_t)cs.size();
-  TORCH_CHECK(a.size(0) % S == 0, "a must hold S views per window: [B * S, ..]");
-  const int64_t B = a.size(0) / S, tile = a.size(1), K = Wh.size(0);
-  TORCH_CHECK(origins.scalar_type() == at::kInt && origins.dim() == 2 && origins.size(0) == B &&
-              origins.size(1) == 2, "origins must be int32 [B, 2] (y0, x0)");
-  TORCH_CHECK(win.scalar_type() == at::kFloat && win.dim() == 1 && win.size(0) == tile,
-              "win must be fp32 [tile]");
-  TORCH_CHECK(acc.scalar_type() == at::kFloat && acc.is_contiguous() && acc.dim() == 3 &&
-              acc.size(2) == 4 * ((K + 4) / 4), "acc must be fp32 [H, W, 4 * ceil((K + 1) / 4)]");
-  const int64_t C = a.size(3);
-  TORCH_CHECK(K >= 1 && K <= 16 && (C == 8 || C == 16 || C == 32 || C == 64) && Wh.numel() == K * C,
-              "head kernel: unsupported (C, K)");
+  checks::head_predict_accum(a, Wh, bh, origins, win, acc, S);
+  TORCH_CHECK(acc.is_contiguous(), "acc must be contiguous");
+  const int64_t B = a.size(0) / S, tile = a.size(1), K = Wh.size(0), C = a.size(3);
+  TORCH_CHECK(K >= 1 && K <= 16 && (C == 8 || C == 16 || C == 32 || C == 64), "head kernel: unsupported (C, K)");
   const int64_t H = acc.size(0), W = acc.size(1), KA = acc.size(2);
   const Tensor A = head_act(a, bn4, 1);
   const Tensor l = (at::matmul(A, f32(Wh).reshape({K, -1}).t()) + f32(bh).reshape({K})).contiguous();
@@ -1440,10 +1274,8 @@ void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, con
         if (sx < 0 || sx >= W || w2 == 0.f) continue;
         float sum[16];
         for (int64_t j = 0; j < S; ++j) {
-          const int code = cs[j];
-          const int64_t ia = (code & 2) ? tile - 1 - wa : wa, ib = (code & 1) ? tile - 1 - wb : wb;
-          const int64_t oy = (code & 4) ? ib : ia, ox = (code & 4) ? ia : ib;
-          const float* z = lp + (((b * S + j) * tile + oy) * tile + ox) * K;
+          const Index2<int64_t> o = d4_inverse(cs[j], tile, wa, wb);
+          const float* z = lp + (((b * S + j) * tile + o.a) * tile + o.b) * K;
           float m = z[0], e[16], se = 0.f;
           for (int64_t k = 1; k < K; ++k) m = std::max(m, z[k]);
           for (int64_t k = 0; k < K; ++k) {
@@ -1462,8 +1294,7 @@ void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, con
 
 std::vector<Tensor> scene_finalize(const Tensor& acc, int64_t K, const optional<Tensor>& labels,
                                    int64_t ignore_index) {
-  TORCH_CHECK(acc.scalar_type() == at::kFloat && acc.dim() == 3, "acc must be fp32 [H, W, KA]");
-  TORCH_CHECK(K >= 1 && K <= 16 && K <= acc.size(2), "1 <= K <= min(16, KA)");
+  checks::scene_finalize(acc, K, labels);
   const int64_t H = acc.size(0), W = acc.size(1), KA = acc.size(2);
   const Tensor ac = acc.contiguous();
   const float* ap = ac.data_ptr<float>();
@@ -1474,8 +1305,6 @@ std::vector<Tensor> scene_finalize(const Tensor& acc, int64_t K, const optional<
   Tensor lc;
   const uint8_t* lp = nullptr;
   if (has(labels)) {
-    TORCH_CHECK(labels->scalar_type() == at::kByte && labels->dim() == 2 && labels->size(0) == H &&
-                labels->size(1) == W, "labels must be uint8 [H, W]");
     lc = labels->contiguous();
     lp = lc.data_ptr<uint8_t>();
   }

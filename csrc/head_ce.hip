@@ -23,6 +23,7 @@
 // channel-split kernels then multiply by a table of ones, the C = 32 kernels are instantiated
 // without the factor (WT = false) — the same bits either way.
 #include "common.h"
+#include "data_math.h"
 #include "ops.h"
 
 namespace ddlpc {
@@ -1020,10 +1021,9 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const bf16_t* __restri
 // channels above K keep their bits, every other pixel is not touched.
 // a [B * S][tile][tile][C] holds S views of every window, window-major, view j of a window
 // predicted under symmetry code j of `codes` (test-time augmentation; 3 bits per code, code j at
-// bits 3 j; the convention of crop_gather / window_gather: network-side pixel (oy, ox) is
-// window-frame pixel (wa, wb) = (oy, ox); code & 4: swap; code & 2: wa = tile - 1 - wa;
-// code & 1: wb = tile - 1 - wb).  A call without codes is S = 1, code 0.  One thread owns one
-// WINDOW-FRAME pixel (wa, wb) of one window: it reads its S activations through the inverse
+// bits 3 j; the index map of crop_gather / window_gather, d4_forward of data_math.h).  A call
+// without codes is S = 1, code 0.  One thread owns one WINDOW-FRAME pixel (wa, wb) of one
+// window: it reads its S activations through the inverse (d4_inverse)
 // map, computes the S softmaxes (e_jk = exp(logit - max), se_j their sum), sums the views
 // before the last in ascending j (r_k = sum_{j < S - 1} (w2 / S) / se_j * e_jk, an fma chain
 // from -0) and does ONE read-modify-write of the scene pixel: acc[.., k] =
@@ -1065,9 +1065,8 @@ __global__ __launch_bounds__(256) void head_predict_accum_kernel(
     // view j -> z = exp(logit - max), ws = (w2 / S) / sum(z)
     auto view = [&](int j) {
       const int code = (int)((codes >> (3 * j)) & 7u);
-      const int ia = (code & 2) ? tile - 1 - wa : wa;
-      const int ib = (code & 1) ? tile - 1 - wb : wb;
-      const int oy = (code & 4) ? ib : ia, ox = (code & 4) ? ia : ib;
+      const Index2<int> o = d4_inverse(code, tile, wa, wb);
+      const int oy = o.a, ox = o.b;
       const long long q = (((long long)b * S + j) * tile + oy) * tile + ox;
       // up to 32 channels (64 bytes) of the pixel are requested before their first use: four
       // loads in flight per thread instead of logits_of's one (the same sums in the same

@@ -64,12 +64,6 @@ __global__ __launch_bounds__(64) void sched_scalars_kernel(float* __restrict__ s
   if (threadIdx.x == 0) sched_scalars(s, a, red[0]);
 }
 
-// a product that stays one rounding (never the multiply of a contracted FMA)
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
 // The Adam update of misc.hip's adam_kernel with a clipped gradient and either weight decay.
 // Per element, with c = scal[5], ss = scal[1], inv = scal[2], dec = scal[6]:
 //     gc = g c                                  (one rounding; c = 1 leaves g as it is)

@@ -5,11 +5,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define DDLPC_HD __host__ __device__
-#else
-#define DDLPC_HD
-#endif
+#include "hd.h"
 
 namespace ddlpc {
 

@@ -16,30 +16,19 @@
 //     counted per workgroup in LDS, then added to HBM with integer atomics (integer sums do
 //     not depend on their order: reproducible).
 #include "common.h"
+#include "data_math.h"
 #include "ops.h"
 
 namespace ddlpc {
 
 namespace {
 
-// Window b under symmetry code c (test-time augmentation; the convention of crop_gather,
-// data.hip: network-side pixel (oy, ox) reads window-frame pixel (a, b) = (oy, ox); c & 4:
-// swap a, b; c & 2: a = tile - 1 - a; c & 1: b = tile - 1 - b; scene pixel (y0 + a, x0 + b),
-// mirrored).  Output [B * S, tile, tile, cpad], window-major: row b * S + j is window b under
-// code j of `codes` (3 bits per code, code j at bits 3 j; a kernel argument, no device read).
-// One workgroup per kWinBS^2 block of one view's output pixels, lanes along ox: every output
-// row segment is one 16-byte store per lane.  Codes without bit 4 read the scene row forwards
-// or backwards (coalesced).  Transposing codes: scene COLUMN = f(oy), scene ROW = f(ox); with
-// LDS_T the block's scene pixels are read with lanes along the scene row into LDS as raw
-// bytes, s[ox][oy] (rows padded to kWinBS + 1: the transposed 8-byte read is conflict-free
-// per 32-lane half), and the output phase reads s transposed; without it adjacent lanes read
-// scene pixels W * in_ch bytes apart (the A/B of scripts/predict_micro.py, docs/PERF.md).
-// The code is uniform in a workgroup: no branch below diverges inside a wave.
+// Window b under symmetry code c (test-time augmentation): network-side pixel (oy, ox) reads
+// scene pixel (y0 + a, x0 + b), (a, b) = d4_forward (data_math.h; spelled out below), mirrored.
+// Output [B * S, tile, tile, cpad], window-major: row b * S + j is window b under code j of
+// `codes` (3 bits per code, code j at bits 3 j; a kernel argument, no device read).  Work split and
+// LDS staging are crop_gather_kernel's (data.hip); LDS_T's A/B: scripts/predict_micro.py.
 constexpr int kWinBS = 32;
-
-DDLPC_DEVICE int reflect_in(int i, int n) {
-  return (unsigned)i < (unsigned)n ? i : reflect_index(i, n);
-}
 
 template <bool LDS_T>
 __global__ __launch_bounds__(256) void window_gather_kernel(
@@ -71,7 +60,7 @@ __global__ __launch_bounds__(256) void window_gather_kernel(
       if (ox < tile && oy < tile) {
         const int a = (code & 2) ? tile - 1 - ox : ox;
         const int c = (code & 1) ? tile - 1 - oy : oy;
-        s_px[r][lx] = load(reflect_in(y0 + a, H), reflect_in(x0 + c, W));
+        s_px[r][lx] = load(reflect_fast(y0 + a, H), reflect_fast(x0 + c, W));
       }
     }
     __syncthreads();
@@ -86,13 +75,13 @@ __global__ __launch_bounds__(256) void window_gather_kernel(
       int a = (code & 4) ? ox : oy, c = (code & 4) ? oy : ox;
       if (code & 2) a = tile - 1 - a;
       if (code & 1) c = tile - 1 - c;
-      px = load(reflect_in(y0 + a, H), reflect_in(x0 + c, W));
+      px = load(reflect_fast(y0 + a, H), reflect_fast(x0 + c, W));
     }
     const uint32_t w[2] = {px.x, px.y};
     float f[8];
 #pragma unroll
     for (int ch = 0; ch < 8; ++ch)
-      f[ch] = ch < in_ch ? __fdiv_rn((float)((w[ch >> 2] >> (8 * (ch & 3))) & 0xffu), 255.0f) : 0.f;
+      f[ch] = ch < in_ch ? u8_unit((w[ch >> 2] >> (8 * (ch & 3))) & 0xffu) : 0.f;
     const long long e = ((long long)v * tile + oy) * tile + ox;
     if (cpad == 8) {
       reinterpret_cast<uint4*>(x)[e] = pack8(f);

@@ -92,6 +92,21 @@ def check_gather(device, tile, in_ch, cpad):
     assert len(seen) == 8
 
 
+def check_far_origins(device):
+    """Origins at and beyond +-2^30 (any int32 origin is accepted; y0 + a still fits an int): the
+    scene is mirrored many periods away, as the numpy twin cuts it, on both backends."""
+    tile, in_ch = 24, 3
+    shapes = [(5, 7), (16, 23)]
+    scenes, labels, table = packed(shapes, in_ch, 5, device)
+    far = 1 << 30
+    origins = [(far, -far), (far + 5, far + 3), (-far - 7, far), (3, far + 11), (-far, -2)]
+    rows = [(k, y0, x0, code) for code in range(8) for k in range(2) for y0, x0 in origins]
+    params = torch.tensor(rows, dtype=torch.int32, device=device)
+    x, y = ops().crop_gather(scenes, labels, table, params, None, tile, 8)
+    assert_batch_equals_twin(x, y, scenes, labels, table, params, None, tile, in_ch)
+    assert bool((y >= 0).all())                                      # every row was read
+
+
 def check_gather_rejects(device):
     scenes, labels, table = packed([(9, 9)], 3, 0, device)
     p = torch.zeros(2, 4, dtype=torch.int32, device=device)

@@ -14,6 +14,10 @@ def test_crop_gather_matches_numpy_oracle(tile, in_ch, cpad):
     cc.check_gather(DEV, tile, in_ch, cpad)
 
 
+def test_crop_gather_far_origins():
+    cc.check_far_origins(DEV)
+
+
 def test_crop_gather_rejects_bad_arguments():
     cc.check_gather_rejects(DEV)
 

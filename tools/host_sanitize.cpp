@@ -9,6 +9,9 @@
 //   convt_wgrad_plan, convt_bwd_fused_ok / convt_bwd_fused_splits: kernel, splits and the
 //                     32-bit buffer-descriptor span bounds of the transposed-conv gradients
 //   bn_bwd_reduce_blocks, reduce_rows_chunks, reduce_rows_scatter_tmp, head_supported
+// and the host side of csrc/data_math.h, the input pipeline's recipe (the text the kernels and
+// the CPU twins both run): mirror index, D4 maps, scene choice, and the warp's fixed-point
+// coordinates at the extremes its validity predicate admits (no signed overflow: UBSan)
 // over the geometry range the U-Net uses (2-D 8^2..1024^2, 3-D 8^3..128^3, batch 1..256), the
 // U-Net's channel pairs in both directions, BN groups 1 / 2 / 4, with and without the
 // prologues and the BN-backward epilogue, at 8, 248 and 256 CUs, asserting the invariants the
@@ -29,6 +32,9 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <climits>
+
+#include "../csrc/data_math.h"
 #include "../csrc/ops.h"
 
 using namespace ddlpc;
@@ -354,6 +360,103 @@ static void sweep_reductions() {
   EXPECT(!head_supported(7, 6), "head rejects C %% 8 != 0");
 }
 
+// ------------------------------------------------------------------ data_math.h
+// the mirror by walking |i| steps between the two edges (i is first reduced by whole periods)
+static long long walk_mirror(long long i, long long n) {
+  if (n == 1) return 0;
+  long long steps = (i < 0 ? -i : i) % (2 * (n - 1)), pos = 0, dir = 1;
+  for (; steps > 0; --steps) {
+    if (pos + dir < 0 || pos + dir >= n) dir = -dir;
+    pos += dir;
+  }
+  return pos;
+}
+
+template <typename I>
+static void check_reflect(I i, I n) {
+  const I r = reflect_index(i, n);
+  EXPECT(r == (I)walk_mirror(i, n) && reflect_fast(i, n) == r, "reflect(%lld, %lld) = %lld", (long long)i,
+         (long long)n, (long long)r);
+}
+
+// the largest scene side, 2^30 - 1: an index of at most one period folds at most once
+static void check_big_reflect(int i) {
+  const long long n = (1 << 30) - 1, m = i < 0 ? -(long long)i : i;
+  EXPECT(m < 2 * (n - 1) && reflect_fast(i, (int)n) == (m < n ? m : 2 * (n - 1) - m), "reflect(%d, 2^30 - 1)", i);
+}
+
+static void sweep_data_math() {
+  for (int n = 1; n <= 9; ++n) {
+    for (int i = -40; i <= 40; ++i) { check_reflect<int>(i, n); check_reflect<int64_t>(i, n); }
+    for (int d = -3; d <= 3; ++d)
+      for (int sign : {-1, 1}) {
+        check_reflect<int>(sign * ((1 << 30) + d), n);
+        check_reflect<int64_t>(sign * ((1LL << 30) + d), n);
+        check_big_reflect(sign * ((1 << 30) + d));
+      }
+  }
+  for (int code = 0; code < 8; ++code)
+    for (int tile : {1, 2, 33})
+      for (int oy = 0; oy < tile; ++oy)
+        for (int ox = 0; ox < tile; ++ox) {
+          const Index2<int> f = d4_forward(code, tile, oy, ox);
+          const Index2<int> g = d4_inverse(code, tile, f.a, f.b);
+          EXPECT(f.a >= 0 && f.a < tile && f.b >= 0 && f.b < tile && g.a == oy && g.b == ox,
+                 "d4 code %d tile %d (%d, %d) -> (%d, %d) -> (%d, %d)", code, tile, oy, ox, f.a, f.b, g.a, g.b);
+          const Index2<int64_t> f64 = d4_forward<int64_t>(code, tile, oy, ox);
+          EXPECT(f64.a == f.a && f64.b == f.b, "d4 int64 code %d", code);
+        }
+  // pick_scene at every boundary of the cumulative table: the draw r0 with (r0 * total) >> 32 == t
+  const int64_t cum[] = {0, 1, 2, 7, 12, 1000, 1LL << 31, (1LL << 32) - 1};
+  const int n = (int)(sizeof(cum) / sizeof(cum[0])) - 1;
+  for (int k = 0; k <= n; ++k)
+    for (int64_t t : {cum[k], cum[k] - 1}) {
+      if (t < 0 || t >= cum[n]) continue;
+      const uint32_t r0 = (uint32_t)((((unsigned __int128)t << 32) + cum[n] - 1) / cum[n]);
+      EXPECT((int64_t)scale_draw(r0, (uint64_t)cum[n]) == t, "draw for t=%lld", (long long)t);
+      const int lo = pick_scene(cum, n, r0);
+      EXPECT(lo >= 0 && lo < n && cum[lo] <= t && t < cum[lo + 1], "pick_scene t=%lld -> %d", (long long)t, lo);
+    }
+  EXPECT(pick_scene(cum, n, 0u) == 0 && pick_scene(cum, n, 0xffffffffu) == n - 1, "pick_scene ends");
+  // the crop origin draw and the footprint centre on the largest scene
+  const long long big = (1LL << 30) - 1;
+  for (long long span : {1LL, 32768LL, big, big + 5})
+    for (uint32_t r : {0u, 1u, 0x80000000u, 0xffffffffu}) {
+      const uint64_t cnt = origin_count(big, span), o = scale_draw(r, cnt);
+      EXPECT(cnt == (uint64_t)(big > span ? big - span : 0) + 1 && o < cnt,
+             "origin draw r=%u span=%lld -> %llu of %llu", r, span, (unsigned long long)o, (unsigned long long)cnt);
+      const long long c = footprint_centre(r, big, span);
+      EXPECT(c == (2 * (long long)o + span - 1) * 32768 && c > -kCentre && c < kCentre, "centre %lld", c);
+    }
+  EXPECT(footprint(32768, INT_MAX) == (1LL << 30) && footprint(1, 65536) == 1, "footprint");
+  EXPECT(matrix_entry(INT_MAX, 65536) == INT_MAX && matrix_entry(INT_MAX, -65536) == -(long long)INT_MAX,
+         "matrix entry");
+  (void)footprint_centre(0xffffffffu, -1, LLONG_MAX);      // wild table entries wrap, unsigned
+  (void)footprint_centre(0xffffffffu, LLONG_MIN, 1);
+  // the warp coordinate at the extremes warp_row_valid admits: far inside int64, taps inside int
+  const int tile = 32768;
+  EXPECT(warp_row_valid(kCoef, -kCoef, kCentre - 1, 1 - kCentre) && !warp_row_valid(kCoef + 1, 0, 0, 0) &&
+         !warp_row_valid(0, -kCoef - 1, 0, 0) && !warp_row_valid(0, 0, kCentre, 0) && !warp_row_valid(0, 0, 0, -kCentre),
+         "warp_row_valid bounds");
+  for (long long cy : {kCentre - 1, 1 - kCentre})
+    for (long long cx : {kCentre - 1, 1 - kCentre})
+      for (int A : {(int)kCoef, -(int)kCoef})
+        for (int Bm : {(int)kCoef, -(int)kCoef})
+          for (int a : {0, tile - 1})
+            for (int b : {0, tile - 1}) {
+              const Index2<long long> p = warp_coord(cy, cx, A, Bm, tile, a, b);
+              for (long long q : {p.a, p.b}) {
+                EXPECT(q > -(kCentre + (1LL << 36)) && q < kCentre + (1LL << 36), "warp coordinate %lld", q);
+                EXPECT((q >> 16) >= INT_MIN && (q >> 16) + 1 <= INT_MAX && warp_tap(q) == (q >> 16) &&
+                       warp_nearest(q) == ((q + 32768) >> 16), "tap of %lld", q);
+                const float w = warp_weight(q);
+                EXPECT(w >= 0.f && w < 1.f && (long long)(w * 65536.0f) == (q & 65535), "weight of %lld", q);
+                check_big_reflect(warp_tap(q));
+                check_big_reflect(warp_tap(q) + 1);
+              }
+            }
+}
+
 // ------------------------------------------------------------------ the plan table
 // Part 1: every conv3_fwd / conv3_wgrad / convt_wgrad / convt_bwd_fused shape of CASES_8 and
 // CASES_0 in tests/test_kernels_exact_gpu.py (its "dgrad" cases in conv3_fwd's own terms: the
@@ -551,6 +654,7 @@ int main(int argc, char** argv) {
   sweep_wgrad();
   sweep_convt();
   sweep_reductions();
+  sweep_data_math();
   std::printf("host_sanitize: %lld planner checks passed (ASan + UBSan)\n", g_checks);
   return 0;
 }
