@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "data_checks.h"
+#include "tail_checks.h"
 #include "ops.h"
 #include "optim_math.h"
 
@@ -157,9 +158,7 @@ int num_cus() { return std::max(8, phys_cus() - g_cu_reserve); }
 
 // fp64 column sums of an fp32 [R][N] partial slab (deterministic two-pass reduction)
 at::Tensor reduce_rows(const at::Tensor& partial, int64_t R, int64_t N) {
-  // reduce_rows_launch's multi-level loop has one scratch region for its intermediate passes:
-  // above 64^3 rows a second intermediate pass would read and write it at once
-  TORCH_CHECK(R >= 0 && R <= 262144, "reduce_rows: at most 262144 rows");
+  checks::reduce_rows(partial, R, N);
   auto dopts = partial.options().dtype(at::kDouble);
   at::Tensor sums = at::empty({N}, dopts);
   const int RC = reduce_rows_chunks((int)R);
@@ -184,22 +183,9 @@ void sum_slab(const at::Tensor& slab, int R, long long N, at::Tensor& dst, int m
 // A = N / (T * B)
 void reduce_rows_scatter(const at::Tensor& slab, int64_t R, int64_t N, at::Tensor& dst, int64_t mode,
                          int64_t T, int64_t B, bool accumulate, int64_t ld) {
-  CHECK_DEV(slab); CHECK_F32(slab); CHECK_CONTIG(slab);
-  CHECK_F32(dst); CHECK_CONTIG(dst);
-  TORCH_CHECK(slab.device() == dst.device(), "reduce_rows_scatter: slab and dst on different devices");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "reduce_rows_scatter: mode must be 0, 1 or 2");
-  TORCH_CHECK(R >= 0 && R <= INT32_MAX && N >= 0, "reduce_rows_scatter: bad R / N");
-  TORCH_CHECK(ld == -1 || ld >= N, "reduce_rows_scatter: ld must be -1 or at least N");
-  TORCH_CHECK(dst.numel() == N, "reduce_rows_scatter: dst must hold exactly N elements");
-  int64_t A = 0;
-  if (mode != 2) {
-    TORCH_CHECK(T > 0 && B > 0 && T <= INT32_MAX && B <= INT32_MAX && N % (T * B) == 0,
-                "reduce_rows_scatter: N must be A * T * B");
-    A = N / (T * B);
-  }
+  CHECK_DEV(slab);
+  const int64_t A = checks::reduce_rows_scatter(slab, R, N, dst, mode, T, B, ld);
   if (R == 0 || N == 0) return;
-  const int64_t stride = ld < 0 ? N : ld;
-  TORCH_CHECK(slab.numel() >= (R - 1) * stride + N, "reduce_rows_scatter: slab shorter than (R - 1) * ld + N");
   c10::DeviceGuard guard(slab.device());
   sum_slab(slab, (int)R, N, dst, (int)mode, (int)A, (int)T, (int)B, accumulate, ld);
 }
@@ -232,14 +218,10 @@ BnGrad bn_grad_from_rows(const at::Tensor& partial, int nb, int C, double count,
   return r;
 }
 
-// an arena slot (optional): the pointer to column aoff of row 0 and the row stride, for
-// `groups` rows of (mean | unbiased var) = 2C floats each
-std::pair<float*, long long> arena_slot(const c10::optional<at::Tensor>& arena, int64_t groups,
-                                        int64_t aoff, int64_t C) {
+// an arena slot (optional, checked by checks::arena_arg): the pointer to column aoff of row 0
+// and the row stride
+std::pair<float*, long long> arena_slot(const c10::optional<at::Tensor>& arena, int64_t aoff) {
   if (!has(arena)) return {nullptr, 0};
-  CHECK_F32(*arena);
-  TORCH_CHECK(arena->dim() == 2 && arena->size(0) >= groups && arena->stride(1) == 1 &&
-              aoff + 2 * C <= arena->size(1), "arena [rows >= groups][>= aoff + 2C]");
   return {arena->data_ptr<float>() + aoff, (long long)arena->stride(0)};
 }
 
@@ -498,7 +480,8 @@ at::Tensor bn_finalize(const at::Tensor& partial, double count, const at::Tensor
                        const at::Tensor& beta, at::Tensor running_mean, at::Tensor running_var,
                        double momentum, double eps, bool update_running,
                        const c10::optional<at::Tensor>& nbt) {
-  CHECK_F32(partial); CHECK_F32(gamma); CHECK_F32(beta);
+  CHECK_DEV(partial); CHECK_CONTIG(partial); CHECK_CONTIG(gamma); CHECK_CONTIG(beta);
+  checks::bn_finalize(partial, gamma, beta, running_mean, running_var, nbt);
   c10::DeviceGuard guard(partial.device());
   const int C = (int)gamma.numel();
   const int P = (int)(partial.numel() / (2 * C));
@@ -524,12 +507,9 @@ at::Tensor bn_finalize(const at::Tensor& partial, double count, const at::Tensor
 // deferred BatchNorm running-statistics updates, in micro-batch order (see reduce.hip)
 void bn_running_apply(at::Tensor running_mean, at::Tensor running_var, const at::Tensor& slots,
                       double momentum, const c10::optional<at::Tensor>& nbt) {
-  // slots: [K][2C] rows of (mean | unbiased var), any row stride (a column slice of a
-  // per-micro-batch arena), rows contiguous
-  CHECK_F32(running_mean); CHECK_F32(running_var); CHECK_F32(slots);
+  CHECK_DEV(slots);
+  checks::bn_running_apply(running_mean, running_var, slots, nbt);
   const int C = (int)running_mean.numel();
-  TORCH_CHECK(running_var.numel() == C && slots.dim() == 2 && slots.size(1) == 2 * C &&
-              slots.stride(1) == 1, "slots [K][2C] with contiguous rows");
   c10::DeviceGuard guard(slots.device());
   const int K = (int)slots.size(0);
   if (K == 0) return;
@@ -543,10 +523,9 @@ void bn_running_apply(at::Tensor running_mean, at::Tensor running_var, const at:
 // (running_mean*, running_var*, nbt* | 0, C | arena column << 32), arena rows 0..K-1
 void bn_running_apply_all(const at::Tensor& entries, const at::Tensor& arena, int64_t K,
                           int64_t maxC, double momentum) {
-  TORCH_CHECK(entries.scalar_type() == at::kLong && entries.is_contiguous() && entries.dim() == 2 &&
-              entries.size(1) == 4, "entries [L][4] int64");
-  CHECK_F32(arena);
-  TORCH_CHECK(arena.dim() == 2 && arena.stride(1) == 1 && arena.size(0) >= K, "arena [rows >= K][cols]");
+  CHECK_DEV(arena); CHECK_CONTIG(entries);
+  checks::bn_running_apply_all(entries, arena, K, maxC);
+  TORCH_CHECK(entries.size(0) <= 65535, "bn_running_apply_all: at most 65535 layers");
   c10::DeviceGuard guard(arena.device());
   if (K == 0 || entries.size(0) == 0) return;
   bn_running_apply_all_launch(entries.data_ptr<int64_t>(), (int)entries.size(0), (int)maxC,
@@ -556,12 +535,12 @@ void bn_running_apply_all(const at::Tensor& entries, const at::Tensor& arena, in
 
 std::vector<at::Tensor> bn_relu_apply(const at::Tensor& y, const at::Tensor& stats4, bool pool,
                                       bool full) {
-  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y);
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_CONTIG(stats4);
+  checks::bn_relu_apply(y, stats4, pool, full);
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
   TORCH_CHECK(g.C % 8 == 0, "C must be a multiple of 8");
   const float* s = stats4.data_ptr<float>();
-  TORCH_CHECK(full || pool, "bn_relu_apply: full=False only with pool (deferred skip)");
   at::Tensor a = full ? at::empty_like(y) : at::empty({0}, y.options());
   at::Tensor p;
   if (pool) p = at::empty(pooled_shape(g), y.options());
@@ -580,17 +559,16 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
                                     const c10::optional<at::Tensor>& dgamma_out,
                                     const c10::optional<at::Tensor>& dbeta_out,
                                     const c10::optional<at::Tensor>& partial_in) {
-  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y);
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_CONTIG(stats4); CHECK_CONTIG(gamma);
+  checks::bn_backward(dA, dP, y, stats4, gamma, gscale, dgamma_out, dbeta_out, partial_in);
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
   const int C = g.C;
   TORCH_CHECK(C % 8 == 0, "C must be a multiple of 8");
   const bool hasA = has(dA);
   const bool hasP = has(dP);
-  TORCH_CHECK(hasA || hasP, "bn_backward needs dA or dP");
-  if (hasA) { CHECK_CONTIG(*dA); CHECK_BF16(*dA); }
-  if (hasP) { CHECK_CONTIG(*dP); CHECK_BF16(*dP); }
-  if (!hasP) TORCH_CHECK(hasA, "dA required without pool");
+  if (hasA) CHECK_CONTIG(*dA);
+  if (hasP) CHECK_CONTIG(*dP);
   const float* s = stats4.data_ptr<float>();
   const float* gs = fptr_opt(gscale);
   const long long items = (long long)g.N * (hasP ? (g.dims == 3 ? g.D / 2 : 1) * (g.H / 2) * (g.W / 2)
@@ -604,9 +582,7 @@ std::vector<at::Tensor> bn_backward(const c10::optional<at::Tensor>& dA,
   int nb;
   at::Tensor partial;
   if (pre) {
-    TORCH_CHECK(!hasP && !has(gscale), "precomputed BN partials: no pool / grad scale");
-    CHECK_F32(*partial_in); CHECK_CONTIG(*partial_in);
-    TORCH_CHECK(partial_in->numel() % (2 * C) == 0, "partial rows must be [R][2][C]");
+    CHECK_CONTIG(*partial_in);
     partial = *partial_in;
     nb = (int)(partial.numel() / (2 * C));
   } else {
@@ -633,11 +609,11 @@ std::vector<at::Tensor> bn_grad_coefs(const at::Tensor& partial, const at::Tenso
                                       const at::Tensor& stats4, const at::Tensor& gamma,
                                       const c10::optional<at::Tensor>& dgamma_out,
                                       const c10::optional<at::Tensor>& dbeta_out) {
-  CHECK_F32(partial); CHECK_CONTIG(partial); CHECK_F32(gamma);
+  CHECK_DEV(partial); CHECK_CONTIG(partial); CHECK_CONTIG(stats4); CHECK_CONTIG(gamma);
+  checks::bn_grad_coefs(partial, y, stats4, gamma, dgamma_out, dbeta_out);
   c10::DeviceGuard guard(partial.device());
   const Geo g = geo_of(y);
   const int C = g.C;
-  TORCH_CHECK(partial.numel() % (2 * C) == 0 && partial.numel() > 0, "partial rows must be [R][2][C]");
   const int nb = (int)(partial.numel() / (2 * C));
   const double count = (double)g.N * g.D * g.H * g.W;
   const BnGrad r = bn_grad_from_rows(partial, nb, C, count, gamma, stats4.data_ptr<float>() + C,
@@ -653,11 +629,10 @@ std::vector<at::Tensor> bn_grad_coefs(const at::Tensor& partial, const at::Tenso
 at::Tensor bn_group_finalize(const at::Tensor& y, int64_t groups, const at::Tensor& gamma,
                              const at::Tensor& beta, double eps,
                              const c10::optional<at::Tensor>& arena, int64_t aoff) {
-  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y); CHECK_F32(gamma); CHECK_F32(beta);
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_CONTIG(gamma); CHECK_CONTIG(beta);
+  checks::bn_group_finalize(y, groups, gamma, beta, arena, aoff);
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
-  TORCH_CHECK(groups >= 1 && groups <= 1024 && g.N % groups == 0,
-              "bn_group_finalize: 1 <= groups <= 1024 dividing the batch");
   TORCH_CHECK(bn_group_supported(g.dims, false, g.D, g.H, g.W, g.C),
               "bn_group_finalize: C / 8 must be a power of two <= 256");
   const long long gpix = (long long)(g.N / groups) * g.D * g.H * g.W;
@@ -665,7 +640,7 @@ at::Tensor bn_group_finalize(const at::Tensor& y, int64_t groups, const at::Tens
   auto fopts = y.options().dtype(at::kFloat);
   at::Tensor part = at::empty({groups, nb, 2, g.C}, fopts);
   at::Tensor st = at::empty({groups, 4, g.C}, fopts);
-  const auto [ap, astride] = arena_slot(arena, groups, aoff, g.C);
+  const auto [ap, astride] = arena_slot(arena, aoff);
   bn_group_stats_finalize_launch(bptr(y), (int)groups, gpix, g.C, gamma.data_ptr<float>(),
                                  beta.data_ptr<float>(), (float)eps, st.data_ptr<float>(), ap,
                                  astride, part.data_ptr<float>(), nb, cur_stream());
@@ -677,14 +652,13 @@ at::Tensor bn_group_finalize(const at::Tensor& y, int64_t groups, const at::Tens
 at::Tensor bn_group_finalize_rows(const at::Tensor& partial, int64_t groups, double count,
                                   const at::Tensor& gamma, const at::Tensor& beta, double eps,
                                   const c10::optional<at::Tensor>& arena, int64_t aoff) {
-  CHECK_DEV(partial); CHECK_F32(partial); CHECK_CONTIG(partial); CHECK_F32(gamma); CHECK_F32(beta);
+  CHECK_DEV(partial); CHECK_CONTIG(partial); CHECK_CONTIG(gamma); CHECK_CONTIG(beta);
+  checks::bn_group_finalize_rows(partial, groups, gamma, beta, arena, aoff);
   c10::DeviceGuard guard(partial.device());
   const int64_t C = gamma.numel();
-  TORCH_CHECK(groups >= 1 && groups <= 1024 && partial.numel() % (groups * 2 * C) == 0,
-              "bn_group_finalize_rows: partial [groups * nb][2][C]");
   const int nb = (int)(partial.numel() / (groups * 2 * C));
   at::Tensor st = at::empty({groups, 4, C}, partial.options());
-  const auto [ap, astride] = arena_slot(arena, groups, aoff, C);
+  const auto [ap, astride] = arena_slot(arena, aoff);
   bn_group_finalize_rows_launch(partial.data_ptr<float>(), nb, (int)groups, (long long)count, (int)C,
                                 gamma.data_ptr<float>(), beta.data_ptr<float>(), (float)eps,
                                 st.data_ptr<float>(), ap, astride, cur_stream());
@@ -693,11 +667,10 @@ at::Tensor bn_group_finalize_rows(const at::Tensor& partial, int64_t groups, dou
 
 std::vector<at::Tensor> bn_group_apply(const at::Tensor& y, const at::Tensor& stats4,
                                        int64_t groups, bool pool) {
-  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y); CHECK_F32(stats4); CHECK_CONTIG(stats4);
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_CONTIG(stats4);
+  checks::bn_group_apply(y, stats4, groups, pool);
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
-  TORCH_CHECK(groups >= 1 && g.N % groups == 0 && stats4.numel() == groups * 4 * g.C,
-              "bn_group_apply: stats4 [groups][4][C], groups dividing the batch");
   TORCH_CHECK(g.C % 8 == 0, "C must be a multiple of 8");
   at::Tensor a = at::empty_like(y);
   at::Tensor p;
@@ -720,17 +693,15 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
                                           const c10::optional<at::Tensor>& dgamma_out,
                                           const c10::optional<at::Tensor>& dbeta_out,
                                           const c10::optional<at::Tensor>& partial) {
-  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y); CHECK_F32(stats4); CHECK_CONTIG(stats4);
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_CONTIG(stats4); CHECK_CONTIG(gamma);
+  checks::bn_group_backward(dA, dP, y, stats4, gamma, groups, dgamma_out, dbeta_out, partial);
   c10::DeviceGuard guard(y.device());
   const Geo g = geo_of(y);
   const int C = g.C;
   const bool hasA = has(dA);
   const bool hasP = has(dP);
-  TORCH_CHECK(hasA || hasP, "bn_group_backward needs dA or dP");
-  if (hasA) { CHECK_CONTIG(*dA); CHECK_BF16(*dA); TORCH_CHECK(dA->numel() == y.numel(), "dA shape"); }
-  if (hasP) { CHECK_CONTIG(*dP); CHECK_BF16(*dP); TORCH_CHECK(dP->numel() * (g.dims == 3 ? 8 : 4) == y.numel(), "dP shape"); }
-  TORCH_CHECK(groups >= 1 && groups <= 1024 && g.N % groups == 0 && stats4.numel() == groups * 4 * C,
-              "bn_group_backward: stats4 [groups][4][C], 1 <= groups <= 1024 dividing the batch");
+  if (hasA) CHECK_CONTIG(*dA);
+  if (hasP) CHECK_CONTIG(*dP);
   TORCH_CHECK(bn_group_supported(g.dims, hasP, g.D, g.H, g.W, C),
               "bn_group_backward: C / 8 a power of two <= 256, even dims with pool");
   const int Ng = g.N / (int)groups;
@@ -738,12 +709,9 @@ std::vector<at::Tensor> bn_group_backward(const c10::optional<at::Tensor>& dA,
                                                 : (long long)g.D * g.H * g.W);
   // partial: group-major rows [groups * nb][2][C] of (sum dyh, sum dyh * xhat) from the
   // data-gradient conv's BN-backward epilogue (conv3_fwd with bnb_y and groups)
-  const bool have_part = has(partial);
-  if (have_part) {
-    CHECK_F32(*partial); CHECK_CONTIG(*partial);
-    TORCH_CHECK(!hasP && partial->numel() % (groups * 2 * C) == 0,
-                "bn_group_backward: partial [groups * nb][2][C], no pooled gradient");
-  }
+  // (an empty tensor means no rows, as for bn_backward and on the CPU)
+  const bool have_part = has(partial) && partial->numel() > 0;
+  if (have_part) CHECK_CONTIG(*partial);
   const int nb = have_part ? (int)(partial->numel() / (groups * 2 * C)) : bn_group_bwd_rows(items, (int)groups);
   auto fopts = y.options().dtype(at::kFloat);
   at::Tensor part = have_part ? *partial : at::empty({groups, nb, 2, C}, fopts);

@@ -15,6 +15,7 @@
 // and the three coefficients of dY = gamma*invstd*(dyhat - mean(dyhat) - xhat*mean(dyhat*xhat));
 // bn_bwd_apply writes dY (bf16) for the conv's data/weight gradients.  The pool backward
 // and the skip-gradient sum are folded into both passes (no unpooled tensor is stored).
+#include "bn_math.h"
 #include "common.h"
 #include "ops.h"
 
@@ -679,24 +680,38 @@ __global__ __launch_bounds__(256) void bn_group_stats_kernel(const bf16_t* __res
 // Finalize kernels: grid (channel chunks of 64, groups), 256 threads = 64 channels x 4 row
 // lanes.  A thread sums rows r = lane4, lane4 + 4, ... of its (group, channel) in fp64 —
 // loads coalesced across the 64 channels (the partial rows are [groups][nb][2][C]) — and the
-// 4 row lanes combine in LDS in a fixed order (deterministic).
+// 4 row lanes combine in LDS in a fixed order (deterministic): -> true in the one thread per
+// (group g, channel c) that then holds the sums
 constexpr int kFR = 4;                       // row lanes per finalize workgroup
-DDLPC_DEVICE void group_rows_sum(const float* __restrict__ rows, int nb, int C, int c, int rl,
+DDLPC_DEVICE bool group_rows_sum(const float* __restrict__ partial, int nb, int C, int c, int g,
                                  double& a, double& b) {
+  __shared__ double red[2][kFR][64];
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const float* rows = partial + (long long)g * nb * 2 * C;
   a = 0.0; b = 0.0;
-  int r = rl;
-  for (; r + 3 * kFR < nb; r += 4 * kFR) {   // four rows' loads in flight
-    const float a0 = rows[(long long)r * 2 * C + c], b0 = rows[(long long)r * 2 * C + C + c];
-    const float a1 = rows[(long long)(r + kFR) * 2 * C + c], b1 = rows[(long long)(r + kFR) * 2 * C + C + c];
-    const float a2 = rows[(long long)(r + 2 * kFR) * 2 * C + c], b2 = rows[(long long)(r + 2 * kFR) * 2 * C + C + c];
-    const float a3 = rows[(long long)(r + 3 * kFR) * 2 * C + c], b3 = rows[(long long)(r + 3 * kFR) * 2 * C + C + c];
-    a += (double)a0 + (double)a1 + (double)a2 + (double)a3;
-    b += (double)b0 + (double)b1 + (double)b2 + (double)b3;
+  if (c < C) {
+    int r = rl;
+    for (; r + 3 * kFR < nb; r += 4 * kFR) {   // four rows' loads in flight
+      const float a0 = rows[(long long)r * 2 * C + c], b0 = rows[(long long)r * 2 * C + C + c];
+      const float a1 = rows[(long long)(r + kFR) * 2 * C + c], b1 = rows[(long long)(r + kFR) * 2 * C + C + c];
+      const float a2 = rows[(long long)(r + 2 * kFR) * 2 * C + c], b2 = rows[(long long)(r + 2 * kFR) * 2 * C + C + c];
+      const float a3 = rows[(long long)(r + 3 * kFR) * 2 * C + c], b3 = rows[(long long)(r + 3 * kFR) * 2 * C + C + c];
+      a += (double)a0 + (double)a1 + (double)a2 + (double)a3;
+      b += (double)b0 + (double)b1 + (double)b2 + (double)b3;
+    }
+    for (; r < nb; r += kFR) {
+      a += (double)rows[(long long)r * 2 * C + c];
+      b += (double)rows[(long long)r * 2 * C + C + c];
+    }
   }
-  for (; r < nb; r += kFR) {
-    a += (double)rows[(long long)r * 2 * C + c];
-    b += (double)rows[(long long)r * 2 * C + C + c];
-  }
+  red[0][rl][cl] = a;
+  red[1][rl][cl] = b;
+  __syncthreads();
+  if (rl != 0 || c >= C) return false;
+  a = 0.0; b = 0.0;
+#pragma unroll
+  for (int k = 0; k < kFR; ++k) { a += red[0][k][cl]; b += red[1][k][cl]; }
+  return true;
 }
 
 // stats4 per group (mean | invstd | scale | shift), and the group's (mean, unbiased var) into
@@ -706,32 +721,18 @@ __global__ __launch_bounds__(64 * kFR) void bn_group_finalize_kernel(
     const float* __restrict__ partial, int nb, int groups, int C, double count,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     float* __restrict__ out4, float* __restrict__ arena, long long astride) {
-  __shared__ double red[2][kFR][64];
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl, g = blockIdx.y;
-  double a = 0.0, b = 0.0;
-  if (c < C) group_rows_sum(partial + (long long)g * nb * 2 * C, nb, C, c, rl, a, b);
-  red[0][rl][cl] = a;
-  red[1][rl][cl] = b;
-  __syncthreads();
-  if (rl != 0 || c >= C) return;
-  a = 0.0; b = 0.0;
-#pragma unroll
-  for (int k = 0; k < kFR; ++k) { a += red[0][k][cl]; b += red[1][k][cl]; }
-  const double mean = a / count;
-  double var = b / count - mean * mean;
-  if (var < 0) var = 0;
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * inv;
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = blockIdx.y;
+  double a, b;
+  if (!group_rows_sum(partial, nb, C, c, g, a, b)) return;
+  const BnStats4 s = bn_stats4(a, b, count, gamma[c], beta[c], eps);
   float* o = out4 + (long long)g * 4 * C;
-  o[c] = (float)mean;
-  o[C + c] = inv;
-  o[2 * C + c] = sc;
-  o[3 * C + c] = beta[c] - (float)mean * sc;
+  o[c] = s.mean;
+  o[C + c] = s.invstd;
+  o[2 * C + c] = s.scale;
+  o[3 * C + c] = s.shift;
   if (arena != nullptr) {
-    const double unb = count > 1 ? var * count / (count - 1) : var;
-    arena[g * astride + c] = (float)mean;
-    arena[g * astride + C + c] = (float)unb;
+    arena[g * astride + c] = s.mean;
+    arena[g * astride + C + c] = bn_unbiased_var(s.var, count);
   }
 }
 
@@ -741,25 +742,17 @@ __global__ __launch_bounds__(64 * kFR) void bn_group_grad_finalize_kernel(
     const float* __restrict__ partial, int nb, int groups, int C, double count,
     const float* __restrict__ gamma, const float* __restrict__ stats4, double* __restrict__ gsum,
     float* __restrict__ coefs, const float* __restrict__ dscale) {
-  __shared__ double red[2][kFR][64];
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl, g = blockIdx.y;
-  double a = 0.0, b = 0.0;
-  if (c < C) group_rows_sum(partial + (long long)g * nb * 2 * C, nb, C, c, rl, a, b);
-  red[0][rl][cl] = a;
-  red[1][rl][cl] = b;
-  __syncthreads();
-  if (rl != 0 || c >= C) return;
-  a = 0.0; b = 0.0;
-#pragma unroll
-  for (int k = 0; k < kFR; ++k) { a += red[0][k][cl]; b += red[1][k][cl]; }
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = blockIdx.y;
+  double a, b;
+  if (!group_rows_sum(partial, nb, C, c, g, a, b)) return;
   if (dscale != nullptr) { a *= (double)dscale[0]; b *= (double)dscale[0]; }
   gsum[((long long)g * 2) * C + c] = a;
   gsum[((long long)g * 2 + 1) * C + c] = b;
+  const BnGradTerms t = bn_grad_terms(a, b, count, gamma[c], stats4[(long long)g * 4 * C + C + c]);
   float* k = coefs + (long long)g * 3 * C;
-  k[c] = gamma[c] * stats4[(long long)g * 4 * C + C + c];
-  k[C + c] = (float)(a / count);
-  k[2 * C + c] = (float)(b / count);
+  k[c] = t.k;
+  k[C + c] = t.m1;
+  k[2 * C + c] = t.m2;
 }
 
 // ... then dbeta / dgamma = those sums over the groups in group order (deterministic)

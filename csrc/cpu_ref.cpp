@@ -23,9 +23,11 @@
 #include <string>
 #include <vector>
 
+#include "bn_math.h"
 #include "data_checks.h"
 #include "data_math.h"
 #include "optim_math.h"
+#include "tail_checks.h"
 
 namespace ddlpc {
 void set_last_path(const std::string& path);    // bindings.cpp: torch.ops.ddlpc.last_path
@@ -36,7 +38,7 @@ namespace ddlpc_cpu {
 
 using at::Tensor;
 using c10::optional;
-using namespace ddlpc;      // data_math.h, data_checks.h, optim_math.h
+using namespace ddlpc;      // the *_math.h and *_checks.h headers
 
 namespace {
 
@@ -175,24 +177,38 @@ BnBwd bn_terms(const Tensor& dtf, const Tensor& yf, const Tensor& s4, int64_t G,
 }
 
 // sums [G][2][C] (fp64) -> coefficients [G][3][C] = (gamma * invstd, s1 / count, s2 / count);
-// dbeta / dgamma = sums over the groups, written or accumulated
+// dbeta / dgamma = sums over the groups in group order, written or accumulated
 Tensor bn_coefs(const Tensor& sums, const Tensor& s4, const Tensor& gamma, int64_t G, double count,
                 Tensor& dgamma, Tensor& dbeta, bool into) {
   const int64_t C = gamma.numel();
-  const Tensor inv = s4row(s4, G, C, 1).reshape({G, C});
-  const Tensor k = gamma.reshape({1, C}) * inv;
-  const Tensor m1 = (sums.select(1, 0) / count).to(at::kFloat);
-  const Tensor m2 = (sums.select(1, 1) / count).to(at::kFloat);
-  const Tensor db = sums.select(1, 0).sum(0).to(at::kFloat);
-  const Tensor dgm = sums.select(1, 1).sum(0).to(at::kFloat);
-  if (into) {
-    dbeta.add_(db);
-    dgamma.add_(dgm);
-  } else {
-    dbeta = db;
-    dgamma = dgm;
+  const Tensor S = sums.contiguous(), gc = gamma.contiguous(), inv = s4row(s4, G, C, 1).reshape({G, C}).contiguous();
+  Tensor coefs = at::empty({G, 3, C}, gamma.options());
+  if (!into) {
+    dbeta = at::empty({C}, gamma.options());
+    dgamma = at::empty({C}, gamma.options());
   }
-  return at::stack({k, m1, m2}, 1);          // [G][3][C]
+  TORCH_INTERNAL_ASSERT(dgamma.is_contiguous() && dbeta.is_contiguous() && dgamma.numel() == C && dbeta.numel() == C);
+  const double* s = S.data_ptr<double>();
+  const float* g = gc.data_ptr<float>();
+  const float* iv = inv.data_ptr<float>();
+  float* k = coefs.data_ptr<float>();
+  float* db = dbeta.data_ptr<float>();
+  float* dg = dgamma.data_ptr<float>();
+  for (int64_t c = 0; c < C; ++c) {
+    double a = 0.0, b = 0.0;
+    for (int64_t q = 0; q < G; ++q) {
+      const double t1 = s[(q * 2) * C + c], t2 = s[(q * 2 + 1) * C + c];
+      const BnGradTerms t = bn_grad_terms(t1, t2, count, g[c], iv[q * C + c]);
+      k[(q * 3) * C + c] = t.k;
+      k[(q * 3 + 1) * C + c] = t.m1;
+      k[(q * 3 + 2) * C + c] = t.m2;
+      a += t1;
+      b += t2;
+    }
+    db[c] = into ? db[c] + (float)a : (float)a;
+    dg[c] = into ? dg[c] + (float)b : (float)b;
+  }
+  return coefs;
 }
 
 Tensor bn_apply_coefs(const BnBwd& t, const Tensor& coefs, const Tensor& like, int64_t G) {
@@ -302,57 +318,26 @@ std::vector<Tensor> conv3_bwd32(const Tensor& dy, const Tensor& y, const Tensor&
 }
 
 Tensor reduce_rows(const Tensor& partial, int64_t R, int64_t N) {
+  checks::reduce_rows(partial, R, N);
   return partial.reshape({R, N}).to(at::kDouble).sum(0);
 }
 
-// dst[perm(j)] (+)= float(fp64 sum over R rows of slab[r * ld + j]): the three row-count
-// regimes of reduce_rows_scatter_launch (csrc/reduce.hip) in their summation orders, and its
-// layouts: mode 0 [co][tap][ci] -> [co][ci][tap], mode 1 [ci][(sub, co)] -> [ci][co][sub],
-// mode 2 identity
+// dst[slab_perm(j)] (+)= float(fp64 sum over R rows of slab[r * ld + j]), in the summation
+// order of the row-count regime reduce_rows_scatter_launch (csrc/reduce.hip) takes for R
 void reduce_rows_scatter(const Tensor& slab, int64_t R, int64_t N, Tensor& dst, int64_t mode, int64_t T,
                          int64_t B, bool accumulate, int64_t ld) {
-  TORCH_CHECK(slab.scalar_type() == at::kFloat && slab.is_contiguous(), "slab must be contiguous fp32");
-  TORCH_CHECK(dst.scalar_type() == at::kFloat && dst.is_contiguous() && dst.numel() == N,
-              "dst must be N contiguous fp32 elements");
-  TORCH_CHECK(mode >= 0 && mode <= 2 && R >= 0 && N >= 0 && (ld == -1 || ld >= N), "bad mode / R / N / ld");
-  TORCH_CHECK(mode == 2 || (T > 0 && B > 0 && N % (T * B) == 0), "N must be A * T * B");
+  checks::reduce_rows_scatter(slab, R, N, dst, mode, T, B, ld);
   if (R == 0 || N == 0) return;
-  if (ld < 0) ld = N;
-  TORCH_CHECK(slab.numel() >= (R - 1) * ld + N, "slab shorter than (R - 1) * ld + N");
   const float* in = slab.data_ptr<float>();
   float* out = dst.data_ptr<float>();
   for (int64_t j = 0; j < N; ++j) {
-    double s = 0.0;
-    if (R <= 64) {                         // one pass
-      for (int64_t r = 0; r < R; ++r) s += (double)in[r * ld + j];
-    } else if (R <= 1024) {                // wide: four interleaved row sets, added in order
-      double w[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int64_t k = 0; k < 4; ++k)
-        for (int64_t r = k; r < R; r += 4) w[k] += (double)in[r * ld + j];
-      for (int64_t k = 0; k < 4; ++k) s += w[k];
-    } else {                               // two passes: chunks of 64 rows, then the chunk sums
-      for (int64_t r0 = 0; r0 < R; r0 += 64) {
-        double c = 0.0;
-        for (int64_t r = r0; r < std::min(R, r0 + 64); ++r) c += (double)in[r * ld + j];
-        s += c;
-      }
-    }
-    int64_t d = j;
-    if (mode == 0) {                       // T = taps, B = Cin ; j = (co*T + tap)*B + ci
-      const int64_t ci = j % B, tap = (j / B) % T, co = j / (B * T);
-      d = (co * B + ci) * T + tap;
-    } else if (mode == 1) {                // T = subs, B = Cout ; j = ci*(T*B) + sub*B + co
-      const int64_t co = j % B, sub = (j / B) % T, ci = j / (B * T);
-      d = (ci * B + co) * T + sub;
-    }
-    const float v = (float)s;
+    const int64_t d = slab_perm((int)mode, j, (int)T, (int)B);
+    const float v = (float)slab_column_sum(in, R, ld < 0 ? N : ld, j);
     out[d] = accumulate ? out[d] + v : v;
   }
 }
 
 // ------------------------------------------------------------------------ BatchNorm
-float mom_update(float running, float x, float m) { return m * x + (1.f - m) * running; }
-
 // stats4 [G][4][C] from fp64 sums [G][2][C]; arena rows (mean | unbiased var) if given
 Tensor stats4_from_sums(const Tensor& sums, double count, const Tensor& gamma, const Tensor& beta,
                         double eps, int64_t G, float* arena, int64_t astride) {
@@ -366,19 +351,15 @@ Tensor stats4_from_sums(const Tensor& sums, double count, const Tensor& gamma, c
   float* o = st.data_ptr<float>();
   for (int64_t k = 0; k < G; ++k)
     for (int64_t c = 0; c < C; ++c) {
-      const double mean = s[(k * 2) * C + c] / count;
-      double var = s[(k * 2 + 1) * C + c] / count - mean * mean;
-      if (var < 0) var = 0;
-      const float inv = (float)(1.0 / std::sqrt(var + (double)(float)eps));   // eps as fp32, as the GPU kernels take it
-      const float sc = g[c] * inv;
+      const BnStats4 r = bn_stats4(s[(k * 2) * C + c], s[(k * 2 + 1) * C + c], count, g[c], b[c], (float)eps);
       float* ok = o + k * 4 * C;
-      ok[c] = (float)mean;
-      ok[C + c] = inv;
-      ok[2 * C + c] = sc;
-      ok[3 * C + c] = b[c] - (float)mean * sc;
+      ok[c] = r.mean;
+      ok[C + c] = r.invstd;
+      ok[2 * C + c] = r.scale;
+      ok[3 * C + c] = r.shift;
       if (arena != nullptr) {
-        arena[k * astride + c] = (float)mean;
-        arena[k * astride + C + c] = (float)(count > 1 ? var * count / (count - 1) : var);
+        arena[k * astride + c] = r.mean;
+        arena[k * astride + C + c] = bn_unbiased_var(r.var, count);
       }
     }
   return st;
@@ -387,6 +368,7 @@ Tensor stats4_from_sums(const Tensor& sums, double count, const Tensor& gamma, c
 Tensor bn_finalize(const Tensor& partial, double count, const Tensor& gamma, const Tensor& beta,
                    Tensor running_mean, Tensor running_var, double momentum, double eps,
                    bool update_running, const optional<Tensor>& nbt) {
+  checks::bn_finalize(partial, gamma, beta, running_mean, running_var, nbt);
   ddlpc::set_last_path("cpu");
   const int64_t C = gamma.numel();
   const Tensor sums = partial.reshape({-1, 2, C}).to(at::kDouble).sum(0, true);
@@ -401,8 +383,8 @@ Tensor bn_finalize(const Tensor& partial, double count, const Tensor& gamma, con
     float* rm = running_mean.data_ptr<float>();
     float* rv = running_var.data_ptr<float>();
     for (int64_t c = 0; c < C; ++c) {
-      rm[c] = mom_update(rm[c], ap[c], (float)momentum);
-      rv[c] = mom_update(rv[c], ap[C + c], (float)momentum);
+      rm[c] = bn_momentum_update(rm[c], ap[c], (float)momentum);
+      rv[c] = bn_momentum_update(rv[c], ap[C + c], (float)momentum);
     }
     if (has(nbt)) nbt->add_(1);
   }
@@ -411,23 +393,16 @@ Tensor bn_finalize(const Tensor& partial, double count, const Tensor& gamma, con
 
 void bn_running_apply(Tensor running_mean, Tensor running_var, const Tensor& slots, double momentum,
                       const optional<Tensor>& nbt) {
-  const int64_t C = running_mean.numel(), K = slots.size(0);
-  TORCH_CHECK(slots.dim() == 2 && slots.size(1) == 2 * C && slots.stride(1) == 1, "slots [K][2C]");
-  float* rm = running_mean.data_ptr<float>();
-  float* rv = running_var.data_ptr<float>();
-  const float* s = slots.data_ptr<float>();
-  for (int64_t c = 0; c < C; ++c)
-    for (int64_t k = 0; k < K; ++k) {
-      rm[c] = mom_update(rm[c], s[k * slots.stride(0) + c], (float)momentum);
-      rv[c] = mom_update(rv[c], s[k * slots.stride(0) + C + c], (float)momentum);
-    }
+  checks::bn_running_apply(running_mean, running_var, slots, nbt);
+  const int C = (int)running_mean.numel(), K = (int)slots.size(0);
+  for (int c = 0; c < C; ++c)
+    bn_running_apply_channel(running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
+                             slots.data_ptr<float>(), K, C, slots.stride(0), c, (float)momentum);
   if (has(nbt) && K > 0) nbt->add_(K);
 }
 
 void bn_running_apply_all(const Tensor& entries, const Tensor& arena, int64_t K, int64_t maxC, double momentum) {
-  (void)maxC;
-  TORCH_CHECK(entries.scalar_type() == at::kLong && entries.dim() == 2 && entries.size(1) == 4,
-              "entries [L][4] int64");
+  checks::bn_running_apply_all(entries, arena, K, maxC);
   const Tensor e = entries.contiguous();
   const int64_t* ep = e.data_ptr<int64_t>();
   const float* a = arena.data_ptr<float>();
@@ -436,14 +411,10 @@ void bn_running_apply_all(const Tensor& entries, const Tensor& arena, int64_t K,
     float* rm = reinterpret_cast<float*>(ep[4 * l]);
     float* rv = reinterpret_cast<float*>(ep[4 * l + 1]);
     int64_t* nb = reinterpret_cast<int64_t*>(ep[4 * l + 2]);
-    const int64_t C = ep[4 * l + 3] & 0xffffffff;
+    const int C = (int)(ep[4 * l + 3] & 0xffffffff);
     const int64_t off = (int64_t)((uint64_t)ep[4 * l + 3] >> 32);
     if (nb != nullptr) nb[0] += K;
-    for (int64_t c = 0; c < C; ++c)
-      for (int64_t k = 0; k < K; ++k) {
-        rm[c] = mom_update(rm[c], a[k * stride + off + c], (float)momentum);
-        rv[c] = mom_update(rv[c], a[k * stride + off + C + c], (float)momentum);
-      }
+    for (int c = 0; c < C; ++c) bn_running_apply_channel(rm, rv, a + off, (int)K, C, stride, c, (float)momentum);
   }
 }
 
@@ -456,7 +427,7 @@ std::vector<Tensor> relu_apply_groups(const Tensor& y, const Tensor& stats4, int
 }
 
 std::vector<Tensor> bn_relu_apply(const Tensor& y, const Tensor& stats4, bool pool, bool full) {
-  TORCH_CHECK(full || pool, "bn_relu_apply: full=False only with pool (deferred skip)");
+  checks::bn_relu_apply(y, stats4, pool, full);
   return relu_apply_groups(y, stats4, 1, pool, full);
 }
 
@@ -467,7 +438,6 @@ std::vector<Tensor> bn_backward_groups(const optional<Tensor>& dA, const optiona
                                        const optional<Tensor>& partial) {
   ddlpc::set_last_path("cpu");
   const bool hasA = has(dA), hasP = has(dP);
-  TORCH_CHECK(hasA || hasP, "bn_backward needs dA or dP");
   const int64_t C = y.size(-1);
   const Tensor yf = f32(y);
   Tensor dt = hasA ? f32(*dA).reshape(y.sizes()) : at::zeros_like(yf);
@@ -495,14 +465,14 @@ std::vector<Tensor> bn_backward(const optional<Tensor>& dA, const optional<Tenso
                                 const Tensor& stats4, const Tensor& gamma, const optional<Tensor>& gscale,
                                 const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
                                 const optional<Tensor>& partial_in) {
-  if (has_nonempty(partial_in))
-    TORCH_CHECK(!has(dP) && !has(gscale), "precomputed BN partials: no pool / grad scale");
+  checks::bn_backward(dA, dP, y, stats4, gamma, gscale, dgamma_out, dbeta_out, partial_in);
   return bn_backward_groups(dA, dP, y, stats4, gamma, 1, scalar_or(gscale, 1.0), dgamma_out, dbeta_out,
                             partial_in);
 }
 
 std::vector<Tensor> bn_grad_coefs(const Tensor& partial, const Tensor& y, const Tensor& stats4, const Tensor& gamma,
                                   const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out) {
+  checks::bn_grad_coefs(partial, y, stats4, gamma, dgamma_out, dbeta_out);
   ddlpc::set_last_path("cpu");
   const int64_t C = y.size(-1);
   const Tensor sums = partial.reshape({1, -1, 2, C}).to(at::kDouble).sum(1);
@@ -514,12 +484,12 @@ std::vector<Tensor> bn_grad_coefs(const Tensor& partial, const Tensor& y, const 
 
 std::pair<float*, int64_t> arena_ptr(const optional<Tensor>& arena, int64_t aoff) {
   if (!has(arena)) return {nullptr, 0};
-  TORCH_CHECK(arena->dim() == 2 && arena->stride(1) == 1, "arena [rows][cols]");
   return {arena->data_ptr<float>() + aoff, arena->stride(0)};
 }
 
 Tensor bn_group_finalize(const Tensor& y, int64_t groups, const Tensor& gamma, const Tensor& beta, double eps,
                          const optional<Tensor>& arena, int64_t aoff) {
+  checks::bn_group_finalize(y, groups, gamma, beta, arena, aoff);
   const int64_t C = y.size(-1);
   const Tensor d = f32(y).to(at::kDouble).reshape({groups, -1, C});
   const Tensor sums = at::stack({d.sum(1), (d * d).sum(1)}, 1);
@@ -529,6 +499,7 @@ Tensor bn_group_finalize(const Tensor& y, int64_t groups, const Tensor& gamma, c
 
 Tensor bn_group_finalize_rows(const Tensor& partial, int64_t groups, double count, const Tensor& gamma,
                               const Tensor& beta, double eps, const optional<Tensor>& arena, int64_t aoff) {
+  checks::bn_group_finalize_rows(partial, groups, gamma, beta, arena, aoff);
   const int64_t C = gamma.numel();
   const Tensor sums = partial.reshape({groups, -1, 2, C}).to(at::kDouble).sum(1);
   auto ap = arena_ptr(arena, aoff);
@@ -536,6 +507,7 @@ Tensor bn_group_finalize_rows(const Tensor& partial, int64_t groups, double coun
 }
 
 std::vector<Tensor> bn_group_apply(const Tensor& y, const Tensor& stats4, int64_t groups, bool pool) {
+  checks::bn_group_apply(y, stats4, groups, pool);
   return relu_apply_groups(y, stats4, groups, pool, true);
 }
 
@@ -543,6 +515,7 @@ std::vector<Tensor> bn_group_backward(const optional<Tensor>& dA, const optional
                                       const Tensor& stats4, const Tensor& gamma, int64_t groups,
                                       const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
                                       const optional<Tensor>& partial) {
+  checks::bn_group_backward(dA, dP, y, stats4, gamma, groups, dgamma_out, dbeta_out, partial);
   return bn_backward_groups(dA, dP, y, stats4, gamma, groups, 1.0, dgamma_out, dbeta_out, partial);
 }
 

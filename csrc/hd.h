@@ -1,5 +1,6 @@
-// What the host+device texts (optim_math.h, data_math.h: one spelling for a gfx950 kernel and its
-// CPU twin, cpu_ref.cpp being plain C++) share: DDLPC_HD and fp32 operations that round on their own.
+// What the host+device texts (optim_math.h, data_math.h, bn_math.h: one spelling for a gfx950
+// kernel and its CPU twin, cpu_ref.cpp being plain C++) share: DDLPC_HD and fp32 operations that
+// round on their own.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)

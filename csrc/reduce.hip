@@ -7,6 +7,7 @@
 // FIXED order: pass 1 sums row chunks of 64 (one thread per column, coalesced across the
 // wave), pass 2 sums the chunk results.  No float atomics, so every data-parallel rank
 // computes bit-identical local gradients from identical inputs.
+#include "bn_math.h"
 #include "common.h"
 #include "ops.h"
 
@@ -14,30 +15,53 @@ namespace ddlpc {
 
 namespace {
 
-constexpr int RB = 64;   // rows per chunk
-
 template <typename T>
 __global__ void rows_chunk_sum_kernel(const T* __restrict__ in, int R, long long N,
                                       double* __restrict__ out, long long ld = -1) {
   const long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (j >= N) return;
   if (ld < 0) ld = N;
-  const int r0 = blockIdx.y * RB;
-  const int r1 = min(R, r0 + RB);
+  const int r0 = blockIdx.y * kSlabChunkRows;
+  const int r1 = min(R, r0 + kSlabChunkRows);
   double s = 0.0;
 #pragma unroll 8
   for (int r = r0; r < r1; ++r) s += (double)in[(long long)r * ld + j];
   out[(long long)blockIdx.y * N + j] = s;
 }
 
-// running <- (1 - m) running + m x, in one fixed fp32 form: the deferred (per-micro-batch
-// slot) updates of bn_running_apply_kernel reproduce the in-kernel ones bit for bit; with
-// m = 1 a slot receives x exactly
-DDLPC_DEVICE float bn_momentum_update(float running, float x, float m) {
-  return fmaf(m, x, (1.f - m) * running);
+// channel c's stats4 (mean | invstd | scale | shift) + running statistics from its fp64 sums
+DDLPC_DEVICE void stats_finalize(double s1, double s2, int c, int C, double count,
+                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                 float* running_mean, float* running_var, float momentum, float eps,
+                                 float* __restrict__ out4, int update_running) {
+  const BnStats4 s = bn_stats4(s1, s2, count, gamma[c], beta[c], eps);
+  out4[c] = s.mean;
+  out4[C + c] = s.invstd;
+  out4[2 * C + c] = s.scale;
+  out4[3 * C + c] = s.shift;
+  if (update_running) {
+    const float unb = bn_unbiased_var(s.var, count);
+    running_mean[c] = bn_momentum_update(running_mean[c], s.mean, momentum);
+    running_var[c] = bn_momentum_update(running_var[c], unb, momentum);
+  }
 }
 
-// mean / invstd / scale / shift + running statistics from fp64 (sum, sum^2)
+// channel c's dgamma, dbeta (accumulated if requested) and dY coefficients from its fp64 sums
+// (sum dyh, sum dyh*xhat); dscale: optional device factor on both sums — partials reduced at a
+// unit gradient scale
+DDLPC_DEVICE void grad_finalize(double t1, double t2, int c, int C, double count,
+                                const float* __restrict__ gamma, const float* __restrict__ invstd,
+                                float* dgamma, float* dbeta, float* coefs, int accumulate,
+                                const float* __restrict__ dscale) {
+  if (dscale != nullptr) { t1 *= (double)dscale[0]; t2 *= (double)dscale[0]; }
+  const BnGradTerms g = bn_grad_terms(t1, t2, count, gamma[c], invstd[c]);
+  dbeta[c] = accumulate ? dbeta[c] + g.dbeta : g.dbeta;
+  dgamma[c] = accumulate ? dgamma[c] + g.dgamma : g.dgamma;
+  coefs[c] = g.k;
+  coefs[C + c] = g.m1;
+  coefs[2 * C + c] = g.m2;
+}
+
 __global__ void bn_stats_finalize_kernel(const double* __restrict__ sums, int C, double count,
                                          const float* __restrict__ gamma,
                                          const float* __restrict__ beta, float* running_mean,
@@ -47,24 +71,10 @@ __global__ void bn_stats_finalize_kernel(const double* __restrict__ sums, int C,
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && update_running && nbt != nullptr) nbt[0] += 1;
   if (c >= C) return;
-  const double mean = sums[c] / count;
-  double var = sums[C + c] / count - mean * mean;
-  if (var < 0) var = 0;
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * inv;
-  out4[c] = (float)mean;
-  out4[C + c] = inv;
-  out4[2 * C + c] = sc;
-  out4[3 * C + c] = beta[c] - (float)mean * sc;
-  if (update_running) {
-    const double unb = count > 1 ? var * count / (count - 1) : var;
-    running_mean[c] = bn_momentum_update(running_mean[c], (float)mean, momentum);
-    running_var[c] = bn_momentum_update(running_var[c], (float)unb, momentum);
-  }
+  stats_finalize(sums[c], sums[C + c], c, C, count, gamma, beta, running_mean, running_var, momentum,
+                 eps, out4, update_running);
 }
 
-// dgamma, dbeta (accumulated if requested) and dY coefficients from fp64 (sum dyh, sum dyh*xhat)
-// (dscale: optional device factor on both sums — partials reduced at a unit gradient scale)
 __global__ void bn_grad_finalize_kernel(const double* __restrict__ sums, int C, double count,
                                         const float* __restrict__ gamma,
                                         const float* __restrict__ invstd, float* dgamma,
@@ -72,33 +82,15 @@ __global__ void bn_grad_finalize_kernel(const double* __restrict__ sums, int C, 
                                         const float* __restrict__ dscale) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double ds = dscale != nullptr ? (double)dscale[0] : 1.0;
-  const double t1 = sums[c] * ds, t2 = sums[C + c] * ds;
-  dbeta[c] = accumulate ? dbeta[c] + (float)t1 : (float)t1;
-  dgamma[c] = accumulate ? dgamma[c] + (float)t2 : (float)t2;
-  coefs[c] = gamma[c] * invstd[c];
-  coefs[C + c] = (float)(t1 / count);
-  coefs[2 * C + c] = (float)(t2 / count);
+  grad_finalize(sums[c], sums[C + c], c, C, count, gamma, invstd, dgamma, dbeta, coefs, accumulate, dscale);
 }
 
-// dst[perm(j)] (+)= scale * sums[j]; perm: conv slab [co][tap][ci] -> OIHW [co][ci][tap]
-// (mode 0), convT slab [ci][(sub, co)] -> IOHW [ci][co][sub] (mode 1), identity (mode 2)
+// dst[slab_perm(j)] (+)= scale * sums[j]
 __global__ void scatter_sums_kernel(const double* __restrict__ sums, long long N, float* dst,
                                     int mode, int A, int T, int B, float scale, int accumulate) {
   for (long long j = blockIdx.x * (long long)blockDim.x + threadIdx.x; j < N;
        j += (long long)gridDim.x * blockDim.x) {
-    long long d = j;
-    if (mode == 0) {          // A = Cout, T = taps, B = Cin ; j = (co*T + tap)*B + ci
-      const int ci = (int)(j % B);
-      const int tap = (int)((j / B) % T);
-      const long long co = j / ((long long)B * T);
-      d = (co * B + ci) * T + tap;
-    } else if (mode == 1) {   // A = Cin, T = subs, B = Cout ; j = ci*(T*B) + sub*B + co
-      const int co = (int)(j % B);
-      const int sub = (int)((j / B) % T);
-      const long long ci = j / ((long long)B * T);
-      d = (ci * B + co) * T + sub;
-    }
+    const long long d = slab_perm(mode, j, T, B);
     const float v = (float)sums[j] * scale;
     dst[d] = accumulate ? dst[d] + v : v;
   }
@@ -118,19 +110,18 @@ __global__ void scatter_sums_dscale_kernel(const double* __restrict__ sums, long
 // deferred running-statistics updates (concurrent micro-batch streams): K slots of
 // (batch mean, unbiased batch var) written by K forwards with momentum 1, applied here in
 // micro-batch order — the sequence of updates the K forwards would have made one by one
-__global__ void bn_running_apply_kernel(float* __restrict__ running_mean, float* __restrict__ running_var,
-                                        const float* __restrict__ slots, int K, int C, long long stride,
-                                        float momentum, int64_t* nbt) {
+DDLPC_DEVICE void running_apply(float* running_mean, float* running_var, const float* slots, int K, int C,
+                                long long stride, float momentum, int64_t* nbt) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && nbt != nullptr) nbt[0] += K;
   if (c >= C) return;
-  float rm = running_mean[c], rv = running_var[c];
-  for (int k = 0; k < K; ++k) {                   // slot k: [mean (C) | var (C)] at k * stride
-    rm = bn_momentum_update(rm, slots[k * stride + c], momentum);
-    rv = bn_momentum_update(rv, slots[k * stride + C + c], momentum);
-  }
-  running_mean[c] = rm;
-  running_var[c] = rv;
+  bn_running_apply_channel(running_mean, running_var, slots, K, C, stride, c, momentum);
+}
+
+__global__ void bn_running_apply_kernel(float* __restrict__ running_mean, float* __restrict__ running_var,
+                                        const float* __restrict__ slots, int K, int C, long long stride,
+                                        float momentum, int64_t* nbt) {
+  running_apply(running_mean, running_var, slots, K, C, stride, momentum, nbt);
 }
 
 // head gradient scale dL/count from the loss kernel's (loss, correct, count) and the incoming
@@ -154,8 +145,14 @@ __global__ void meter_add_kernel(double* __restrict__ buf, const float* __restri
 }
 
 // one block per channel: fp64 sum of P partial rows, then finalize (P <= a few thousand)
-DDLPC_DEVICE void block_sum2(double& a, double& b) {
+DDLPC_DEVICE void block_rows_sum2(const float* __restrict__ partial, int P, int C, int c, double& a,
+                                  double& b) {
   __shared__ double r1[4], r2[4];
+  a = 0.0; b = 0.0;
+  for (int r = threadIdx.x; r < P; r += 256) {
+    a += partial[(long long)r * 2 * C + c];
+    b += partial[(long long)r * 2 * C + C + c];
+  }
   a = wave_sum_d(a);
   b = wave_sum_d(b);
   if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = a; r2[threadIdx.x >> 6] = b; }
@@ -170,28 +167,12 @@ __global__ void bn_stats_rows_kernel(const float* __restrict__ partial, int P, i
                                      float eps, float* __restrict__ out4, int update_running,
                                      int64_t* nbt) {
   const int c = blockIdx.x;
-  double a = 0.0, b = 0.0;
-  for (int r = threadIdx.x; r < P; r += 256) {
-    a += partial[(long long)r * 2 * C + c];
-    b += partial[(long long)r * 2 * C + C + c];
-  }
-  block_sum2(a, b);
+  double a, b;
+  block_rows_sum2(partial, P, C, c, a, b);
   if (threadIdx.x != 0) return;
   if (c == 0 && update_running && nbt != nullptr) nbt[0] += 1;
-  const double mean = a / count;
-  double var = b / count - mean * mean;
-  if (var < 0) var = 0;
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * inv;
-  out4[c] = (float)mean;
-  out4[C + c] = inv;
-  out4[2 * C + c] = sc;
-  out4[3 * C + c] = beta[c] - (float)mean * sc;
-  if (update_running) {
-    const double unb = count > 1 ? var * count / (count - 1) : var;
-    running_mean[c] = bn_momentum_update(running_mean[c], (float)mean, momentum);
-    running_var[c] = bn_momentum_update(running_var[c], (float)unb, momentum);
-  }
+  stats_finalize(a, b, c, C, count, gamma, beta, running_mean, running_var, momentum, eps, out4,
+                 update_running);
 }
 
 __global__ void bn_grad_rows_kernel(const float* __restrict__ partial, int P, int C, double count,
@@ -199,19 +180,10 @@ __global__ void bn_grad_rows_kernel(const float* __restrict__ partial, int P, in
                                     const float* __restrict__ invstd, float* dgamma, float* dbeta,
                                     float* coefs, int accumulate, const float* __restrict__ dscale) {
   const int c = blockIdx.x;
-  double a = 0.0, b = 0.0;
-  for (int r = threadIdx.x; r < P; r += 256) {
-    a += partial[(long long)r * 2 * C + c];
-    b += partial[(long long)r * 2 * C + C + c];
-  }
-  block_sum2(a, b);
+  double a, b;
+  block_rows_sum2(partial, P, C, c, a, b);
   if (threadIdx.x != 0) return;
-  if (dscale != nullptr) { a *= (double)dscale[0]; b *= (double)dscale[0]; }
-  dbeta[c] = accumulate ? dbeta[c] + (float)a : (float)a;
-  dgamma[c] = accumulate ? dgamma[c] + (float)b : (float)b;
-  coefs[c] = gamma[c] * invstd[c];
-  coefs[C + c] = (float)(a / count);
-  coefs[2 * C + c] = (float)(b / count);
+  grad_finalize(a, b, c, C, count, gamma, invstd, dgamma, dbeta, coefs, accumulate, dscale);
 }
 
 // final pass fused with the scatter/accumulate into the destination gradient
@@ -224,18 +196,7 @@ __global__ void rows_sum_scatter_kernel(const T* __restrict__ in, int R, long lo
   double s = 0.0;
 #pragma unroll 8
   for (int r = 0; r < R; ++r) s += (double)in[(long long)r * ld + j];
-  long long d = j;
-  if (mode == 0) {
-    const int ci = (int)(j % B);
-    const int tap = (int)((j / B) % Tt);
-    const long long co = j / ((long long)B * Tt);
-    d = (co * B + ci) * Tt + tap;
-  } else if (mode == 1) {
-    const int co = (int)(j % B);
-    const int sub = (int)((j / B) % Tt);
-    const long long ci = j / ((long long)B * Tt);
-    d = (ci * B + co) * Tt + sub;
-  }
+  const long long d = slab_perm(mode, j, Tt, B);
   const float v = (float)s;
   dst[d] = accumulate ? dst[d] + v : v;
 }
@@ -248,7 +209,8 @@ __global__ void rows_sum_scatter_kernel(const T* __restrict__ in, int R, long lo
 // persistent data-gradient kernels, and a 1024-thread block (four waves on every SIMD of one
 // CU) waited for a wholly free CU — 300-570 us per launch in the two-stream trace against
 // 8-15 us alone (profiles/r5/tail_img_wgrad_main_g64_g65/)
-constexpr int kWideWaves = 4;
+// (kWideMaxRows = 1024; up to 64 rows per wave: longer serial chains lose to the two-pass form —
+// measured 22 us vs 2 x 5 us for the head's 4096-row, 198-column reduction)
 template <bool SCATTER>
 __global__ __launch_bounds__(64 * kWideWaves) void rows_sum_wide_kernel(const float* __restrict__ in, int R,
                                                                         long long N, long long ld,
@@ -270,25 +232,10 @@ __global__ __launch_bounds__(64 * kWideWaves) void rows_sum_wide_kernel(const fl
 #pragma unroll
   for (int k = 0; k < kWideWaves; ++k) t += red[k][lane];
   if (!SCATTER) { sums[j] = t; return; }
-  long long d = j;
-  if (mode == 0) {
-    const int ci = (int)(j % B);
-    const int tap = (int)((j / B) % Tt);
-    const long long co = j / ((long long)B * Tt);
-    d = (co * B + ci) * Tt + tap;
-  } else if (mode == 1) {
-    const int co = (int)(j % B);
-    const int sub = (int)((j / B) % Tt);
-    const long long ci = j / ((long long)B * Tt);
-    d = (ci * B + co) * Tt + sub;
-  }
+  const long long d = slab_perm(mode, j, Tt, B);
   const float v = (float)t;
   dst[d] = accumulate ? dst[d] + v : v;
 }
-
-// (up to 64 rows per wave: longer serial chains lose to the two-pass form — measured 22 us vs
-// 2 x 5 us for the head's 4096-row, 198-column reduction)
-constexpr int kWideMaxRows = 1024;
 
 }  // namespace
 
@@ -315,7 +262,7 @@ void reduce_rows_scatter_launch(const float* in, int R, long long N, double* tmp
                                 long long ld) {
   const unsigned gx = (unsigned)((N + 255) / 256);
   if (ld < 0) ld = N;
-  if (R <= 64) {
+  if (R <= kSlabChunkRows) {
     hipLaunchKernelGGL(rows_sum_scatter_kernel<float>, dim3(gx), dim3(256), 0, st, in, R, N, dst,
                        mode, A, T, B, accumulate ? 1 : 0, ld);
     return;
@@ -325,19 +272,19 @@ void reduce_rows_scatter_launch(const float* in, int R, long long N, double* tmp
                        R, N, ld, nullptr, dst, mode, A, T, B, accumulate ? 1 : 0);
     return;
   }
-  const int RC = (R + RB - 1) / RB;
+  const int RC = (R + kSlabChunkRows - 1) / kSlabChunkRows;
   hipLaunchKernelGGL(rows_chunk_sum_kernel<float>, dim3(gx, RC), dim3(256), 0, st, in, R, N, tmp, ld);
   hipLaunchKernelGGL(rows_sum_scatter_kernel<double>, dim3(gx), dim3(256), 0, st, tmp, RC, N, dst,
                      mode, A, T, B, accumulate ? 1 : 0, N);
 }
 
-// the caller's scratch for reduce_rows_scatter_launch: one fp64 row per RB-row chunk, read
+// the caller's scratch for reduce_rows_scatter_launch: one fp64 row per kSlabChunkRows-row chunk, read
 // only by the two-pass form above kWideMaxRows rows (0 below: tmp is never touched)
 long long reduce_rows_scatter_tmp(int R, long long N) {
-  return R > kWideMaxRows ? (long long)((R + RB - 1) / RB) * N : 0;
+  return R > kWideMaxRows ? (long long)((R + kSlabChunkRows - 1) / kSlabChunkRows) * N : 0;
 }
 
-int reduce_rows_chunks(int R) { return (R + RB - 1) / RB; }
+int reduce_rows_chunks(int R) { return (R + kSlabChunkRows - 1) / kSlabChunkRows; }
 
 // sums[N] (fp64) = sum over R rows of in[R][N]; tmp must hold reduce_rows_chunks(R) * N doubles
 void reduce_rows_launch(const float* in, int R, long long N, double* tmp, double* sums,
@@ -404,17 +351,7 @@ __global__ void bn_running_apply_all_kernel(const int64_t* __restrict__ entries,
   int64_t* nbt = reinterpret_cast<int64_t*>(e[2]);
   const int C = (int)(e[3] & 0xffffffff);
   const long long off = (long long)((uint64_t)e[3] >> 32);
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0 && nbt != nullptr) nbt[0] += K;
-  if (c >= C) return;
-  const float* slots = arena + off;
-  float rm = running_mean[c], rv = running_var[c];
-  for (int k = 0; k < K; ++k) {
-    rm = bn_momentum_update(rm, slots[k * stride + c], momentum);
-    rv = bn_momentum_update(rv, slots[k * stride + C + c], momentum);
-  }
-  running_mean[c] = rm;
-  running_var[c] = rv;
+  running_apply(running_mean, running_var, arena + off, K, C, stride, momentum, nbt);
 }
 
 void bn_running_apply_all_launch(const int64_t* entries, int L, int maxC, const float* arena, int K,

@@ -288,8 +288,9 @@ def run_backward_big(o, dev, shape, pool, seed=17):
     return path
 
 
-def run_grad_coefs(o, dev, c):
-    """bn_grad_coefs from integer rows: k bit-equal, m1 / m2 the fp64 quotient rounded once"""
+def grad_coefs_inputs(c):
+    """-> y, stats4, gamma, the fp64 reference (sums, magnitudes, k, m), the integer rows [R][2][C]
+    and the pre-filled outs"""
     shape, C, seed, R = tuple(c["shape"]), c["shape"][-1], c.get("seed", 12), c["rows"]
     y, dA = tern(shape, 0.5, seed), tern(shape, 0.5, seed + 1)
     s4, gamma = stats_of(C, seed + 3), gamma_of(C)
@@ -299,6 +300,13 @@ def run_grad_coefs(o, dev, c):
     pre = c.get("prefill")
     dg0 = (torch.arange(C, dtype=torch.float32) % 7 - 3) if pre else None
     db0 = (torch.arange(C, dtype=torch.float32) % 5 - 2) if pre else None
+    return y, s4, gamma, sums, mags, k, m, part, pre, dg0, db0
+
+
+def run_grad_coefs(o, dev, c):
+    """bn_grad_coefs from integer rows: k bit-equal, m1 / m2 the fp64 quotient rounded once"""
+    C = c["shape"][-1]
+    y, s4, gamma, sums, mags, k, m, part, pre, dg0, db0 = grad_coefs_inputs(c)
     t = lambda v: None if v is None else v.to(dev)
     coefs, dg, db = o.bn_grad_coefs(part.to(dev), y.to(dev), s4.to(dev), gamma.to(dev),
                                      dg0.clone().to(dev) if pre else None, db0.clone().to(dev) if pre else None)
@@ -392,13 +400,20 @@ def finalize_rows_case(P, C, count, seed):
     return rows.float().contiguous(), A, B
 
 
-def run_finalize(o, dev, c):
-    """bn_finalize from integer rows [P][2][C]: stats4 and the running statistics (nbt + 1)"""
+def finalize_inputs(c):
+    """-> rows [P][2][C], their exact sums A, B, gamma, beta, the running statistics before"""
     P, C, count, seed = c["P"], c["C"], c["count"], c.get("seed", 14)
     rows, A, B = finalize_rows_case(P, C, count, seed)
     g = torch.Generator().manual_seed(seed + 2)
     gamma, beta = gamma_of(C), torch.randn(C, generator=g)
     rm0, rv0 = torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5
+    return rows, A, B, gamma, beta, rm0, rv0
+
+
+def run_finalize(o, dev, c):
+    """bn_finalize from integer rows [P][2][C]: stats4 and the running statistics (nbt + 1)"""
+    count = c["count"]
+    rows, A, B, gamma, beta, rm0, rv0 = finalize_inputs(c)
     mom = 0.1
     m32 = float(torch.tensor(mom, dtype=torch.float32))
     r = finalize_ref(A, B, count, gamma, beta)
@@ -424,9 +439,8 @@ def run_finalize(o, dev, c):
 SENTINEL = -77.0
 
 
-def run_group_finalize(o, dev, c):
-    """bn_group_finalize on ternary y (channels 2 and 3 offset by 64: cancellation) and
-    bn_group_finalize_rows on the exact per-group rows: stats4, and the arena rows at aoff = 16"""
+def group_finalize_inputs(c):
+    """-> y, groups, C, seed, gamma, beta, pixels per group, the exact per-group sums A, B"""
     shape, G, seed = tuple(c["shape"]), c["groups"], c.get("seed", 15)
     C = shape[-1]
     y = tern(shape, 0.5, seed)
@@ -435,8 +449,20 @@ def run_group_finalize(o, dev, c):
     gen = torch.Generator().manual_seed(seed + 1)
     gamma, beta = gamma_of(C), torch.randn(C, generator=gen)
     yd = y.double().reshape(G, -1, C)
-    count = yd.shape[1]
-    A, B = yd.sum(1), (yd * yd).sum(1)
+    return y, G, C, seed, gamma, beta, yd.shape[1], yd.sum(1), (yd * yd).sum(1)
+
+
+def group_rows(A, B, G, R, seed):
+    """the exact per-group sums split into R integer rows each: [G * R][2][C]"""
+    rows = torch.stack([torch.stack([split_rows(A[g], R, 1.0, seed + 20 + g),
+                                     split_rows(B[g], R, 1.0, seed + 40 + g)], 1) for g in range(G)])
+    return rows.reshape(G * R, 2, -1).contiguous()
+
+
+def run_group_finalize(o, dev, c):
+    """bn_group_finalize on ternary y (channels 2 and 3 offset by 64: cancellation) and
+    bn_group_finalize_rows on the exact per-group rows: stats4, and the arena rows at aoff = 16"""
+    y, G, C, seed, gamma, beta, count, A, B = group_finalize_inputs(c)
     # the kernel's fp32 partial rows are exact: a workgroup sums about count / nb pixels
     nb = bn_group_stats_rows(count, C, G)
     assert nb == c.get("nb", nb), (c["id"], nb)
@@ -456,11 +482,8 @@ def run_group_finalize(o, dev, c):
         assert torch.equal(ar[:G, aoff:aoff + C], r["mean"].float()), fam + " arena mean"
         record(fam + " arena var", ar[:G, aoff + C:aoff + 2 * C], r["unb"], 2.0 ** -23 * r["unb"].abs())
     check("bn_group_finalize", st, arena)
-    R = 3
-    rows = torch.stack([torch.stack([split_rows(A[g], R, 1.0, seed + 20 + g),
-                                     split_rows(B[g], R, 1.0, seed + 40 + g)], 1) for g in range(G)])
     arena2 = torch.full((G + 1, cols), SENTINEL).to(dev)
-    st2 = o.bn_group_finalize_rows(rows.reshape(G * R, 2, C).contiguous().to(dev), G, float(count),
+    st2 = o.bn_group_finalize_rows(group_rows(A, B, G, 3, seed).to(dev), G, float(count),
                                    gamma.to(dev), beta.to(dev), EPS, arena2, aoff)
     check("bn_group_finalize_rows", st2, arena2)
     assert torch.equal(st2, st) and torch.equal(arena2, arena), "finalize_rows differs from finalize"
@@ -497,14 +520,9 @@ def running_case(Cs, K, exact, seed):
     return offs, arena, bufs
 
 
-def run_running(o, dev, c):
-    """bn_running_apply (per layer, a column slice of the arena) or bn_running_apply_all (entries
-    built as fused_unet.py's bn_defer_apply does): K in-order updates, nbt += K, and nothing else
-    written"""
-    Cs, K, exact, seed = c["Cs"], c["K"], c["exact"], c.get("seed", 16)
-    mom = 0.25 if exact else 0.1
-    m32 = float(torch.tensor(mom, dtype=torch.float32))
-    offs, arena0, bufs0 = running_case(Cs, K, exact, seed)
+def running_call(o, dev, c, mom, offs, arena0, bufs0):
+    """the operator call of run_running on copies of the case on `dev` -> arena, buffers, nbts, layers"""
+    Cs, K = c["Cs"], c["K"]
     arena = arena0.clone().to(dev)
     bufs = [b.clone().to(dev) for b in bufs0]
     # running_mean at [4, 4 + C), running_var at [C + 12, 2C + 12) of the padded buffer
@@ -521,6 +539,18 @@ def run_running(o, dev, c):
     else:
         for i in layers:
             o.bn_running_apply(rms[i], rvs[i], arena[:K, offs[i]:offs[i] + 2 * Cs[i]], mom, nbts[i])
+    return arena, bufs, nbts, layers
+
+
+def run_running(o, dev, c):
+    """bn_running_apply (per layer, a column slice of the arena) or bn_running_apply_all (entries
+    built as fused_unet.py's bn_defer_apply does): K in-order updates, nbt += K, and nothing else
+    written"""
+    Cs, K, exact, seed = c["Cs"], c["K"], c["exact"], c.get("seed", 16)
+    mom = 0.25 if exact else 0.1
+    m32 = float(torch.tensor(mom, dtype=torch.float32))
+    offs, arena0, bufs0 = running_case(Cs, K, exact, seed)
+    arena, bufs, nbts, layers = running_call(o, dev, c, mom, offs, arena0, bufs0)
     assert torch.equal(arena.cpu(), arena0), "the arena was written"
     fam = "bn_running_apply_all" if c.get("all") else "bn_running_apply"
     for i, C in enumerate(Cs):
@@ -542,3 +572,221 @@ def run_running(o, dev, c):
                 mag = torch.maximum(b0[lo:lo + C].abs(), slots.abs().max(0).values).double()
                 record(fam, b[lo:lo + C], ref, K * 2.0 ** -22 * mag)
     return fam
+
+
+# ------------------------------------------------------------------ the two backends agree
+def assert_same(what, gpu, cpu):
+    """the GPU operator's results and the CPU operator's, bit for bit"""
+    assert len(gpu) == len(cpu)
+    for i, (g, h) in enumerate(zip(gpu, cpu)):
+        assert g.dtype == h.dtype and g.shape == h.shape, (what, i, g.dtype, h.dtype, g.shape, h.shape)
+        ne = g.cpu() != h
+        assert not bool(ne.any()), f"{what}: result {i} differs in {int(ne.sum())} of {ne.numel()} elements"
+
+
+def agree_finalize(o, c):
+    rows, _, _, gamma, beta, rm0, rv0 = finalize_inputs(c)
+
+    def call(dev):
+        rm, rv = rm0.clone().to(dev), rv0.clone().to(dev)
+        nbt = torch.tensor(5, dtype=torch.int64, device=dev)
+        st = o.bn_finalize(rows.to(dev), float(c["count"]), gamma.to(dev), beta.to(dev), rm, rv, 0.1, EPS, True, nbt)
+        return st, rm, rv, nbt
+    assert_same("bn_finalize " + c["id"], call("cuda"), call("cpu"))
+
+
+def agree_group_finalize(o, c):
+    y, G, C, seed, gamma, beta, count, A, B = group_finalize_inputs(c)
+    rows = group_rows(A, B, G, 3, seed)
+
+    def call(dev):
+        ar, ar2 = (torch.full((G + 1, 16 + 2 * C + 24), SENTINEL).to(dev) for _ in range(2))
+        st = o.bn_group_finalize(y.to(dev), G, gamma.to(dev), beta.to(dev), EPS, ar, 16)
+        st2 = o.bn_group_finalize_rows(rows.to(dev), G, float(count), gamma.to(dev), beta.to(dev), EPS, ar2, 16)
+        return st, ar, st2, ar2
+    assert_same("bn_group_finalize " + c["id"], call("cuda"), call("cpu"))
+
+
+def agree_running(o, c):
+    assert not c["exact"]
+    offs, arena0, bufs0 = running_case(c["Cs"], c["K"], False, c.get("seed", 16))
+
+    def call(dev):
+        _, bufs, nbts, _ = running_call(o, dev, c, 0.1, offs, arena0, bufs0)
+        return bufs + nbts
+    assert_same("running statistics " + c["id"], call("cuda"), call("cpu"))
+
+
+def agree_grad_coefs(o, c):
+    y, s4, gamma, _, _, _, _, part, pre, dg0, db0 = grad_coefs_inputs(c)
+
+    def call(dev):
+        return o.bn_grad_coefs(part.to(dev), y.to(dev), s4.to(dev), gamma.to(dev),
+                               dg0.clone().to(dev) if pre else None, db0.clone().to(dev) if pre else None)
+    assert_same("bn_grad_coefs " + c["id"], call("cuda"), call("cpu"))
+
+
+def agree_group_backward_rows(o, c):
+    """dgamma / dbeta of bn_group_backward from precomputed rows: the per-group fp64 sums added in
+    group order on both backends (rows whose sum over the groups depends on the order).  The
+    per-group coefficients are not an output of the operator, so they are not compared here
+    (docs/TESTING.md); dY is held per element by run_backward"""
+    shape, G, R, seed = tuple(c["shape"]), c["groups"], c["rows"], c.get("seed", 11)
+    C = shape[-1]
+    y, dA = tern(shape, 0.5, seed), tern(shape, 0.5, seed + 1)
+    s4, gamma = stats_of(C, seed + 3, G), gamma_of(C)
+    # Within a group the rows are of like magnitude, so their fp64 sum is exact in any order.
+    # Across the groups it is not: group 1 is minus group 0 at 2^70 times group 2's size, so
+    # (g0 + g1) + g2 = g2 in group order and 0 in the orders that add g2 to a large term first.
+    assert G == 3
+    gen = torch.Generator().manual_seed(seed + 5)
+    part = (torch.randn(G, R, 2, C, generator=gen) * 1e3).float()
+    part[0] *= 2.0 ** 70
+    part[1] = -part[0]
+    gs = part.double().sum(1)                                          # [G][2][C], exact
+    assert bool((((gs[0] + gs[1]) + gs[2]).float() != ((gs[0] + gs[2]) + gs[1]).float()).all()), "bad case"
+    part = part.reshape(G * R, 2, C).contiguous()
+    dg0, db0 = torch.arange(C, dtype=torch.float32) % 7 - 3, torch.arange(C, dtype=torch.float32) % 5 - 2
+
+    def call(dev):
+        out = []
+        for pre in (False, True):
+            dgo, dbo = (dg0.clone().to(dev), db0.clone().to(dev)) if pre else (None, None)
+            _, dg, db = o.bn_group_backward(dA.to(dev), None, y.to(dev), s4.to(dev), gamma.to(dev), G, dgo, dbo,
+                                            part.to(dev))
+            out += [dg, db]
+        return out
+    assert_same("bn_group_backward rows " + c["id"], call("cuda"), call("cpu"))
+
+
+# ------------------------------------------------------------------ bindings
+CROSS_DEVICE = "on the host"          # (names with it need a second device: skipped on the CPU)
+
+
+def _binding_args(dev):
+    """valid arguments of every BatchNorm / tail operator at C = 8, two images of 4 x 4 pixels"""
+    C = 8
+    f = lambda *s, dt=torch.float32, d=dev: torch.zeros(*s, dtype=dt, device=d)
+    return dict(
+        C=C, f=f, y=f(2, 4, 4, C, dt=torch.bfloat16), dA=f(2, 4, 4, C, dt=torch.bfloat16),
+        dP=f(2, 2, 2, C, dt=torch.bfloat16), part=f(3, 2, C), gamma=f(C) + 1, beta=f(C), s4=f(4, C) + 1,
+        s4g=f(2, 4, C) + 1, rm=f(C), rv=f(C) + 1, nbt=f(1, dt=torch.int64)[0], arena=f(3, 2 * C + 8),
+        entries=f(0, 4, dt=torch.int64))
+
+
+def binding_accepts(o, dev):
+    """the valid neighbours of binding_calls: every operator runs on the shared arguments"""
+    a = _binding_args(dev)
+    C, f = a["C"], a["f"]
+    st = o.bn_finalize(a["part"], 32.0, a["gamma"], a["beta"], a["rm"], a["rv"], 0.1, EPS, True, a["nbt"])
+    assert tuple(st.shape) == (4, C) and int(a["nbt"]) == 1
+    o.bn_running_apply(a["rm"], a["rv"], a["arena"][:2, 4:4 + 2 * C], 0.1, a["nbt"])
+    assert int(a["nbt"]) == 3
+    o.bn_running_apply_all(a["entries"], a["arena"], 2, C, 0.1)
+    o.bn_relu_apply(a["y"], a["s4"], True, True)
+    o.bn_group_apply(a["y"], a["s4g"], 2, True)
+    o.bn_backward(a["dA"], a["dP"], a["y"], a["s4"], a["gamma"], None, f(C), f(C), None)
+    o.bn_backward(a["dA"], None, a["y"], a["s4"], a["gamma"], None, None, None, a["part"])
+    o.bn_group_backward(a["dA"], None, a["y"], a["s4g"], a["gamma"], 2, None, None, f(6, 2, C))
+    # an empty partial means "no rows given": the operator reduces dA itself, as without one
+    want = o.bn_group_backward(a["dA"] + 1, None, a["y"], a["s4g"], a["gamma"], 2, None, None, None)
+    got = o.bn_group_backward(a["dA"] + 1, None, a["y"], a["s4g"], a["gamma"], 2, None, None, f(0))
+    assert all(torch.equal(g, w) for g, w in zip(got, want)) and bool((want[2] != 0).any())
+    o.bn_grad_coefs(a["part"], a["y"], a["s4"], a["gamma"], f(C), f(C))
+    o.bn_group_finalize(a["y"], 2, a["gamma"], a["beta"], EPS, a["arena"], 8)
+    o.bn_group_finalize_rows(f(6, 2, C), 2, 16.0, a["gamma"], a["beta"], EPS, a["arena"], 8)
+    assert float(o.reduce_rows(f(3 * 5) + 1, 3, 5)[4]) == 3.0
+
+
+def binding_calls(o, dev):
+    """name -> a call both registrations must refuse (csrc/tail_checks.h) before any launch: one
+    call per check the operators gained"""
+    a = _binding_args(dev)
+    C, f = a["C"], a["f"]
+    y, dA, dP, part, gamma, beta, s4, s4g, rm, rv, nbt, arena = (a[k] for k in (
+        "y", "dA", "dP", "part", "gamma", "beta", "s4", "s4g", "rm", "rv", "nbt", "arena"))
+    strided = lambda: f(2 * C)[::2]
+    fin = lambda p=part, g=gamma, b=beta, m=rm, v=rv, n=nbt, upd=True: o.bn_finalize(
+        p, 32.0, g, b, m, v, 0.1, EPS, upd, n)
+    run = lambda m=rm, v=rv, s=None, n=nbt: o.bn_running_apply(
+        m, v, arena[:2, 4:4 + 2 * C] if s is None else s, 0.1, n)
+    bwd = lambda dA=dA, dP=None, s4=s4, g=gamma, dg=None, db=None, p=None, gs=None: o.bn_backward(
+        dA, dP, y, s4, g, gs, dg, db, p)
+    gbwd = lambda s4=s4g, g=gamma, G=2, p=None, dP=None: o.bn_group_backward(dA, dP, y, s4, g, G, None, None, p)
+    coefs = lambda p=part, s4=s4, g=gamma, dg=None, db=None: o.bn_grad_coefs(p, y, s4, g, dg, db)
+    gfin = lambda G=2, g=gamma, b=beta, ar=arena, off=8: o.bn_group_finalize(y, G, g, b, EPS, ar, off)
+    gfr = lambda p=None, G=2, g=gamma, b=beta, ar=arena, off=8: o.bn_group_finalize_rows(
+        f(6, 2, C) if p is None else p, G, 16.0, g, b, EPS, ar, off)
+    return {
+        "bn_finalize partial not a multiple of 2C": lambda: fin(p=f(3 * 2 * C - 1)),
+        "bn_finalize partial fp64": lambda: fin(p=part.double()),
+        "bn_finalize beta shorter": lambda: fin(b=f(C - 1)),
+        "bn_finalize beta fp64": lambda: fin(b=beta.double()),
+        "bn_finalize beta on the host": lambda: fin(b=f(C, d="cpu")),
+        "bn_finalize running_mean shorter": lambda: fin(m=f(C - 1)),
+        "bn_finalize running_mean fp64": lambda: fin(m=rm.double()),
+        "bn_finalize running_mean strided": lambda: fin(m=strided()),
+        "bn_finalize running_mean on the host": lambda: fin(m=f(C, d="cpu")),
+        "bn_finalize running_var longer": lambda: fin(v=f(C + 1)),
+        "bn_finalize running_var strided": lambda: fin(v=strided()),
+        "bn_finalize running_var shorter, no update": lambda: fin(v=f(C - 1), upd=False),
+        "bn_finalize nbt int32": lambda: fin(n=nbt.int()),
+        "bn_finalize nbt on the host": lambda: fin(n=f(1, dt=torch.int64, d="cpu")[0]),
+        "bn_running_apply running_var shorter": lambda: run(v=f(C - 1)),
+        "bn_running_apply running_mean fp64": lambda: run(m=rm.double()),
+        "bn_running_apply running_mean strided": lambda: run(m=strided()),
+        "bn_running_apply slots narrower": lambda: run(s=arena[:2, 4:4 + 2 * C - 1]),
+        "bn_running_apply slots column stride": lambda: run(s=f(2, 4 * C)[:, ::2]),
+        "bn_running_apply slots on the host": lambda: run(s=f(2, 2 * C, d="cpu")),
+        "bn_running_apply nbt int32": lambda: run(n=nbt.int()),
+        "bn_running_apply_all entries int32": lambda: o.bn_running_apply_all(f(0, 4, dt=torch.int32), arena, 2, C, 0.1),
+        "bn_running_apply_all entries [L][3]": lambda: o.bn_running_apply_all(f(1, 3, dt=torch.int64), arena, 2, C, 0.1),
+        "bn_running_apply_all fewer arena rows than K": lambda: o.bn_running_apply_all(a["entries"], arena, 4, C, 0.1),
+        "bn_running_apply_all maxC wider than the arena": lambda: o.bn_running_apply_all(a["entries"], arena, 2, C + 5, 0.1),
+        "bn_running_apply_all arena fp64": lambda: o.bn_running_apply_all(a["entries"], arena.double(), 2, C, 0.1),
+        "bn_relu_apply stats4 shorter": lambda: o.bn_relu_apply(y, f(3, C), True, True),
+        "bn_relu_apply stats4 fp64": lambda: o.bn_relu_apply(y, s4.double(), True, True),
+        "bn_relu_apply stats4 on the host": lambda: o.bn_relu_apply(y, f(4, C, d="cpu"), True, True),
+        "bn_relu_apply neither output": lambda: o.bn_relu_apply(y, s4, False, False),
+        "bn_group_apply stats4 of one group": lambda: o.bn_group_apply(y, s4, 2, True),
+        "bn_group_apply groups not dividing": lambda: o.bn_group_apply(y, f(3, 4, C), 3, True),
+        "bn_backward stats4 shorter": lambda: bwd(s4=f(3, C)),
+        "bn_backward gamma shorter": lambda: bwd(g=f(C - 1)),
+        "bn_backward gamma fp64": lambda: bwd(g=gamma.double()),
+        "bn_backward dA of another size": lambda: bwd(dA=f(2, 4, 3, C, dt=torch.bfloat16)),
+        "bn_backward dP of another size": lambda: bwd(dP=f(2, 2, 3, C, dt=torch.bfloat16)),
+        "bn_backward neither dA nor dP": lambda: bwd(dA=None),
+        "bn_backward dgamma_out alone": lambda: bwd(dg=f(C)),
+        "bn_backward dbeta_out shorter": lambda: bwd(dg=f(C), db=f(C - 1)),
+        "bn_backward dgamma_out strided": lambda: bwd(dg=strided(), db=f(C)),
+        "bn_backward partial not a multiple of 2C": lambda: bwd(p=f(2 * C + 1)),
+        "bn_backward partial with dP": lambda: bwd(dP=dP, p=part),
+        "bn_backward partial with gscale": lambda: bwd(p=part, gs=f(1) + 1),
+        "bn_backward gscale fp64": lambda: bwd(gs=f(1, dt=torch.float64) + 1),
+        "bn_group_backward stats4 of one group": lambda: gbwd(s4=s4),
+        "bn_group_backward groups 0": lambda: gbwd(G=0),
+        "bn_group_backward gamma shorter": lambda: gbwd(g=f(C - 1)),
+        "bn_group_backward partial not a multiple of groups 2C": lambda: gbwd(p=f(3, 2, C)),
+        "bn_grad_coefs partial not a multiple of 2C": lambda: coefs(p=f(3 * 2 * C - 1)),
+        "bn_grad_coefs no rows": lambda: coefs(p=f(0)),
+        "bn_grad_coefs stats4 shorter": lambda: coefs(s4=f(3, C)),
+        "bn_grad_coefs gamma longer": lambda: coefs(g=f(C + 1)),
+        "bn_grad_coefs dbeta_out alone": lambda: coefs(db=f(C)),
+        "bn_grad_coefs stats4 on the host": lambda: coefs(s4=f(4, C, d="cpu")),
+        "bn_group_finalize gamma shorter": lambda: gfin(g=f(C - 1)),
+        "bn_group_finalize beta fp64": lambda: gfin(b=beta.double()),
+        "bn_group_finalize groups not dividing": lambda: gfin(G=3),
+        "bn_group_finalize arena narrower than aoff + 2C": lambda: gfin(off=9),
+        "bn_group_finalize fewer arena rows than groups": lambda: gfin(ar=arena[:1]),
+        "bn_group_finalize aoff negative": lambda: gfin(off=-1),
+        "bn_group_finalize arena on the host": lambda: gfin(ar=f(3, 2 * C + 8, d="cpu")),
+        "bn_group_finalize_rows partial not a multiple of groups 2C": lambda: gfr(p=f(3, 2, C)),
+        "bn_group_finalize_rows beta shorter": lambda: gfr(b=f(C - 1)),
+        "bn_group_finalize_rows groups 0": lambda: gfr(G=0),
+        "bn_group_finalize_rows arena narrower than aoff + 2C": lambda: gfr(off=9),
+        "reduce_rows partial shorter than R x N": lambda: o.reduce_rows(f(14), 3, 5),
+        "reduce_rows partial fp64": lambda: o.reduce_rows(f(15, dt=torch.float64), 3, 5),
+    }
+
+
+BINDING_NAMES = list(binding_calls(None, "cpu"))      # (the calls are built lazily: none runs here)

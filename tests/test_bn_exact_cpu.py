@@ -16,7 +16,8 @@ _src = _src.replace("pytestmark = pytest.mark.gpu", "pytestmark = []", 1).replac
     'DEV = "cuda"', 'DEV = "cpu"', 1)
 exec(compile(_src, _path, "exec"), globals())
 
-# the 34 M-element case is about the GPU apply pass's grid cap (the CPU kernels have no grid)
-_GPU_ONLY = {"test_backward_apply_second_trip"}
+# the 34 M-element case is about the GPU apply pass's grid cap (the CPU kernels have no grid);
+# test_backends_agree compares the two registrations, so it needs both
+_GPU_ONLY = {"test_backward_apply_second_trip", "test_backends_agree"}
 for _name in _GPU_ONLY:
     del globals()[_name]

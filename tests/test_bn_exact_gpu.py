@@ -148,25 +148,50 @@ def test_paths_covered():
 
 
 # bn_group_finalize / bn_group_finalize_rows (they report no path: one kernel pair for every shape)
-@pytest.mark.parametrize("c", [
+GROUP_FINALIZE = [
     dict(id="g3-63px", shape=(3, 9, 7, 8), groups=3, nb=1),            # odd: the 2-in-flight loop's tail
     dict(id="g2-2070px", shape=(4, 23, 45, 8), groups=2, nb=1),
     dict(id="g2-4158px", shape=(4, 33, 63, 8), groups=2, nb=2),        # two partial rows per group
     dict(id="g5-c256", shape=(5, 13, 11, 256), groups=5, nb=2),
     dict(id="g2-c2048", shape=(2, 5, 3, 2048), groups=2, nb=1),
-], ids=lambda c: c["id"])
+]
+
+
+@pytest.mark.parametrize("c", GROUP_FINALIZE, ids=lambda c: c["id"])
 def test_group_finalize(ops, c):
     bc.run_group_finalize(ops, DEV, c)
 
 
-@pytest.mark.parametrize("c", [
+RUNNING = [
     dict(id="apply-exact", Cs=[8, 24, 72], K=5, exact=True),
     dict(id="apply-gauss", Cs=[8, 24, 72], K=7, exact=False),
     dict(id="all-exact", Cs=[8, 24, 72, 16], K=5, exact=True, all=True),
     dict(id="all-gauss", Cs=[8, 24, 72, 16], K=7, exact=False, all=True),
-], ids=lambda c: c["id"])
+]
+
+
+@pytest.mark.parametrize("c", RUNNING, ids=lambda c: c["id"])
 def test_running_apply(ops, c):
     bc.run_running(ops, DEV, c)
+
+
+# ---------------------------------------------------------------------------------------------
+# The kernels and their CPU twins run one text (csrc/bn_math.h): on the inputs of the cases above
+# the two registrations return the same bits.  GPU only (it needs both).
+AGREE = (
+    [("finalize", p.values[2]) for p in FINALIZE]
+    + [("group_finalize", c) for c in GROUP_FINALIZE]
+    + [("running", c) for c in RUNNING if not c["exact"]]
+    + [("coefs", p.values[2]) for p in BACKWARD if p.values[0] == "coefs"]
+    + [("group_rows", dict(id="g3-rows3", shape=(6, 9, 7, 64), groups=3, rows=3))])
+AGREE_RUNNERS = {"finalize": bc.agree_finalize, "group_finalize": bc.agree_group_finalize,
+                 "running": bc.agree_running, "coefs": bc.agree_grad_coefs,
+                 "group_rows": bc.agree_group_backward_rows}
+
+
+@pytest.mark.parametrize("kind,c", AGREE, ids=[f"{k}-{c['id']}" for k, c in AGREE])
+def test_backends_agree(ops, kind, c):
+    AGREE_RUNNERS[kind](ops, c)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -186,6 +211,24 @@ def test_backward_apply_second_trip(ops, pool):
     path = bc.run_backward_big(ops, DEV, BIG, pool)
     print(f"second-trip case pool={pool}: {time.perf_counter() - t0:.1f} s")
     assert path == ("bn_backward:v2:pool" if pool else "bn_backward:v2")
+
+
+# ---------------------------------------------------------------------------------------------
+# The argument checks both registrations share (csrc/tail_checks.h): one refused call per check.
+@pytest.mark.parametrize("name", bc.BINDING_NAMES)
+def test_binding_refuses(ops, name):
+    if DEV == "cpu" and bc.CROSS_DEVICE in name:
+        pytest.skip("a cross-device call needs a second device")
+    call = bc.binding_calls(ops, DEV)[name]
+    with pytest.raises(RuntimeError):
+        call()
+    if DEV == "cuda":
+        torch.cuda.synchronize()
+
+
+def test_binding_accepts(ops):
+    """the valid neighbours of the refused calls run (the refusals are not refusing everything)"""
+    bc.binding_accepts(ops, DEV)
 
 
 def test_report():

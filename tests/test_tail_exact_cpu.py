@@ -15,8 +15,3 @@ assert 'DEV = "cuda"' in _src and "pytestmark = pytest.mark.gpu" in _src
 _src = _src.replace("pytestmark = pytest.mark.gpu", "pytestmark = []", 1).replace(
     'DEV = "cuda"', 'DEV = "cpu"', 1)
 exec(compile(_src, _path, "exec"), globals())
-
-# the refusals are the TORCH_CHECKs of the GPU bindings
-_GPU_ONLY = {"test_binding_refuses"}
-for _name in _GPU_ONLY:
-    del globals()[_name]

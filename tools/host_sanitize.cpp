@@ -12,6 +12,8 @@
 // and the host side of csrc/data_math.h, the input pipeline's recipe (the text the kernels and
 // the CPU twins both run): mirror index, D4 maps, scene choice, and the warp's fixed-point
 // coordinates at the extremes its validity predicate admits (no signed overflow: UBSan)
+// and of csrc/bn_math.h, the BatchNorm / gradient-tail recipe: the slab permutation is a
+// bijection, stats4 at its edge inputs, the three summation orders at the regime borders
 // over the geometry range the U-Net uses (2-D 8^2..1024^2, 3-D 8^3..128^3, batch 1..256), the
 // U-Net's channel pairs in both directions, BN groups 1 / 2 / 4, with and without the
 // prologues and the BN-backward epilogue, at 8, 248 and 256 CUs, asserting the invariants the
@@ -34,6 +36,9 @@
 
 #include <climits>
 
+#include <vector>
+
+#include "../csrc/bn_math.h"
 #include "../csrc/data_math.h"
 #include "../csrc/ops.h"
 
@@ -593,6 +598,66 @@ static const Case kFillCases[] = {
     {"convt_bwd_fused", 2, 0, 32, 32, 64, 0, 64, 0, BN, 0},
 };
 
+// ------------------------------------------------------------------ bn_math.h
+static void check_perm(int mode, int A, int T, int B) {
+  const long long N = (long long)A * T * B;
+  std::vector<char> hit((size_t)N, 0);
+  for (long long j = 0; j < N; ++j) {
+    const long long d = slab_perm(mode, j, T, B);
+    EXPECT(d >= 0 && d < N && !hit[(size_t)d], "slab_perm(%d, %lld, %d, %d) = %lld", mode, j, T, B, d);
+    hit[(size_t)d] = 1;
+    // the element (a, t, b) of the slab is the element (a, b, t) of the parameter
+    EXPECT(d == ((j / ((long long)B * T)) * B + j % B) * T + (j / B) % T, "slab_perm layout");
+  }
+  EXPECT(slab_perm(2, N - 1, T, B) == N - 1, "mode 2 is the identity");
+}
+
+static void sweep_bn_math() {
+  for (auto& ch : kChans)                                   // conv: (Cout, taps, Cin), 2-D and 3-D
+    for (int taps : {9, 27}) check_perm(0, ch[2], taps, ch[0] + ch[1]);
+  for (auto& ch : {std::pair<int, int>{512, 256}, {256, 128}, {128, 64}, {64, 32}, {40, 24}})
+    for (int subs : {4, 8}) check_perm(1, ch.first, subs, ch.second);   // convT: (Cin, subs, Cout)
+  check_perm(0, 3, 1, 5);
+  check_perm(1, 1, 7, 1);
+
+  const float eps = 1e-5f, inv0 = (float)(1.0 / std::sqrt((double)eps));
+  // one pixel: var = 0, the running variance keeps the biased one (no division by count - 1 = 0)
+  BnStats4 s = bn_stats4(3.0, 9.0, 1.0, 2.f, 0.5f, eps);
+  EXPECT(s.mean == 3.f && s.var == 0.0 && s.invstd == inv0 && bn_unbiased_var(s.var, 1.0) == 0.f, "stats4, count = 1");
+  // a raw variance below zero (s2 / count < mean^2) clamps to 0
+  s = bn_stats4(7.0, 4.0, 10.0, 1.f, 0.f, eps);
+  EXPECT(s.var == 0.0 && s.invstd == inv0 && s.scale == inv0 && s.shift == fmaf(-0.7f, inv0, 0.f), "stats4, clamp");
+  // a constant channel y = 3: var = 0 exactly, shift = beta - 3 scale in one rounding
+  s = bn_stats4(3.0 * 441, 9.0 * 441, 441.0, -1.f, 0.25f, eps);
+  EXPECT(s.mean == 3.f && s.var == 0.0 && s.scale == -inv0 && s.shift == fmaf(-3.f, -inv0, 0.25f), "stats4, constant");
+  EXPECT(bn_unbiased_var(2.0, 5.0) == 2.5f, "unbiased variance");
+  EXPECT(bn_momentum_update(7.f, 3.f, 1.f) == 3.f && bn_momentum_update(4.f, 8.f, 0.25f) == 5.f, "momentum update");
+
+  // the three summation orders at the regime borders, on rows whose fp64 sum depends on the order
+  for (long long R : {1LL, (long long)kSlabChunkRows, kSlabChunkRows + 1LL, (long long)kWideMaxRows, kWideMaxRows + 1LL}) {
+    const long long ld = 3;
+    std::vector<float> in((size_t)(R * ld));
+    for (long long r = 0; r < R; ++r)
+      for (long long j = 0; j < ld; ++j) in[(size_t)(r * ld + j)] = (r % 3 == 0 ? 1e30f : r % 3 == 1 ? -1e30f : 1.f) * (float)(j + 1);
+    for (long long j = 0; j < ld; ++j) {
+      double want = 0.0;
+      if (R <= kSlabChunkRows) {
+        for (long long r = 0; r < R; ++r) want += (double)in[(size_t)(r * ld + j)];
+      } else if (R <= kWideMaxRows) {
+        double w[kWideWaves] = {};
+        for (long long r = 0; r < R; ++r) w[r % kWideWaves] += (double)in[(size_t)(r * ld + j)];
+        for (double v : w) want += v;
+      } else {
+        std::vector<double> chunk((size_t)((R + kSlabChunkRows - 1) / kSlabChunkRows), 0.0);
+        for (long long r = 0; r < R; ++r) chunk[(size_t)(r / kSlabChunkRows)] += (double)in[(size_t)(r * ld + j)];
+        for (double v : chunk) want += v;
+      }
+      EXPECT(slab_column_sum(in.data(), R, ld, j) == want, "slab_column_sum R=%lld j=%lld", R, j);
+    }
+    EXPECT((R > kWideMaxRows) == (reduce_rows_scatter_tmp((int)R, 7) > 0), "scratch only above the wide form, R=%lld", R);
+  }
+}
+
 static void print_row(const Case& c, int cus) {
   char shape[160];
   int n = std::snprintf(shape, sizeof(shape), "N=%d", c.N);
@@ -655,6 +720,7 @@ int main(int argc, char** argv) {
   sweep_convt();
   sweep_reductions();
   sweep_data_math();
+  sweep_bn_math();
   std::printf("host_sanitize: %lld planner checks passed (ASan + UBSan)\n", g_checks);
   return 0;
 }
