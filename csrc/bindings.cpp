@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "data_checks.h"
+#include "head_math.h"
 #include "tail_checks.h"
 #include "ops.h"
 #include "optim_math.h"
@@ -940,6 +941,64 @@ static const float* class_weight_ptr(const c10::optional<at::Tensor>& cw, const 
   return cw->data_ptr<float>();
 }
 
+// dice (optional): the float[40] table of head_dice_coefs on a's device — the backward kernels
+// add the soft-Dice dlogits (the DICE instantiations).  The passes of one backward take the same.
+static const float* dice_ptr(const c10::optional<at::Tensor>& dice, const at::Tensor& a) {
+  if (!has(dice)) return nullptr;
+  CHECK_F32(*dice); CHECK_CONTIG(*dice);
+  TORCH_CHECK(dice->numel() == kDiceTable && dice->device() == a.device(),
+              "dice must be head_dice_coefs' float[40] table on the activation's device");
+  return dice->data_ptr<float>();
+}
+
+// Training forward with a soft-Dice term: {loss rows [R][3], Dice rows [R][3][16] = I | S | Y}
+std::vector<at::Tensor> head_dice_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+                                      const at::Tensor& labels, int64_t ignore_index,
+                                      const c10::optional<at::Tensor>& bn4,
+                                      const c10::optional<at::Tensor>& class_weight) {
+  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a); CHECK_F32(Wh); CHECK_CONTIG(Wh); CHECK_F32(bh); CHECK_CONTIG(bh);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous(), "labels must be int64");
+  c10::DeviceGuard guard(a.device());
+  const int C = (int)a.size(-1), K = (int)Wh.size(0);
+  TORCH_CHECK(head_supported(C, K), "head kernel: unsupported (C, K)");
+  TORCH_CHECK(Wh.numel() == (int64_t)K * C && bh.numel() == K && Wh.device() == a.device() &&
+                  bh.device() == a.device() && labels.device() == a.device(),
+              "head_dice_fwd: Wh [K][C], bh [K] and the labels on the activation's device");
+  const long long P = a.numel() / C;
+  TORCH_CHECK(labels.numel() == P, "labels size mismatch");
+  const float* pbn = bn4_ptr(bn4, C);
+  const int nb = head_dice_fwd_blocks(C, P, num_cus());
+  auto fopts = a.options().dtype(at::kFloat);
+  at::Tensor lrows = at::empty({nb, 3}, fopts);
+  at::Tensor drows = at::empty({nb, 3, kDiceK}, fopts);
+  head_dice_fwd_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(), pbn,
+                       lrows.data_ptr<float>(), drows.data_ptr<float>(), nb, P, C, K, (int)ignore_index,
+                       cur_stream(), class_weight_ptr(class_weight, a, K));
+  set_last_path(std::string("head_dice_fwd:") + head_variant(C) + (pbn != nullptr ? ":defer" : ""));
+  return {lrows, drows};
+}
+
+// The finalize of head_dice_fwd's rows: {out3 = [L_CE + dice_weight dice, hits, count], table}
+std::vector<at::Tensor> head_dice_coefs(const at::Tensor& loss_rows, const at::Tensor& dice_rows, int64_t K,
+                                        double dice_weight, double dice_smooth) {
+  CHECK_DEV(loss_rows); CHECK_F32(loss_rows); CHECK_CONTIG(loss_rows); CHECK_F32(dice_rows); CHECK_CONTIG(dice_rows);
+  c10::DeviceGuard guard(loss_rows.device());
+  const int64_t nb = loss_rows.numel() / 3;
+  TORCH_CHECK(nb >= 1 && loss_rows.dim() == 2 && loss_rows.size(1) == 3 && dice_rows.dim() == 3 &&
+                  dice_rows.size(0) == nb && dice_rows.size(1) == 3 && dice_rows.size(2) == kDiceK &&
+                  dice_rows.device() == loss_rows.device(),
+              "head_dice_coefs: loss rows [R][3] and Dice rows [R][3][16] of one head_dice_fwd");
+  TORCH_CHECK(K >= 1 && K <= kDiceK && dice_weight >= 0 && dice_smooth > 0,
+              "head_dice_coefs: 1 <= K <= 16, dice_weight >= 0, dice_smooth > 0");
+  at::Tensor out3 = at::empty({3}, loss_rows.options());
+  at::Tensor table = at::empty({kDiceTable}, loss_rows.options());
+  head_dice_coefs_launch(loss_rows.data_ptr<float>(), dice_rows.data_ptr<float>(), (int)nb, (int)K,
+                         (float)dice_weight, (float)dice_smooth, out3.data_ptr<float>(),
+                         table.data_ptr<float>(), cur_stream());
+  set_last_path("head_dice_coefs");
+  return {out3, table};
+}
+
 at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                        const at::Tensor& labels, int64_t ignore_index,
                        const c10::optional<at::Tensor>& bn4,
@@ -962,19 +1021,20 @@ at::Tensor head_ce_fwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
   return out3;
 }
 
-std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+std::vector<at::Tensor> head_dice_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                                     const at::Tensor& labels, const at::Tensor& out3,
                                     const c10::optional<at::Tensor>& gscale, int64_t ignore_index,
                                     const c10::optional<at::Tensor>& dw_out,
                                     const c10::optional<at::Tensor>& db_out,
                                     const c10::optional<at::Tensor>& bn4, bool store_da,
-                                    const c10::optional<at::Tensor>& class_weight) {
+                                    const c10::optional<at::Tensor>& class_weight,
+                                    const c10::optional<at::Tensor>& dice) {
   CHECK_DEV(a); CHECK_CONTIG(a);
   c10::DeviceGuard guard(a.device());
   const int C = (int)a.size(-1), K = (int)Wh.size(0);
   const float* pbn = bn4_ptr(bn4, C);
   TORCH_CHECK(head_supported(C, K), "head kernel: unsupported (C, K)");
-  TORCH_CHECK(store_da || pbn != nullptr, "head_ce_bwd: store_da=False needs the deferred BN (bn4)");
+  TORCH_CHECK(store_da || pbn != nullptr, "head_ce_bwd / head_dice_bwd: store_da=False needs the deferred BN (bn4)");
   const long long P = a.numel() / C;
   const int nb = head_ce_bwd_blocks(C, K, P, num_cus());
   auto fopts = a.options().dtype(at::kFloat);
@@ -987,9 +1047,9 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
                      fptr_opt(gscale), out3.data_ptr<float>(), store_da ? bptr_mut(dA) : nullptr,
                      part.data_ptr<float>(), nb, P, C, K, (int)ignore_index, pbn,
                      pbn != nullptr ? bnpart.data_ptr<float>() : nullptr, cur_stream(),
-                     class_weight_ptr(class_weight, a, K));
+                     class_weight_ptr(class_weight, a, K), dice_ptr(dice, a));
   set_last_path(std::string("head_ce_bwd:") + head_variant(C) + (pbn != nullptr ? ":defer" : "") +
-                (store_da ? "" : ":stats"));
+                (store_da ? "" : ":stats") + (has(dice) ? ":dice" : ""));
   const bool into = has(dw_out);
   at::Tensor sums = reduce_rows(part, nb, K * C + K);   // rows are [dW (K*C) | db (K)]
   if (into) {
@@ -1012,7 +1072,7 @@ std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, c
 // Second pass of the two-pass head backward: the last decoder block's BatchNorm backward
 // applied to the recomputed head gradient.  partial: the stats pass's [R][2][C] rows;
 // returns {dY, dgamma, dbeta} like bn_backward (accumulated into the outs when given)
-std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+std::vector<at::Tensor> head_dice_bn_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
                                        const at::Tensor& labels, const at::Tensor& out3,
                                        const c10::optional<at::Tensor>& gscale, int64_t ignore_index,
                                        const at::Tensor& bn4, const at::Tensor& partial,
@@ -1020,22 +1080,25 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
                                        const c10::optional<at::Tensor>& dgamma_out,
                                        const c10::optional<at::Tensor>& dbeta_out,
                                        const c10::optional<at::Tensor>& pscale, int64_t groups,
-                                       const c10::optional<at::Tensor>& class_weight) {
+                                       const c10::optional<at::Tensor>& class_weight,
+                                       const c10::optional<at::Tensor>& dice) {
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
   // pscale: device factor on the partial rows (rows from the fused forward at unit scale)
   const float* ps = fptr_opt(pscale);
   c10::DeviceGuard guard(a.device());
   const int C = (int)a.size(-1), K = (int)Wh.size(0);
   const float* pcw = class_weight_ptr(class_weight, a, K);
+  const float* pdice = dice_ptr(dice, a);
+  TORCH_CHECK(pdice == nullptr || groups <= 1, "head_dice_bn_bwd: the Dice term is not combined with BN groups");
   if (groups > 1) {
     // BN groups (a batched window): bn4 [groups][4][C], partial rows group-major (the fused
     // forward's head_ce_fwd_stats with groups), per-group coefficients
     const long long P = a.numel() / C;
     TORCH_CHECK(C == 32 && K <= 16 && P % (groups * 16) == 0,
-                "head_ce_bn_bwd groups: C = 32 head, pixels per group a multiple of 16");
+                "head_ce_bn_bwd / head_dice_bn_bwd groups: C = 32 head, pixels per group a multiple of 16");
     CHECK_F32(bn4); CHECK_CONTIG(bn4); CHECK_F32(partial); CHECK_CONTIG(partial); CHECK_F32(gamma);
     TORCH_CHECK(bn4.numel() == groups * 4 * C && partial.numel() % (groups * 2 * C) == 0,
-                "head_ce_bn_bwd groups: bn4 [groups][4][C], partial [groups * R][2][C]");
+                "head_ce_bn_bwd / head_dice_bn_bwd groups: bn4 [groups][4][C], partial [groups * R][2][C]");
     auto fopts = a.options().dtype(at::kFloat);
     const bool into = has(dgamma_out);
     at::Tensor dgamma = into ? *dgamma_out : at::empty({C}, fopts);
@@ -1065,9 +1128,33 @@ std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh
   at::Tensor dY = at::empty_like(a);
   head_bn_apply_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(),
                        fptr_opt(gscale), out3.data_ptr<float>(), pbn, r.coefs.data_ptr<float>(),
-                       bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream(), 1, pcw);
-  set_last_path(std::string("head_ce_bn_bwd:") + head_variant(C));
+                       bptr_mut(dY), P, C, K, (int)ignore_index, num_cus(), cur_stream(), 1, pcw, pdice);
+  set_last_path(std::string("head_ce_bn_bwd:") + head_variant(C) + (pdice != nullptr ? ":dice" : ""));
   return {dY, r.dgamma, r.dbeta};
+}
+
+// head_ce_bwd / head_ce_bn_bwd: the operators without the soft-Dice table
+std::vector<at::Tensor> head_ce_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+                                    const at::Tensor& labels, const at::Tensor& out3,
+                                    const c10::optional<at::Tensor>& gscale, int64_t ignore_index,
+                                    const c10::optional<at::Tensor>& dw_out,
+                                    const c10::optional<at::Tensor>& db_out,
+                                    const c10::optional<at::Tensor>& bn4, bool store_da,
+                                    const c10::optional<at::Tensor>& class_weight) {
+  return head_dice_bwd(a, Wh, bh, labels, out3, gscale, ignore_index, dw_out, db_out, bn4, store_da,
+                       class_weight, c10::nullopt);
+}
+std::vector<at::Tensor> head_ce_bn_bwd(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh,
+                                       const at::Tensor& labels, const at::Tensor& out3,
+                                       const c10::optional<at::Tensor>& gscale, int64_t ignore_index,
+                                       const at::Tensor& bn4, const at::Tensor& partial,
+                                       const at::Tensor& gamma,
+                                       const c10::optional<at::Tensor>& dgamma_out,
+                                       const c10::optional<at::Tensor>& dbeta_out,
+                                       const c10::optional<at::Tensor>& pscale, int64_t groups,
+                                       const c10::optional<at::Tensor>& class_weight) {
+  return head_dice_bn_bwd(a, Wh, bh, labels, out3, gscale, ignore_index, bn4, partial, gamma, dgamma_out,
+                          dbeta_out, pscale, groups, class_weight, c10::nullopt);
 }
 
 // Training forward of the head with the deferred BatchNorm, fused with the backward's
@@ -1691,10 +1778,22 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("head_ce_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
         "int ignore_index, Tensor(a!)? dw_out=None, Tensor(b!)? db_out=None, Tensor? bn4=None, "
         "bool store_da=True, Tensor? class_weight=None) -> Tensor[]");
+  // head_ce_bwd / head_ce_bn_bwd with the soft-Dice table (dice=None: exactly those operators)
+  m.def("head_dice_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
+        "int ignore_index, Tensor(a!)? dw_out=None, Tensor(b!)? db_out=None, Tensor? bn4=None, "
+        "bool store_da=True, Tensor? class_weight=None, Tensor? dice=None) -> Tensor[]");
+  m.def("head_dice_bn_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
+        "int ignore_index, Tensor bn4, Tensor partial, Tensor gamma, Tensor(a!)? dgamma_out=None, "
+        "Tensor(b!)? dbeta_out=None, Tensor? pscale=None, int groups=0, "
+        "Tensor? class_weight=None, Tensor? dice=None) -> Tensor[]");
   m.def("head_ce_bn_bwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, Tensor out3, Tensor? gscale, "
         "int ignore_index, Tensor bn4, Tensor partial, Tensor gamma, Tensor(a!)? dgamma_out=None, "
         "Tensor(b!)? dbeta_out=None, Tensor? pscale=None, int groups=0, "
         "Tensor? class_weight=None) -> Tensor[]");
+  m.def("head_dice_fwd(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, Tensor? bn4=None, "
+        "Tensor? class_weight=None) -> Tensor[]");
+  m.def("head_dice_coefs(Tensor loss_rows, Tensor dice_rows, int K, float dice_weight, float dice_smooth) "
+        "-> Tensor[]");
   m.def("head_ce_fwd_stats(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, "
         "Tensor bn4, int groups=0, Tensor? class_weight=None) -> Tensor[]");
   m.def("head_wgrad_from_rows(Tensor rows, Tensor scale, int K, int C, Tensor(a!)? dw_out=None, "
@@ -1758,7 +1857,11 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("head_ce_fwd", &ddlpc::head_ce_fwd);
   m.impl("head_ce_bwd", &ddlpc::head_ce_bwd);
   m.impl("head_ce_bn_bwd", &ddlpc::head_ce_bn_bwd);
+  m.impl("head_dice_bwd", &ddlpc::head_dice_bwd);
+  m.impl("head_dice_bn_bwd", &ddlpc::head_dice_bn_bwd);
   m.impl("head_ce_fwd_stats", &ddlpc::head_ce_fwd_stats);
+  m.impl("head_dice_fwd", &ddlpc::head_dice_fwd);
+  m.impl("head_dice_coefs", &ddlpc::head_dice_coefs);
   m.impl("head_wgrad_from_rows", &ddlpc::head_wgrad_from_rows);
   m.impl("head_grad_scale", &ddlpc::head_grad_scale);
   m.impl("meter_add", &ddlpc::meter_add);

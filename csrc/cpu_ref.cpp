@@ -26,6 +26,7 @@
 #include "bn_math.h"
 #include "data_checks.h"
 #include "data_math.h"
+#include "head_math.h"
 #include "optim_math.h"
 #include "tail_checks.h"
 
@@ -625,6 +626,7 @@ Tensor head_act(const Tensor& a, const optional<Tensor>& bn4, int64_t G) {
 // valid-pixel count (out3[2]); hits stay unweighted.  Without weights nothing is multiplied.
 struct HeadFwd {
   Tensor A, logits, valid, lab, out3, pw;
+  double ce_sum = 0;      // the sum of the (weighted) loss terms: out3[0] before the division
 };
 HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                      int64_t ignore_index, const optional<Tensor>& bn4, int64_t G,
@@ -653,17 +655,28 @@ HeadFwd head_forward(const Tensor& a, const Tensor& Wh, const Tensor& bh, const 
     count = h.pw.to(at::kDouble).sum().item<double>();
   }
   const double correct = (h.logits.argmax(1) == lab).sum().item<double>();
-  const double loss = count > 0 ? ce.sum().item<double>() / count : 0.0;
+  h.ce_sum = ce.sum().item<double>();
+  const double loss = count > 0 ? h.ce_sum / count : 0.0;
   h.out3 = at::tensor({(float)loss, (float)correct, (float)count}, a.options().dtype(at::kFloat));
   return h;
 }
-// dlogits = (softmax - onehot) * scale on valid pixels
-Tensor head_dlogits(const HeadFwd& h, double scale) {
-  Tensor p = at::softmax(h.logits, 1);
-  p = p - at::one_hot(h.lab, h.logits.size(1)).to(at::kFloat);
-  if (h.pw.defined())     // (softmax - onehot) * (scale * w): the GPU kernels' operand order
-    return at::where(h.valid.unsqueeze(1), p * (h.pw * scale).unsqueeze(1), at::zeros_like(p));
-  return at::where(h.valid.unsqueeze(1), p * scale, at::zeros_like(p));
+// dlogits = (softmax - onehot) * scale on valid pixels; with the Dice table (head_math.h) plus
+// p_j (g_j - sum_c p_c g_c) * gd, g_c = B_c + A_c [y = c], gd = the upstream dL
+Tensor head_dlogits(const HeadFwd& h, double scale, const optional<Tensor>& dice = c10::nullopt, double gd = 0) {
+  const Tensor sm = at::softmax(h.logits, 1);
+  const int64_t K = h.logits.size(1);
+  const Tensor onehot = at::one_hot(h.lab, K).to(at::kFloat);
+  const Tensor p = sm - onehot;
+  // (softmax - onehot) * (scale * w): the GPU kernels' operand order
+  Tensor d = h.pw.defined() ? p * (h.pw * scale).unsqueeze(1) : p * scale;
+  if (has(dice)) {
+    TORCH_CHECK(dice->scalar_type() == at::kFloat && dice->numel() == kDiceTable,
+                "dice must be head_dice_coefs' float[40] table on the activation's device");
+    const Tensor A = dice->narrow(0, 0, K), B = dice->narrow(0, kDiceK, K);
+    const Tensor g = B.unsqueeze(0) + onehot * A.unsqueeze(0);
+    d = d + sm * (g - (sm * g).sum(1, true)) * gd;
+  }
+  return at::where(h.valid.unsqueeze(1), d, at::zeros_like(d));
 }
 double head_scale(const Tensor& out3, const optional<Tensor>& gs) {
   const double cnt = out3[2].item<double>();
@@ -671,20 +684,52 @@ double head_scale(const Tensor& out3, const optional<Tensor>& gs) {
 }
 void add_into(const optional<Tensor>& dst, const Tensor& v) { add_to(*dst, v); }
 
+// the twins of head_dice_fwd (one row of each kind: fp64 sums rounded once) and head_dice_coefs
+std::vector<Tensor> head_dice_fwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
+                                  int64_t ignore_index, const optional<Tensor>& bn4,
+                                  const optional<Tensor>& class_weight) {
+  const int64_t K = Wh.size(0);
+  TORCH_CHECK(K <= kDiceK, "head kernel: unsupported (C, K)");
+  const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, 1, class_weight);
+  // (the row carries the sum of the loss terms, as the GPU rows do)
+  const Tensor lrows = at::tensor({(float)h.ce_sum, h.out3[1].item<float>(), h.out3[2].item<float>()},
+                                  h.out3.options()).reshape({1, 3});
+  const Tensor p = at::where(h.valid.unsqueeze(1), at::softmax(h.logits, 1), at::zeros_like(h.logits)).to(at::kDouble);
+  const Tensor hit = (at::one_hot(h.lab, K) * h.valid.unsqueeze(1)).to(at::kDouble);
+  Tensor drows = at::zeros({1, 3, kDiceK}, at::kDouble);
+  drows[0][0].narrow(0, 0, K).copy_((p * hit).sum(0));
+  drows[0][1].narrow(0, 0, K).copy_(p.sum(0));
+  drows[0][2].narrow(0, 0, K).copy_(hit.sum(0));
+  return {lrows, drows.to(at::kFloat)};
+}
+
+std::vector<Tensor> head_dice_coefs(const Tensor& loss_rows, const Tensor& dice_rows, int64_t K,
+                                    double dice_weight, double dice_smooth) {
+  ddlpc::set_last_path("cpu");
+  TORCH_CHECK(K >= 1 && K <= kDiceK && dice_weight >= 0 && dice_smooth > 0,
+              "head_dice_coefs: 1 <= K <= 16, dice_weight >= 0, dice_smooth > 0");
+  const Tensor ce3 = loss_rows.reshape({-1, 3}).to(at::kDouble).sum(0).contiguous();
+  const Tensor isy = dice_rows.reshape({-1, kDiceRow}).to(at::kDouble).sum(0).contiguous();
+  Tensor out3 = at::empty({3}, loss_rows.options()), table = at::empty({kDiceTable}, loss_rows.options());
+  dice_finalize(ce3.data_ptr<double>(), isy.data_ptr<double>(), (int)K, (float)dice_weight, (float)dice_smooth,
+                out3.data_ptr<float>(), table.data_ptr<float>());
+  return {out3, table};
+}
+
 Tensor head_ce_fwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                    int64_t ignore_index, const optional<Tensor>& bn4, const optional<Tensor>& class_weight) {
   return head_forward(a, Wh, bh, labels, ignore_index, bn4, 1, class_weight).out3;
 }
 
-std::vector<Tensor> head_ce_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
+std::vector<Tensor> head_dice_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                                 const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
                                 const optional<Tensor>& dw_out, const optional<Tensor>& db_out,
                                 const optional<Tensor>& bn4, bool store_da,
-                                const optional<Tensor>& class_weight) {
-  TORCH_CHECK(store_da || has(bn4), "head_ce_bwd: store_da=False needs the deferred BN (bn4)");
+                                const optional<Tensor>& class_weight, const optional<Tensor>& dice) {
+  TORCH_CHECK(store_da || has(bn4), "head_ce_bwd / head_dice_bwd: store_da=False needs the deferred BN (bn4)");
   const int64_t K = Wh.size(0), C = a.size(-1);
   const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, 1, class_weight);
-  const Tensor dl = head_dlogits(h, head_scale(out3, gscale));
+  const Tensor dl = head_dlogits(h, head_scale(out3, gscale), dice, scalar_or(gscale, 1.0));
   const Tensor dAf = at::matmul(dl, f32(Wh).reshape({K, C}));
   const Tensor dA = store_da ? bf(dAf.reshape(a.sizes())) : at::empty({0}, a.options());
   const Tensor dW = at::matmul(dl.t(), h.A), db = dl.sum(0);
@@ -697,16 +742,17 @@ std::vector<Tensor> head_ce_bwd(const Tensor& a, const Tensor& Wh, const Tensor&
   return {dA, dW, db, bnpart};
 }
 
-std::vector<Tensor> head_ce_bn_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
+std::vector<Tensor> head_dice_bn_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
                                    const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
                                    const Tensor& bn4, const Tensor& partial, const Tensor& gamma,
                                    const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
                                    const optional<Tensor>& pscale, int64_t groups,
-                                   const optional<Tensor>& class_weight) {
+                                   const optional<Tensor>& class_weight, const optional<Tensor>& dice) {
   const int64_t G = groups > 1 ? groups : 1;
+  TORCH_CHECK(!has(dice) || G == 1, "head_dice_bn_bwd: the Dice term is not combined with BN groups");
   const int64_t K = Wh.size(0), C = a.size(-1);
   const HeadFwd h = head_forward(a, Wh, bh, labels, ignore_index, bn4, G, class_weight);
-  const Tensor dl = head_dlogits(h, head_scale(out3, gscale));
+  const Tensor dl = head_dlogits(h, head_scale(out3, gscale), dice, scalar_or(gscale, 1.0));
   const Tensor dAf = rbf(at::matmul(dl, f32(Wh).reshape({K, C}))).reshape(a.sizes());
   const BnBwd t = bn_terms(dAf, f32(a), bn4, G, 1.0);
   const Tensor sums = partial.reshape({G, -1, 2, C}).to(at::kDouble).sum(1) * scalar_or(pscale, 1.0);
@@ -714,6 +760,24 @@ std::vector<Tensor> head_ce_bn_bwd(const Tensor& a, const Tensor& Wh, const Tens
   Tensor dgamma = into ? *dgamma_out : Tensor(), dbeta = into ? *dbeta_out : Tensor();
   const Tensor coefs = bn_coefs(sums, bn4, gamma, G, (double)(a.numel() / C / G), dgamma, dbeta, into);
   return {bn_apply_coefs(t, coefs, a, G), dgamma, dbeta};
+}
+
+std::vector<Tensor> head_ce_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
+                                const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
+                                const optional<Tensor>& dw_out, const optional<Tensor>& db_out,
+                                const optional<Tensor>& bn4, bool store_da,
+                                const optional<Tensor>& class_weight) {
+  return head_dice_bwd(a, Wh, bh, labels, out3, gscale, ignore_index, dw_out, db_out, bn4, store_da, class_weight,
+                       c10::nullopt);
+}
+std::vector<Tensor> head_ce_bn_bwd(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
+                                   const Tensor& out3, const optional<Tensor>& gscale, int64_t ignore_index,
+                                   const Tensor& bn4, const Tensor& partial, const Tensor& gamma,
+                                   const optional<Tensor>& dgamma_out, const optional<Tensor>& dbeta_out,
+                                   const optional<Tensor>& pscale, int64_t groups,
+                                   const optional<Tensor>& class_weight) {
+  return head_dice_bn_bwd(a, Wh, bh, labels, out3, gscale, ignore_index, bn4, partial, gamma, dgamma_out,
+                          dbeta_out, pscale, groups, class_weight, c10::nullopt);
 }
 
 std::vector<Tensor> head_ce_fwd_stats(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels,
@@ -1319,7 +1383,11 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("head_ce_fwd", &head_ce_fwd);
   m.impl("head_ce_bwd", &head_ce_bwd);
   m.impl("head_ce_bn_bwd", &head_ce_bn_bwd);
+  m.impl("head_dice_bwd", &head_dice_bwd);
+  m.impl("head_dice_bn_bwd", &head_dice_bn_bwd);
   m.impl("head_ce_fwd_stats", &head_ce_fwd_stats);
+  m.impl("head_dice_fwd", &head_dice_fwd);
+  m.impl("head_dice_coefs", &head_dice_coefs);
   m.impl("head_wgrad_from_rows", &head_wgrad_from_rows);
   m.impl("meter_add", &meter_add);
   m.impl("head_grad_scale", &head_grad_scale);

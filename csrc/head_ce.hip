@@ -22,8 +22,17 @@
 // after it was found inside it (class_w).  Without weights every factor is exactly 1: the
 // channel-split kernels then multiply by a table of ones, the C = 32 kernels are instantiated
 // without the factor (WT = false) — the same bits either way.
+//
+// Soft-Dice term (L = L_CE + lambda dice, head_math.h; optional): its gradient at a pixel needs
+// per-class sums over the whole call, so the forward is a kernel of its own (head_dice_fwd:
+// loss / hits / count rows plus [3][16] rows of I, S, Y per workgroup, no gradient work),
+// head_dice_coefs reduces the rows in fp64 into out3 and the A | B table, and every backward
+// kernel has a DICE instantiation that reads the table from LDS and adds
+// p_j (g_j - sum_c p_c g_c) dL to the CE dlogits before dA, dWh, dbh and the BN partials are
+// formed.  Without a table the kernels launched are exactly the ones without the term.
 #include "common.h"
 #include "data_math.h"
+#include "head_math.h"
 #include "ops.h"
 
 namespace ddlpc {
@@ -31,6 +40,12 @@ namespace ddlpc {
 namespace {
 
 constexpr int MAXC = 64, MAXK = 16;
+static_assert(MAXK == kDiceK, "the Dice table has one slot per class slot of the head");
+
+// stage the Dice table's A[16] | B[16] into LDS
+DDLPC_DEVICE void load_dice(const float* tab, float* sD) {
+  if (threadIdx.x < 2 * MAXK) sD[threadIdx.x] = tab[threadIdx.x];
+}
 
 // Classes: the kernels are instantiated for KP in {2, 4, 8, 16} (and 6, the
 // Vaihingen class count, unpadded) logit slots and take
@@ -212,14 +227,15 @@ DDLPC_DEVICE float dpp_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
-// head_pixel with the extras of the fused forward + statistics pass: dA before rounding
-// (o8), the log-sum-exp, the label's logit and the arg-max class
+// The softmax half of a channel-split pixel: the activation f, e[k] = exp(z_k - max) and their
+// sum se (identical on the G lanes of the pixel), the maximum m, the label's logit and the
+// arg-max class.  w2: the lane's 8 channels of every class row, as packed pairs
+typedef float f2_t __attribute__((ext_vector_type(2)));
 template <int C, int K, bool DEFER>
-DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* __restrict__ w,
-                               const float (&bk)[K], const float (&sc)[8], const float (&sh)[8],
-                               float gs, int ignore_index, float (&y8)[8], float (&f)[8],
-                               float (&d)[K], uint4& pk, float (&o8)[8], float& lse, float& zy,
-                               int& am) {
+DDLPC_DEVICE void split_softmax(const uint4 av, const int64_t lab, const f2_t* __restrict__ w2,
+                                const float (&bk)[K], const float (&sc)[8], const float (&sh)[8],
+                                float (&y8)[8], float (&f)[8], float (&z)[K], float& se, float& m,
+                                float& zy, int& am) {
   constexpr int G = C / 8;
   unpack8(av, y8);
 #pragma unroll
@@ -227,12 +243,9 @@ DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* _
   if (DEFER) unpack8(pack8(f), f);                // the activation rounded as materialised
   // packed f32 math (v_pk_fma_f32: two channels per instruction) — this kernel pair is
   // VALU-issue bound; the per-channel operation order of dA and dWh is unchanged
-  typedef float f2_t __attribute__((ext_vector_type(2)));
-  const f2_t* w2 = reinterpret_cast<const f2_t*>(w);
   f2_t f2[4];
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) f2[jj] = f2_t{f[2 * jj], f[2 * jj + 1]};
-  float z[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     f2_t t2 = f2_t{0.f, 0.f};
@@ -248,7 +261,7 @@ DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* _
     if (G >= 4) z[k] += dpp_f<0x4E>(z[k]);
     if (G >= 8) z[k] += dpp_f<0x141>(z[k]);
   }
-  float m = -INFINITY;
+  m = -INFINITY;
   am = 0;
   zy = 0.f;
 #pragma unroll
@@ -257,13 +270,40 @@ DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* _
     if (z[k] > m) { m = z[k]; am = k; }              // first maximum (padded classes: -inf)
     zy = k == lab ? z[k] : zy;
   }
-  float se = 0.f;
+  se = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) { z[k] = __expf(z[k] - m); se += z[k]; }
+}
+
+// head_pixel with the extras of the fused forward + statistics pass: dA before rounding
+// (o8), the log-sum-exp, the label's logit and the arg-max class.  DICE: dt = the table's
+// A[16] | B[16] in LDS, gd = the upstream dL — the Dice dlogits join the CE ones in d
+template <int C, int K, bool DEFER, bool DICE = false>
+DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* __restrict__ w,
+                               const float (&bk)[K], const float (&sc)[8], const float (&sh)[8],
+                               float gs, int ignore_index, float (&y8)[8], float (&f)[8],
+                               float (&d)[K], uint4& pk, float (&o8)[8], float& lse, float& zy,
+                               int& am, const float* __restrict__ dt = nullptr, float gd = 0.f) {
+  const f2_t* w2 = reinterpret_cast<const f2_t*>(w);
+  float z[K], se, m;
+  split_softmax<C, K, DEFER>(av, lab, w2, bk, sc, sh, y8, f, z, se, m, zy, am);
   lse = m + __logf(se);
   const float inv = __builtin_amdgcn_rcpf(se);      // (se >= 1: the max term is exp(0))
+  if (DICE) {
+    float p[K], g[K], dot = 0.f;
 #pragma unroll
-  for (int k = 0; k < K; ++k) d[k] = lab != ignore_index ? (z[k] * inv - (k == lab ? 1.f : 0.f)) * gs : 0.f;
+    for (int k = 0; k < K; ++k) {
+      p[k] = z[k] * inv;
+      g[k] = dice_g(dt[k], dt[MAXK + k], k == lab);
+      dot = fmaf(p[k], g[k], dot);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      d[k] = lab != ignore_index ? fmaf(dice_dz(p[k], g[k], dot), gd, (p[k] - (k == lab ? 1.f : 0.f)) * gs) : 0.f;
+  } else {
+#pragma unroll
+    for (int k = 0; k < K; ++k) d[k] = lab != ignore_index ? (z[k] * inv - (k == lab ? 1.f : 0.f)) * gs : 0.f;
+  }
   f2_t o2[4];
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) o2[jj] = f2_t{0.f, 0.f};
@@ -277,14 +317,16 @@ DDLPC_DEVICE void head_pixel_x(const uint4 av, const int64_t lab, const float* _
   pk = pack8(o8);
 }
 
-template <int C, int K, bool DEFER>
+template <int C, int K, bool DEFER, bool DICE = false>
 DDLPC_DEVICE void head_pixel(const uint4 av, const int64_t lab, const float* __restrict__ w,
                              const float (&bk)[K], const float (&sc)[8], const float (&sh)[8],
                              float gs, int ignore_index, float (&y8)[8], float (&f)[8],
-                             float (&d)[K], uint4& pk) {
+                             float (&d)[K], uint4& pk, const float* __restrict__ dt = nullptr,
+                             float gd = 0.f) {
   float o8[8], lse, zy;
   int am;
-  head_pixel_x<C, K, DEFER>(av, lab, w, bk, sc, sh, gs, ignore_index, y8, f, d, pk, o8, lse, zy, am);
+  head_pixel_x<C, K, DEFER, DICE>(av, lab, w, bk, sc, sh, gs, ignore_index, y8, f, d, pk, o8, lse, zy, am,
+                                  dt, gd);
 }
 
 // STORE = false (deferred BN only): the stats pass of the two-pass head backward — dWh,
@@ -295,15 +337,22 @@ DDLPC_DEVICE void head_pixel(const uint4 av, const int64_t lab, const float* __r
 // UNIT gradient scale: dWh, dbh and the BN partials (from the unrounded dA) are linear in
 // the scale dL/count, which the backward applies on the device (head_wgrad_from_rows,
 // head_ce_bn_bwd's pscale) — one pass over the activation and labels instead of two.
-template <int C, int K, bool DEFER, bool STORE = true, bool LOSS = false>
+//
+// DICE: the Dice dlogits are added in head_pixel_x (dice = the table)
+template <int C, int K, bool DEFER, bool STORE = true, bool LOSS = false, bool DICE = false>
 __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, bf16_t* __restrict__ dA, float* __restrict__ dWp,
     long long P, int ignore_index, const float* __restrict__ bn4, float* __restrict__ bnpart,
-    int Kreal, float* __restrict__ lossp, const float* __restrict__ cw) {
+    int Kreal, float* __restrict__ lossp, const float* __restrict__ cw,
+    const float* __restrict__ dice) {
   static_assert(STORE || DEFER, "the stats-only pass exists for the deferred BatchNorm");
   static_assert(!LOSS || (DEFER && !STORE), "the fused forward is the deferred stats pass");
+  static_assert(!(LOSS && DICE), "the Dice forward is head_dice_fwd");
+  __shared__ float sDice[2 * MAXK];
+  if (DICE) load_dice(dice, sDice);
+  const float gd = DICE ? (gscale != nullptr ? gscale[0] : 1.0f) : 0.f;
   constexpr int G = C / 8;                          // lanes per pixel
   constexpr int PPB = 256 / G;                      // pixels per workgroup step
   constexpr int NACC = 8 * K + K + (DEFER ? 16 : 0) + (LOSS ? 3 : 0);
@@ -335,7 +384,6 @@ __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
   float acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
-  typedef float f2_t __attribute__((ext_vector_type(2)));
   f2_t accw[K][4];                                  // dWh[k][c8 + 2jj, +1] (packed pairs)
 #pragma unroll
   for (int k = 0; k < K; ++k)
@@ -362,8 +410,8 @@ __global__ __launch_bounds__(256) void head_ce_bwd_kernel(
     int am;
     uint4 pk;
     const float wy = class_w<K>(scw, lab, wout);     // (x 1 without weights: the same bits)
-    head_pixel_x<C, K, DEFER>(a_cur, lab, sW + opaque_zero() + c8, bk, sc, sh, gs * wy, ignore_index,
-                              y8, f, d, pk, o8, lse, zy, am);
+    head_pixel_x<C, K, DEFER, DICE>(a_cur, lab, sW + opaque_zero() + c8, bk, sc, sh, gs * wy, ignore_index,
+                                    y8, f, d, pk, o8, lse, zy, am, DICE ? sDice + opaque_zero() : nullptr, gd);
     if (STORE) *reinterpret_cast<uint4*>(dA + px * C + c8) = pk;
     if (LOSS && cg == 0) {
       if (lab != ignore_index) { acc[LA] += (lse - zy) * wy; acc[LA + 2] += wy; }
@@ -452,18 +500,21 @@ DDLPC_DEVICE f32x4_t mfma16x16x16(const uint2& a, const uint2& b, f32x4_t c) {
 // bn_bwd2_kernel's apply, same operand order) — dA never reaches HBM and the separate
 // BN-apply pass (read dA + y, write dY) is gone: y + labels in, dY out.
 // Two pixels per lane per iteration with all loads first (memory-level parallelism).
-template <int C, int K>
+template <int C, int K, bool DICE = false>
 __global__ __launch_bounds__(256) void head_bn_apply_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, const float* __restrict__ bn4,
     const float* __restrict__ coefs, bf16_t* __restrict__ dY, long long P, int ignore_index,
-    int Kreal, const float* __restrict__ cw) {
+    int Kreal, const float* __restrict__ cw, const float* __restrict__ dice) {
   constexpr int G = C / 8;
   constexpr int PPB = 256 / G;
   constexpr int U = 4;                               // pixels per lane in flight
   __shared__ __attribute__((aligned(16))) float sW[K * C];
   __shared__ float scw[K];                           // class weights (ones without)
+  __shared__ float sDice[2 * MAXK];
+  if (DICE) load_dice(dice, sDice);
+  const float gd = DICE ? (gscale != nullptr ? gscale[0] : 1.0f) : 0.f;
   const int tid = threadIdx.x, lane = tid & 63;
   const int cg = lane % G, c8 = cg * 8;
   for (int i = tid; i < K * C; i += 256) sW[i] = i < Kreal * C ? Wh[i] : 0.f;
@@ -500,8 +551,9 @@ __global__ __launch_bounds__(256) void head_bn_apply_kernel(
       float y8[8], f[8], d[K];
       uint4 pk;
       // (the same gs * w as the stats pass: dA is recomputed bit for bit)
-      head_pixel<C, K, true>(av[r], lab[r], sW + opaque_zero() + c8, bk, sc, sh,
-                             gs * class_w<K>(scw, lab[r], wout), ignore_index, y8, f, d, pk);
+      head_pixel<C, K, true, DICE>(av[r], lab[r], sW + opaque_zero() + c8, bk, sc, sh,
+                                   gs * class_w<K>(scw, lab[r], wout), ignore_index, y8, f, d, pk,
+                                   DICE ? sDice + opaque_zero() : nullptr, gd);
       float rr[8], o[8];
       unpack8(pk, rr);
 #pragma unroll
@@ -604,20 +656,12 @@ DDLPC_DEVICE Head32W head32_weights(const float* __restrict__ Wh, const float* _
   return w;
 }
 
-// one 16-pixel step of a wave: from the lane's 8 raw channels yv (pixel n, channels 8g..),
-// its label and validity -> the activation f (BN + ReLU when DEFER, bf16-rounded), the 4
-// dlogits d (classes 4g..4g+3, scaled by gs; zero for ignored / tail pixels), dA before
-// rounding (o8, the lane's 8 channels) and rounded (pk); LOSS extras: lse, the label's
-// logit, the arg-max class (valid on every lane of the pixel).  gs carries the pixel's class
-// weight when there are weights.  WT only keeps the weighted kernels' instantiation apart: this
-// function is internal, and the unweighted fused forward passes the constant gs = 1, which the
-// compiler propagates into an instantiation whose every caller does (measured: with a shared
-// instantiation that kernel came out 22 instructions longer and 2.7 % slower)
-template <bool DEFER, bool LOSS, bool WT>
-DDLPC_DEVICE void head32_step(const uint4 yv, const int lab, const bool valid, const Head32W* __restrict__ wl,
-                              const float (&sc)[8], const float (&sh)[8], float gs, int ignore_index,
-                              int g, float (&y8)[8], uint4& fb, float (&d)[4], uint2& bh2, uint2& bl2,
-                              float (&o8)[8], uint4& pk, float& lse, float& zy, int& am) {
+// The softmax half of a 16-pixel step (head32_step; the whole step of the Dice forward): the
+// logits z, their maximum m over the pixel, e = exp(z - m) and se = their sum over the pixel.
+template <bool DEFER>
+DDLPC_DEVICE void head32_softmax(const uint4 yv, const bool valid, const Head32W* __restrict__ wl,
+                                 const float (&sc)[8], const float (&sh)[8], float (&y8)[8], uint4& fb,
+                                 f32x4_t& z, float& m, float (&e)[4], float& se) {
   unpack8(yv, y8);
   if (DEFER) {
     // the activation as materialised (bf16 of relu(y * scale + shift)), packed: two channels
@@ -639,29 +683,73 @@ DDLPC_DEVICE void head32_step(const uint4 yv, const int lab, const bool valid, c
   const uint4 fz = valid ? fb : make_uint4(0, 0, 0, 0);
   // (the lane's constant operands are read from LDS where they are used: held in VGPRs across
   // the step loop they cost 20 registers and a wave per SIMD of occupancy)
-  f32x4_t z = mfma16x16x32(wl->zh, fz, wl->b4);
+  z = mfma16x16x32(wl->zh, fz, wl->b4);
   z = mfma16x16x32(wl->zl, fz, z);
-  float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+  m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
   m = rows4_max(m);
-  float e[4], se = 0.f;
+  se = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) { e[i] = __expf(z[i] - m); se += e[i]; }
   se = rows4_sum(se);
+}
+
+// the label's logit and the first-maximum class of a pixel, on every lane of the pixel
+DDLPC_DEVICE void head32_pick(const f32x4_t z, float m, int lab, int g, float& zy, int& am) {
+  float t = 0.f;
+  int c = 16;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    t = (4 * g + i == lab) ? z[i] : t;
+    c = (z[i] == m && c == 16) ? 4 * g + i : c;     // first maximum
+  }
+  zy = rows4_sum(t);
+  am = rows4_min_i(c);
+}
+
+// one 16-pixel step of a wave: from the lane's 8 raw channels yv (pixel n, channels 8g..),
+// its label and validity -> the activation f (BN + ReLU when DEFER, bf16-rounded), the 4
+// dlogits d (classes 4g..4g+3, scaled by gs; zero for ignored / tail pixels), dA before
+// rounding (o8, the lane's 8 channels) and rounded (pk); LOSS extras: lse, the label's
+// logit, the arg-max class (valid on every lane of the pixel).  gs carries the pixel's class
+// weight when there are weights.  WT only keeps the weighted kernels' instantiation apart: this
+// function is internal, and the unweighted fused forward passes the constant gs = 1, which the
+// compiler propagates into an instantiation whose every caller does (measured: with a shared
+// instantiation that kernel came out 22 instructions longer and 2.7 % slower)
+// DICE: dt = the table's A[16] | B[16] in LDS, gd = the upstream dL — the Dice dlogits
+// p_i (g_i - sum_c p_c g_c) gd join the CE ones (one more rows4_sum per step)
+template <bool DEFER, bool LOSS, bool WT, bool DICE = false>
+DDLPC_DEVICE void head32_step(const uint4 yv, const int lab, const bool valid, const Head32W* __restrict__ wl,
+                              const float (&sc)[8], const float (&sh)[8], float gs, int ignore_index,
+                              int g, float (&y8)[8], uint4& fb, float (&d)[4], uint2& bh2, uint2& bl2,
+                              float (&o8)[8], uint4& pk, float& lse, float& zy, int& am,
+                              const float* __restrict__ dt = nullptr, float gd = 0.f) {
+  f32x4_t z;
+  float m, e[4], se;
+  head32_softmax<DEFER>(yv, valid, wl, sc, sh, y8, fb, z, m, e, se);
   const float inv = __builtin_amdgcn_rcpf(se);     // (se >= 1: the max term is exp(0))
   const bool live = valid && lab != ignore_index;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) d[i] = live ? (e[i] * inv - (4 * g + i == lab ? 1.f : 0.f)) * gs : 0.f;
-  if (LOSS) {
-    lse = m + __logf(se);
-    float t = 0.f;
-    int c = 16;
+  if (DICE) {
+    const float4 A4 = *reinterpret_cast<const float4*>(dt + 4 * g);
+    const float4 B4 = *reinterpret_cast<const float4*>(dt + MAXK + 4 * g);
+    const float Ai[4] = {A4.x, A4.y, A4.z, A4.w}, Bi[4] = {B4.x, B4.y, B4.z, B4.w};
+    float p[4], gk[4], dot = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      t = (4 * g + i == lab) ? z[i] : t;
-      c = (z[i] == m && c == 16) ? 4 * g + i : c;   // first maximum
+      p[i] = e[i] * inv;
+      gk[i] = dice_g(Ai[i], Bi[i], 4 * g + i == lab);
+      dot = fmaf(p[i], gk[i], dot);
     }
-    zy = rows4_sum(t);
-    am = rows4_min_i(c);
+    dot = rows4_sum(dot);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      d[i] = live ? fmaf(dice_dz(p[i], gk[i], dot), gd, (p[i] - (4 * g + i == lab ? 1.f : 0.f)) * gs) : 0.f;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] = live ? (e[i] * inv - (4 * g + i == lab ? 1.f : 0.f)) * gs : 0.f;
+  }
+  if (LOSS) {
+    lse = m + __logf(se);
+    head32_pick(z, m, lab, g, zy, am);
   }
   // dA: hi / lo splits of the dlogits as the B operand (classes 4g..4g+3 of pixel n; also the
   // caller's dWh staging)
@@ -704,16 +792,21 @@ struct Head32Ld {
 // partials), the dA store (STORE), and with LOSS the training forward's loss / hits / count at
 // a unit gradient scale.  WT: class weights (cw [K], staged as 16 slots, the padded ones 0) —
 // the pixel's weight multiplies gs (hence every dlogit) and the loss / count terms.
-template <bool DEFER, bool STORE, bool LOSS, bool WT>
+// DICE: the Dice dlogits are added in head32_step (dice = the table).
+template <bool DEFER, bool STORE, bool LOSS, bool WT, bool DICE = false>
 __global__ __launch_bounds__(256, 4) void head32_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, bf16_t* __restrict__ dA, float* __restrict__ dWp,
     long long P, int ignore_index, const float* __restrict__ bn4, float* __restrict__ bnpart,
     int Kreal, float* __restrict__ lossp, int groups, long long gsteps,
-    const float* __restrict__ cw) {
+    const float* __restrict__ cw, const float* __restrict__ dice) {
   static_assert(!LOSS || (DEFER && !STORE), "the fused forward is the deferred stats pass");
+  static_assert(!(LOSS && DICE), "the Dice forward is head_dice_fwd");
   constexpr int C = 32;
+  __shared__ __attribute__((aligned(16))) float sDice[2 * MAXK];
+  if (DICE) load_dice(dice, sDice);
+  const float gd = DICE ? (gscale != nullptr ? gscale[0] : 1.0f) : 0.f;
   // BN groups (a batched window, groups > 1): the deferred BatchNorm has per-group statistics
   // bn4 [groups][4][C]; the grid is groups x Rb workgroups and workgroup b walks only the
   // 16-pixel steps of group b / Rb (gsteps per group: a step never straddles two groups), so
@@ -797,8 +890,8 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
         wy = class_w<MAXK>(sCW, lab, 0.f);
         gsw = gs * wy;
       }
-      head32_step<DEFER, LOSS, WT>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh, gsw, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
-                               lse, zy, am);
+      head32_step<DEFER, LOSS, WT, DICE>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh, gsw, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
+                                         lse, zy, am, DICE ? sDice + opaque_zero() : nullptr, gd);
       if (STORE && valid) *reinterpret_cast<uint4*>(dA + px * C + 8 * g) = pk;
       // dWh via the LDS transpose: act row (the lane's 8 channels; zero for tail pixels),
       // dlogits hi / lo (the lane's 4 classes; zero for tail pixels already)
@@ -906,15 +999,19 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(
 
 // The C = 32 counterpart of head_bn_apply_kernel: dA recomputed exactly as head32_kernel
 // stores it, the deferred BatchNorm's backward applied in registers (bn_bwd2_kernel's apply
-// arithmetic), dY stored.  A HEAD32_DA-deep load pipeline.  WT: as head32_kernel.
-template <bool WT>
+// arithmetic), dY stored.  A HEAD32_DA-deep load pipeline.  WT, DICE: as head32_kernel.
+template <bool WT, bool DICE = false>
 __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
     const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
     const int64_t* __restrict__ labels, const float* __restrict__ gscale,
     const float* __restrict__ stats3, const float* __restrict__ bn4,
     const float* __restrict__ coefs, bf16_t* __restrict__ dY, long long P, int ignore_index,
-    int Kreal, int groups, long long gsteps, const float* __restrict__ cw) {
+    int Kreal, int groups, long long gsteps, const float* __restrict__ cw,
+    const float* __restrict__ dice) {
   constexpr int C = 32;
+  __shared__ __attribute__((aligned(16))) float sDice[2 * MAXK];
+  if (DICE) load_dice(dice, sDice);
+  const float gd = DICE ? (gscale != nullptr ? gscale[0] : 1.0f) : 0.f;
   // scale | shift | invstd | -mean*invstd | k | m1 | m2 (the BN backward coefficients)
   __shared__ __attribute__((aligned(16))) float sK[7][C];
   __shared__ Head32W sW[64];                       // the lanes' constant MFMA operands
@@ -970,9 +1067,9 @@ __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
       int am;
       uint4 pk, fb;
       uint2 bh2, bl2;
-      head32_step<true, false, WT>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh,
-                               WT ? gs * class_w<MAXK>(sCW, lab, 0.f) : gs, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
-                               lse, zy, am);
+      head32_step<true, false, WT, DICE>(yv, lab, valid, sW + opaque_zero() + lane, sc, sh,
+                                         WT ? gs * class_w<MAXK>(sCW, lab, 0.f) : gs, ignore_index, g, y8, fb, d, bh2, bl2, o8, pk,
+                                         lse, zy, am, DICE ? sDice + opaque_zero() : nullptr, gd);
       float rr[8], o[8], is[8], nm[8], k1[8], m1[8], m2[8];
       unpack8(pk, rr);
       k8(2, is); k8(3, nm); k8(4, k1); k8(5, m1); k8(6, m2);
@@ -988,6 +1085,233 @@ __global__ __launch_bounds__(256, 4) void head32_apply_kernel(
       load(sl < steps ? sl : s0, q4.y[j], q4.l[j]);
     }
   }
+}
+
+// ===================================================================== the Dice forward
+// head_dice_fwd: the training forward when the loss has a soft-Dice term.  One read of the
+// activation and the labels; per workgroup a row [loss terms | hits | count or weight sum] (the
+// conventions of head_ce_fwd) and a row I[16] | S[16] | Y[16] of the Dice sums over the
+// workgroup's valid pixels (head_math.h).  No gradient work: the Dice gradient needs the sums
+// of the whole call first (head_dice_coefs_kernel), so nothing of the backward can be formed
+// here.  The grid is a function of the pixel count and num_cus only (head_dice_fwd_blocks), the
+// reductions run in a fixed order, no atomics: the same bits on every run.
+constexpr int DICE_FWD_PER_CU = 4;      // resident workgroups per CU that size the grid
+
+// C = 32: head32_kernel's MFMA layout and load pipeline.  A lane holds classes 4g..4g+3 of
+// pixel n after the two logit MFMAs, so I, S, Y are 12 fp32 accumulators per lane across the
+// step loop and need no transpose; at the end they are summed over the 16 pixel lanes of each
+// row (DPP), then over the 4 waves through LDS in wave order.
+template <bool DEFER, bool WT>
+__global__ __launch_bounds__(256, DICE_FWD_PER_CU) void head32_dice_fwd_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int64_t* __restrict__ labels, float* __restrict__ lossp, float* __restrict__ dicep,
+    long long P, int ignore_index, const float* __restrict__ bn4, int Kreal,
+    const float* __restrict__ cw) {
+  constexpr int C = 32;
+  __shared__ float sred[4][4][15];                 // [wave][row g][I 4 | S 4 | Y 4 | loss 3]
+  __shared__ __attribute__((aligned(16))) float sK[2][C];   // scale | shift
+  __shared__ Head32W sW[64];                       // the lanes' constant MFMA operands
+  __shared__ float sCW[MAXK];                      // class weights (WT)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  if (tid < 64) sW[tid] = head32_weights(Wh, bh, Kreal, lane);
+  if (WT) load_cw<MAXK>(cw, Kreal, sCW);
+  if (DEFER && tid < C) {
+    sK[0][tid] = bn4[2 * C + tid];
+    sK[1][tid] = bn4[3 * C + tid];
+  }
+  __syncthreads();
+  float sI[4], sS[4], sY[4], ls[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { sI[i] = 0.f; sS[i] = 0.f; sY[i] = 0.f; }
+  const long long steps = (P + 15) / 16;
+  const long long wstride = (long long)gridDim.x * 4;
+  const long long s0 = (long long)blockIdx.x * 4 + wave;
+  auto load = [&](long long st, uint4& yv, int& lb) __attribute__((always_inline)) {
+    const long long px = st * 16 + n;
+    const long long pc = px < P ? px : 0;
+    yv = *reinterpret_cast<const uint4*>(a + pc * C + 8 * g);
+    lb = reinterpret_cast<const int*>(labels)[2 * pc];
+  };
+  Head32Ld<HEAD32_D> q4;
+#pragma unroll
+  for (int j = 0; j < HEAD32_D; ++j) load(s0 + j * wstride < steps ? s0 + j * wstride : s0, q4.y[j], q4.l[j]);
+#pragma unroll 1
+  for (long long sb = s0; sb < steps; sb += HEAD32_D * wstride) {   // wave-uniform trip count
+#pragma unroll
+    for (int j = 0; j < HEAD32_D; ++j) {
+      // (branch-free, slot refilled after its last use: see head32_kernel)
+      const long long s = sb + j * wstride;
+      const uint4 yv = q4.y[j];
+      const int lab = q4.l[j];
+      const bool valid = s < steps && s * 16 + n < P;
+      float sc[8], sh[8];
+      if (DEFER) {
+        const float4* kp = reinterpret_cast<const float4*>(&sK[0][0] + opaque_zero() + 8 * g);
+        const float4 a0 = kp[0], a1 = kp[1], c0 = kp[8], c1 = kp[9];
+        sc[0] = a0.x; sc[1] = a0.y; sc[2] = a0.z; sc[3] = a0.w; sc[4] = a1.x; sc[5] = a1.y; sc[6] = a1.z; sc[7] = a1.w;
+        sh[0] = c0.x; sh[1] = c0.y; sh[2] = c0.z; sh[3] = c0.w; sh[4] = c1.x; sh[5] = c1.y; sh[6] = c1.z; sh[7] = c1.w;
+      } else {
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) { sc[jj] = 0.f; sh[jj] = 0.f; }
+      }
+      float y8[8], m, e[4], se, zy;
+      int am;
+      uint4 fb;
+      f32x4_t z;
+      head32_softmax<DEFER>(yv, valid, sW + opaque_zero() + lane, sc, sh, y8, fb, z, m, e, se);
+      head32_pick(z, m, lab, g, zy, am);
+      const float inv = __builtin_amdgcn_rcpf(se);   // (se >= 1: the max term is exp(0))
+      const bool live = valid && lab != ignore_index;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {                  // (padded classes: e = exp(-inf) = 0)
+        const float p = live ? e[i] * inv : 0.f;
+        const bool hit = live && 4 * g + i == lab;
+        sS[i] += p;
+        sI[i] += hit ? p : 0.f;
+        sY[i] += hit ? 1.f : 0.f;
+      }
+      const bool cnt_px = g == 0 && valid;           // (row g = 0 counts a pixel)
+      const float wy = WT ? class_w<MAXK>(sCW, lab, 0.f) : 1.f;
+      ls[0] += (cnt_px && live) ? (m + __logf(se) - zy) * wy : 0.f;
+      ls[1] += (cnt_px && am == lab) ? 1.f : 0.f;
+      ls[2] += (cnt_px && live) ? wy : 0.f;
+      const long long sl = s + HEAD32_D * wstride;
+      load(sl < steps ? sl : s0, q4.y[j], q4.l[j]);
+    }
+  }
+  float red[15];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { red[i] = row16_sum(sI[i]); red[4 + i] = row16_sum(sS[i]); red[8 + i] = row16_sum(sY[i]); }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) red[12 + i] = row16_sum(ls[i]);
+  if (n == 0)
+#pragma unroll
+    for (int i = 0; i < 15; ++i) sred[wave][g][i] = red[i];
+  __syncthreads();
+  if (tid < kDiceRow) {                              // [I (c) | S (c) | Y (c)], class c = 4 g + i
+    const int j = tid / MAXK, c = tid % MAXK;
+    float t = 0.f;
+    for (int wv = 0; wv < 4; ++wv) t += sred[wv][c >> 2][4 * j + (c & 3)];
+    dicep[(long long)blockIdx.x * kDiceRow + tid] = t;
+  } else if (tid < kDiceRow + 3) {
+    float t = 0.f;
+    for (int wv = 0; wv < 4; ++wv) t += sred[wv][0][12 + tid - kDiceRow];
+    lossp[(long long)blockIdx.x * 3 + tid - kDiceRow] = t;
+  }
+}
+
+// C in {8, 16, 64}: the channel-split layout (G = C / 8 lanes per pixel, split_softmax).  After
+// the DPP sums every lane of a pixel holds all K softmax terms; the classes are shared out among
+// the G lanes — lane cg accumulates the classes k = cg (mod G) in slot k / G — so a lane
+// carries 3 ceil(K / G) accumulators instead of 3 K, and every pixel is counted once.  Reduced
+// over the lanes with equal cg (shuffles over the pixel-slot bits), then over the waves in order.
+template <int C, int K, bool DEFER>
+__global__ __launch_bounds__(256) void head_dice_fwd_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int64_t* __restrict__ labels, float* __restrict__ lossp, float* __restrict__ dicep,
+    long long P, int ignore_index, const float* __restrict__ bn4, int Kreal,
+    const float* __restrict__ cw) {
+  constexpr int G = C / 8;                          // lanes per pixel
+  constexpr int PPB = 256 / G;                      // pixels per workgroup step
+  constexpr int NS = (K + G - 1) / G;               // class slots per lane
+  constexpr int NACC = 3 * NS + 3;                  // I | S | Y slots, loss | hits | count
+  __shared__ float sred[4][G][NACC];
+  __shared__ __attribute__((aligned(16))) float sW[K * C];      // Wh, padded classes zero
+  __shared__ float scw[K];                                       // class weights (ones without)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cg = lane % G, c8 = cg * 8;
+  for (int i = tid; i < K * C; i += 256) sW[i] = i < Kreal * C ? Wh[i] : 0.f;
+  load_cw<K>(cw, Kreal, scw);
+  const float wout = cw != nullptr ? 0.f : 1.f;
+  float bk[K], sc[8], sh[8];
+#pragma unroll
+  for (int k = 0; k < K; ++k) bk[k] = k < Kreal ? bh[k] : -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sc[j] = DEFER ? bn4[2 * C + c8 + j] : 0.f;
+    sh[j] = DEFER ? bn4[3 * C + c8 + j] : 0.f;
+  }
+  __syncthreads();
+  float acc[NACC];
+#pragma unroll
+  for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
+  const long long stride = (long long)gridDim.x * PPB;
+  // (one pixel ahead: the next activation + label loads are in flight while this one computes)
+  long long px = (long long)blockIdx.x * PPB + tid / G;
+  uint4 a_nx = make_uint4(0, 0, 0, 0);
+  int64_t l_nx = 0;
+  if (px < P) { a_nx = *reinterpret_cast<const uint4*>(a + px * C + c8); l_nx = labels[px]; }
+#pragma unroll 1
+  for (; px < P; px += stride) {
+    const uint4 a_cur = a_nx;
+    const int64_t lab = l_nx;
+    if (px + stride < P) {
+      a_nx = *reinterpret_cast<const uint4*>(a + (px + stride) * C + c8);
+      l_nx = labels[px + stride];
+    }
+    float y8[8], f[8], e[K], se, m, zy;
+    int am;
+    split_softmax<C, K, DEFER>(a_cur, lab, reinterpret_cast<const f2_t*>(sW + opaque_zero() + c8), bk, sc, sh,
+                               y8, f, e, se, m, zy, am);
+    const float inv = __builtin_amdgcn_rcpf(se);    // (se >= 1: the max term is exp(0))
+    const bool live = lab != ignore_index;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const bool own = live && cg == k % G;         // (k % G is a constant: one compare)
+      const float p = own ? e[k] * inv : 0.f;
+      const bool hit = own && k == lab;
+      acc[NS + k / G] += p;
+      acc[k / G] += hit ? p : 0.f;
+      acc[2 * NS + k / G] += hit ? 1.f : 0.f;
+    }
+    if (cg == 0) {
+      const float wy = class_w<K>(scw, lab, wout);
+      if (live) { acc[3 * NS] += (m + __logf(se) - zy) * wy; acc[3 * NS + 2] += wy; }
+      acc[3 * NS + 1] += am == lab ? 1.f : 0.f;
+    }
+  }
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1)
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
+  if (lane < G)
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) sred[wave][lane][i] = acc[i];
+  __syncthreads();
+  if (tid < kDiceRow) {                              // [I (c) | S (c) | Y (c)]; classes >= K: 0
+    const int j = tid / MAXK, c = tid % MAXK;
+    float t = 0.f;
+    if (c < K)
+      for (int wv = 0; wv < 4; ++wv) t += sred[wv][c % G][j * NS + c / G];
+    dicep[(long long)blockIdx.x * kDiceRow + tid] = t;
+  } else if (tid < kDiceRow + 3) {                   // lanes cg == 0 hold them
+    float t = 0.f;
+    for (int wv = 0; wv < 4; ++wv) t += sred[wv][0][3 * NS + tid - kDiceRow];
+    lossp[(long long)blockIdx.x * 3 + tid - kDiceRow] = t;
+  }
+}
+
+// head_dice_coefs: one workgroup sums the nb rows of both kinds in a fixed order in fp64 and
+// thread 0 writes out3 = [L_CE + lambda dice, hits, count] and the table (dice_finalize).
+// lambda and eps reach this kernel only.
+__global__ __launch_bounds__(256) void head_dice_coefs_kernel(
+    const float* __restrict__ lossp, const float* __restrict__ dicep, int nb, int K, float lambda,
+    float eps, float* __restrict__ out3, float* __restrict__ tab) {
+  constexpr int NV = kDiceRow + 3;                   // I | S | Y | loss | hits | count
+  __shared__ double part[4][NV];                     // 4 row quarters x NV columns
+  const int tid = threadIdx.x, col = tid % 64, qt = tid / 64;
+  if (col < NV) {                                    // quarter qt sums rows qt, qt + 4, ...
+    double s = 0;
+    for (int r = qt; r < nb; r += 4)
+      s += col < kDiceRow ? dicep[(long long)r * kDiceRow + col] : lossp[(long long)r * 3 + col - kDiceRow];
+    part[qt][col] = s;
+  }
+  __syncthreads();
+  __shared__ double tot[NV];
+  if (tid < NV) tot[tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+  __syncthreads();
+  if (tid == 0) dice_finalize(tot + kDiceRow, tot, K, lambda, eps, out3, tab);
 }
 
 template <int C, int K, bool DEFER>
@@ -1227,12 +1551,34 @@ int head_ce_bwd_blocks(int C, int K, long long P, int num_cus) {
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         const float* gscale, const float* stats3, bf16_t* dA, float* dW_partial,
                         int nblocks, long long P, int C, int K, int ignore_index, const float* bn4,
-                        float* bnpart, hipStream_t st, const float* cw) {
+                        float* bnpart, hipStream_t st, const float* cw, const float* dice) {
+  if (dice != nullptr) {                             // the DICE instantiations, on the same grids
+    if (C == 32 && K <= MAXK) {
+#define HEAD32_BWD(D_, S_)                                                                          \
+  HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<D_, S_, false, WT, true>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, \
+                                   labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, \
+                                   nullptr, 1, 0LL, cw, dice))
+      if (bn4 != nullptr && dA == nullptr) HEAD32_BWD(true, false);
+      else if (bn4 != nullptr) HEAD32_BWD(true, true);
+      else HEAD32_BWD(false, true);
+#undef HEAD32_BWD
+      return;
+    }
+#define HEAD_BWD(...)                                                                              \
+  hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, __VA_ARGS__, false, true>), dim3(nblocks), dim3(256), 0, st, a, Wh, \
+                     bh, labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, cw, dice)
+    if (bn4 != nullptr && dA == nullptr)
+      HEAD_SWITCH(C, K, HEAD_BWD(true, false));
+    else
+      HEAD_SWITCH_D(C, K, bn4, HEAD_BWD(DD, true));
+#undef HEAD_BWD
+    return;
+  }
   if (C == 32 && K <= MAXK) {
 #define HEAD32_BWD(D_, S_)                                                                          \
   HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<D_, S_, false, WT>), dim3(nblocks), dim3(256), 0, st, a, Wh, \
                                    bh, labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4,   \
-                                   bnpart, K, nullptr, 1, 0LL, cw))
+                                   bnpart, K, nullptr, 1, 0LL, cw, nullptr))
     if (bn4 != nullptr && dA == nullptr) HEAD32_BWD(true, false);
     else if (bn4 != nullptr) HEAD32_BWD(true, true);
     else HEAD32_BWD(false, true);
@@ -1241,7 +1587,7 @@ void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const
   }
 #define HEAD_BWD(...)                                                                              \
   hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, __VA_ARGS__>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, \
-                     labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, cw)
+                     labels, gscale, stats3, dA, dW_partial, P, ignore_index, bn4, bnpart, K, nullptr, cw, nullptr)
   if (bn4 != nullptr && dA == nullptr)               // stats pass of the two-pass backward
     HEAD_SWITCH(C, K, HEAD_BWD(true, false));
   else
@@ -1269,11 +1615,11 @@ void head_ce_fwd_stats_launch(const bf16_t* a, const float* Wh, const float* bh,
     HEAD32_WT(cw, hipLaunchKernelGGL((head32_kernel<true, false, true, WT>), dim3(nblocks), dim3(256), 0, st, a,
                                      Wh, bh, labels, nullptr, nullptr, nullptr, dW_partial, P, ignore_index,
                                      bn4, bnpart, K, loss_partial, groups,
-                                     groups > 1 ? P / groups / 16 : 0LL, cw));
+                                     groups > 1 ? P / groups / 16 : 0LL, cw, nullptr));
   else
     HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_ce_bwd_kernel<CC, KK, true, false, true>), dim3(nblocks),
                                          dim3(256), 0, st, a, Wh, bh, labels, nullptr, nullptr, nullptr,
-                                         dW_partial, P, ignore_index, bn4, bnpart, K, loss_partial, cw));
+                                         dW_partial, P, ignore_index, bn4, bnpart, K, loss_partial, cw, nullptr));
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, loss_partial, nblocks, out3);
 }
 
@@ -1286,20 +1632,63 @@ int head_bn_apply_blocks(long long P, int C) {
 void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                           const float* gscale, const float* stats3, const float* bn4,
                           const float* coefs, bf16_t* dY, long long P, int C, int K,
-                          int ignore_index, int num_cus, hipStream_t st, int groups, const float* cw) {
+                          int ignore_index, int num_cus, hipStream_t st, int groups, const float* cw,
+                          const float* dice) {
   if (C == 32 && K <= MAXK) {
     static const int per_cu = head32_per_cu(reinterpret_cast<const void*>(&head32_apply_kernel<false>));
     const int nb = head32_grid(P, per_cu, num_cus);
     const int grid = groups > 1 ? groups * std::max(1, nb / groups) : nb;
+    if (dice != nullptr) {
+      HEAD32_WT(cw, hipLaunchKernelGGL((head32_apply_kernel<WT, true>), dim3(grid), dim3(256), 0, st, a, Wh, bh,
+                                       labels, gscale, stats3, bn4, coefs, dY, P, ignore_index, K, groups,
+                                       groups > 1 ? P / groups / 16 : 0LL, cw, dice));
+      return;
+    }
     HEAD32_WT(cw, hipLaunchKernelGGL((head32_apply_kernel<WT>), dim3(grid), dim3(256), 0, st, a, Wh, bh,
                                      labels, gscale, stats3, bn4, coefs, dY, P, ignore_index, K, groups,
-                                     groups > 1 ? P / groups / 16 : 0LL, cw));
+                                     groups > 1 ? P / groups / 16 : 0LL, cw, nullptr));
     return;
   }
   const int nb = head_bn_apply_blocks(P, C);
+  if (dice != nullptr) {
+    HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_bn_apply_kernel<CC, KK, true>), dim3(nb), dim3(256), 0, st,
+                                         a, Wh, bh, labels, gscale, stats3, bn4, coefs, dY, P,
+                                         ignore_index, K, cw, dice));
+    return;
+  }
   HEAD_SWITCH(C, K, hipLaunchKernelGGL((head_bn_apply_kernel<CC, KK>), dim3(nb), dim3(256), 0, st,
                                        a, Wh, bh, labels, gscale, stats3, bn4, coefs, dY, P,
-                                       ignore_index, K, cw));
+                                       ignore_index, K, cw, nullptr));
+}
+
+// the Dice forward's grid: a function of the pixel count and num_cus only
+int head_dice_fwd_blocks(int C, long long P, int num_cus) {
+  if (C == 32) return head32_grid(P, DICE_FWD_PER_CU, num_cus);
+  const long long ppb = 256 / (C / 8);
+  return (int)std::max<long long>(1, std::min<long long>((P + ppb - 1) / ppb, (long long)DICE_FWD_PER_CU * num_cus));
+}
+
+void head_dice_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
+                          const float* bn4, float* loss_partial, float* dice_partial, int nblocks,
+                          long long P, int C, int K, int ignore_index, hipStream_t st, const float* cw) {
+  if (C == 32 && K <= MAXK) {
+    if (bn4 != nullptr)
+      HEAD32_WT(cw, hipLaunchKernelGGL((head32_dice_fwd_kernel<true, WT>), dim3(nblocks), dim3(256), 0, st, a, Wh,
+                                       bh, labels, loss_partial, dice_partial, P, ignore_index, bn4, K, cw));
+    else
+      HEAD32_WT(cw, hipLaunchKernelGGL((head32_dice_fwd_kernel<false, WT>), dim3(nblocks), dim3(256), 0, st, a, Wh,
+                                       bh, labels, loss_partial, dice_partial, P, ignore_index, bn4, K, cw));
+  } else {
+    HEAD_SWITCH_D(C, K, bn4, hipLaunchKernelGGL((head_dice_fwd_kernel<CC, KK, DD>), dim3(nblocks), dim3(256), 0,
+                                                st, a, Wh, bh, labels, loss_partial, dice_partial, P,
+                                                ignore_index, bn4, K, cw));
+  }
+}
+
+void head_dice_coefs_launch(const float* loss_partial, const float* dice_partial, int nblocks, int K,
+                            float lambda, float eps, float* out3, float* table, hipStream_t st) {
+  hipLaunchKernelGGL(head_dice_coefs_kernel, dim3(1), dim3(256), 0, st, loss_partial, dice_partial, nblocks, K,
+                     lambda, eps, out3, table);
 }
 
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits,

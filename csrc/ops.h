@@ -304,7 +304,8 @@ int head_fwd_stats_blocks(int C, int K, long long P, int num_cus, int groups = 1
 void head_ce_bwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
                         const float* gscale, const float* stats3, bf16_t* dA, float* dW_partial,
                         int nblocks, long long P, int C, int K, int ignore_index, const float* bn4,
-                        float* bnpart, hipStream_t st, const float* cw = nullptr);
+                        float* bnpart, hipStream_t st, const float* cw = nullptr,
+                        const float* dice = nullptr);
 // two-pass backward with the deferred BatchNorm of the last decoder block: dA == nullptr in
 // head_ce_bwd_launch runs the stats pass (dWh, dbh, BN partials); this second pass
 // recomputes dA and writes that BatchNorm's dY (coefs = [k | m1 | m2] x C); its C = 32 grid
@@ -320,7 +321,21 @@ void head_bn_apply_launch(const bf16_t* a, const float* Wh, const float* bh, con
                           const float* gscale, const float* stats3, const float* bn4,
                           const float* coefs, bf16_t* dY, long long P, int C, int K,
                           int ignore_index, int num_cus, hipStream_t st, int groups = 1,
+                          const float* cw = nullptr, const float* dice = nullptr);
+// Soft-Dice term (head_math.h).  head_dice_fwd_launch: the forward kernel — loss_partial
+// [nblocks][3] by head_ce_fwd's conventions, dice_partial [nblocks][3][16] = I | S | Y; nblocks
+// from head_dice_fwd_blocks (a function of P and num_cus only).  head_dice_coefs_launch: the
+// one-workgroup finalize — out3 = [L_CE + lambda dice, hits, count], table float[40] =
+// A[16] | B[16] | dice | L_CE | 0...; lambda and eps reach no other kernel.  dice (the table)
+// in head_ce_bwd_launch / head_bn_apply_launch selects the DICE instantiations of the backward
+// kernels, on the same grids; every pass of one backward takes the same table
+int head_dice_fwd_blocks(int C, long long P, int num_cus);
+void head_dice_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
+                          const float* bn4, float* loss_partial, float* dice_partial, int nblocks,
+                          long long P, int C, int K, int ignore_index, hipStream_t st,
                           const float* cw = nullptr);
+void head_dice_coefs_launch(const float* loss_partial, const float* dice_partial, int nblocks, int K,
+                            float lambda, float eps, float* out3, float* table, hipStream_t st);
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
 // whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the

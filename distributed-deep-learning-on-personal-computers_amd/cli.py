@@ -24,6 +24,8 @@ counterpart of ``train --augment d4``.)
 ``--class-weights 1,1,1,1,4,4`` (one number per class) or ``--class-weights median_freq`` (from
 the training split's labels) trains with ``CrossEntropyLoss(weight=...)``, fused into the head
 kernels — the validation loss stays unweighted, the per-class IoU shows the effect;
+``--dice-weight 1 --dice-smooth 1`` adds a soft-Dice term to the training loss (cross-entropy +
+lambda * dice, formed inside the head kernels);
 ``config`` prints the resolved configuration (handy for writing a YAML to start from).
 """
 from __future__ import annotations

@@ -121,6 +121,11 @@ class TrainConfig:
     # None | "w0,w1,..." (out_classes non-negative numbers, not all zero; a YAML list too)
     # | "median_freq" (from the training split's label histogram; real data only)
     class_weights: Optional[str] = None
+    # soft-Dice term of the training loss, L = L_CE + dice_weight * dice (0: off; fused into the
+    # head kernels; per rank and per micro-batch, so not combined with bn_window > 1; validation
+    # stays the plain cross-entropy).  dice_smooth: the eps of numerator and denominator
+    dice_weight: float = 0.0
+    dice_smooth: float = 1.0
     # ---- optimisation ----------------------------------------------------------
     batch_per_gpu: int = 1               # batch_size, ref.py:686
     accum_steps: int = 1                 # frequency_sending_gradients, ref.py:685
@@ -239,6 +244,11 @@ class TrainConfig:
             raise ValueError("zoom_min and zoom_max must satisfy 0.25 <= zoom_min <= zoom_max <= 4")
         if not 0.0 <= self.rotate_deg <= 180.0:
             raise ValueError("rotate_deg must be in [0, 180]")
+        if not self.dice_weight >= 0 or not self.dice_smooth > 0:
+            raise ValueError("dice_weight must be >= 0 and dice_smooth > 0")
+        if self.dice_weight > 0 and self.bn_window > 1:
+            raise ValueError("dice_weight > 0 is not combined with bn_window > 1 (the Dice sums are per "
+                             "micro-batch; bn_window=-1 or 0 runs the micro-batches one by one)")
         if isinstance(self.class_weights, (list, tuple)):      # a YAML / JSON list
             self.class_weights = ",".join(repr(float(v)) for v in self.class_weights)
         cw = parse_class_weights(self.class_weights, self.model.out_classes)

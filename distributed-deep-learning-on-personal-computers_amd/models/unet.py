@@ -98,6 +98,18 @@ class UpBlock(nn.Module):
         return self.double_conv(x)
 
 
+def soft_dice(logits, y, ignore_index: int = -100, smooth: float = 1.0):
+    """``1 - mean_c (2 I_c + eps) / (S_c + Y_c + eps)`` over the valid pixels of ``logits``
+    ``[N, K, ...]`` / labels ``y``; 0 when every pixel is ignored."""
+    K = logits.shape[1]
+    valid = (y != ignore_index).unsqueeze(1)
+    p = torch.softmax(logits, 1) * valid
+    hot = F.one_hot(torch.where(valid.squeeze(1), y, torch.zeros_like(y)), K).movedim(-1, 1) * valid
+    dims = [0] + list(range(2, logits.dim()))
+    I, S, Y = (p * hot).sum(dims), p.sum(dims), hot.sum(dims).to(p.dtype)
+    return 1.0 - ((2.0 * I + smooth) / (S + Y + smooth)).mean()
+
+
 class UNet(nn.Module):
     """Reference-compatible U-Net (ref.py:620-656), generalised to depth/dims."""
 
@@ -159,7 +171,8 @@ class UNet(nn.Module):
             x = blk(x, s)
         return self.conv_last(x)
 
-    def loss_and_correct(self, x, y, ignore_index: int = -100, class_weight=None):
+    def loss_and_correct(self, x, y, ignore_index: int = -100, class_weight=None,
+                         dice_weight: float = 0.0, dice_smooth: float = 1.0):
         """Mean cross-entropy (nn.CrossEntropyLoss defaults, ref.py:703) and the number of
         correctly classified pixels (ref.py:775).  The HIP path fuses the 1x1 head,
         softmax, CE, its gradient and the arg-max into one kernel (logits never hit HBM).
@@ -168,13 +181,33 @@ class UNet(nn.Module):
         ``CrossEntropyLoss(weight=...)``: the loss is ``sum w[y_p] ce_p / sum w[y_p]`` over the
         valid pixels; the hit count stays unweighted.  Where the weight sum is 0 (every pixel
         ignored, or every valid label of weight 0) the engine gives loss 0 and zero gradients;
-        this stock path gives PyTorch's NaN."""
+        this stock path gives PyTorch's NaN.
+
+        ``dice_weight`` = lambda > 0 adds a soft-Dice term, ``L = L_CE + lambda * dice`` with
+        ``dice = 1 - mean_c (2 I_c + eps) / (S_c + Y_c + eps)``, ``eps = dice_smooth``, where
+        ``I_c = sum p_c [y = c]``, ``S_c = sum p_c`` and ``Y_c = sum [y = c]`` run over the valid
+        pixels of the call (p = softmax; class weights do not enter the sums).  The HIP path
+        forms it inside the head kernels; this stock path computes the same formula."""
         if self._engine is not None:
-            return self._engine.loss_and_correct(x, y, ignore_index, class_weight)
+            return self._engine.loss_and_correct(x, y, ignore_index, class_weight, dice_weight, dice_smooth)
         logits = self.forward_torch(x)
         loss = F.cross_entropy(logits.float(), y, weight=class_weight, ignore_index=ignore_index)
+        if dice_weight > 0:
+            dice = soft_dice(logits.float(), y, ignore_index, dice_smooth)
+            self._dice_terms = torch.stack([dice, loss]).detach()
+            loss = loss + dice_weight * dice
         correct = (logits.detach().argmax(1) == y).sum()
         return loss, correct
+
+    def dice_terms(self):
+        """``(dice, ce)`` of the last ``loss_and_correct`` call with ``dice_weight > 0`` (``None``
+        before one): on the HIP path read from the head's device table, on the stock path kept
+        by that call in ``_dice_terms``.  Copies two floats to the host, so it waits for the
+        device: for logging, not for the step."""
+        t = getattr(self, "_dice_terms", None)
+        if self._engine is not None:
+            t = None if self._engine.dice_table is None else self._engine.dice_table[32:34]
+        return None if t is None else tuple(float(v) for v in t.tolist())
 
     def to_hip(self, strict: bool = True):
         """Attach the operator engine (``ops.fused_unet.UNetEngine``; fails loudly if the kernel

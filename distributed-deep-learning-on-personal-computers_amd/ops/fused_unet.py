@@ -65,6 +65,7 @@ class _GradNote:
     one consumer; a second consumer's sum drops the note)."""
     head: Optional[tuple] = None                   # two-pass head: head_ce_bn_bwd's leading arguments
     class_weight: Optional[torch.Tensor] = None    # ... and the loss's class weights
+    dice: Optional[torch.Tensor] = None            # ... and its soft-Dice table (head_dice_coefs)
     bn_partial: Optional[torch.Tensor] = None      # BN-backward partial rows the consumer reduced
     bn_pscale: Optional[torch.Tensor] = None       # ... and the scale they are still to take
     colsum_rows: Optional[torch.Tensor] = None     # per-channel sums: a transposed conv's db
@@ -315,7 +316,12 @@ class _DoubleConvFn(torch.autograd.Function):
         # ---- BN2 + ReLU (+ unpool + skip sum) backward; deferred into the head: its second
         # pass recomputes dA and applies BN2's backward (the class weights of the loss: the
         # second pass must see the first pass's)
-        if head is not None:
+        if head is not None and note.dice is not None:
+            dy2, dg2, dbe2 = F.head_dice_bn_bwd(*head, s2, note.bn_partial, g2,
+                                                dgamma_out=acc(bn2.weight), dbeta_out=acc(bn2.bias),
+                                                pscale=note.bn_pscale, groups=G,
+                                                class_weight=note.class_weight, dice=note.dice)
+        elif head is not None:
             dy2, dg2, dbe2 = F.head_ce_bn_bwd(*head, s2, note.bn_partial, g2,
                                               dgamma_out=acc(bn2.weight), dbeta_out=acc(bn2.bias),
                                               pscale=note.bn_pscale, groups=G,
@@ -467,16 +473,27 @@ class _BilinearFn(torch.autograd.Function):
 class _HeadCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, wh, bh, labels, ignore_index: int, engine,
-                bn: Optional[torch.Tensor] = None, cw: Optional[torch.Tensor] = None):
+                bn: Optional[torch.Tensor] = None, cw: Optional[torch.Tensor] = None,
+                dice_weight: float = 0.0, dice_smooth: float = 1.0):
         # training with the deferred BN: the forward also runs the backward's statistics
         # pass (unit gradient scale) — one read of the activation and labels for both
         ctx.rows = None
+        ctx.dice = None
         # (Function.forward runs with grad mode off: needs_input_grad says whether a
         # backward will follow)
         # (BN groups: bn = [groups][4][C] per-group statistics, fused forward only —
         # UNetEngine.group_head_defer)
         groups = bn.shape[0] if (bn is not None and bn.dim() == 3) else 0
-        if (bn is not None and engine.head_apply and engine.head_fused_fwd
+        if dice_weight > 0:
+            # soft-Dice term: its gradient needs per-class sums over the whole call, so the
+            # forward cannot run the statistics pass — a forward kernel of its own, the finalize
+            # (out3 with the term, the A | B table), and the table in every backward pass
+            if groups:
+                raise ValueError("the soft-Dice term is not combined with BN groups (bn_window)")
+            lrows, drows = _ops().head_dice_fwd(a, wh, bh, labels, ignore_index, bn4=bn, class_weight=cw)
+            out3, ctx.dice = _ops().head_dice_coefs(lrows, drows, wh.shape[0], dice_weight, dice_smooth)
+            engine.dice_table = ctx.dice
+        elif (bn is not None and engine.head_apply and engine.head_fused_fwd
                 and any(ctx.needs_input_grad[:3])):
             out3, wrows, brows = _ops().head_ce_fwd_stats(a, wh, bh, labels, ignore_index, bn,
                                                           groups=groups, class_weight=cw)
@@ -518,6 +535,10 @@ class _HeadCEFn(torch.autograd.Function):
             wrows, part = ctx.rows
             scale = F.head_grad_scale(out3, gs=gs)         # one launch, on the device
             dw, db = F.head_wgrad_from_rows(wrows, scale, wh.shape[0], wh.shape[1], **grads)
+        elif ctx.dice is not None:
+            da, dw, db, part = F.head_dice_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index, bn4=bn,
+                                               store_da=not two_pass, class_weight=ctx.cw, dice=ctx.dice,
+                                               **grads)
         else:
             da, dw, db, part = F.head_ce_bwd(a, wh, bh, labels, out3, gs, ctx.ignore_index, bn4=bn,
                                              store_da=not two_pass, class_weight=ctx.cw, **grads)
@@ -529,10 +550,10 @@ class _HeadCEFn(torch.autograd.Function):
         if bn is not None:
             da._ddlpc_note = _GradNote(
                 head=(a, wh, bh, labels, out3, gs, ctx.ignore_index) if two_pass else None,
-                class_weight=ctx.cw, bn_partial=part, bn_pscale=scale)
+                class_weight=ctx.cw, dice=ctx.dice, bn_partial=part, bn_pscale=scale)
         if direct:
             dw = db = None
-        return da, dw, db, None, None, None, None, None
+        return da, dw, db, None, None, None, None, None, None, None
 
 
 class _Block:
@@ -681,6 +702,8 @@ class UNetEngine:
         # ... and its statistics pass fused into the training forward (False: separate
         # forward and statistics passes)
         self.head_fused_fwd = True
+        # the last soft-Dice call's device table (head_dice_coefs: [32] dice, [33] cross-entropy)
+        self.dice_table = None
         # 64 -> 64-channel transposed conv: data + weight gradient in one kernel
         # (False: separate kernels, weight gradient on the side stream)
         self.convt_fused = True
@@ -1007,8 +1030,13 @@ class UNetEngine:
         return _ops().head_logits(a, wh.detach().contiguous(), bh.detach(), bn4=s)
 
     def loss_and_correct(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int = -100,
-                         class_weight: Optional[torch.Tensor] = None):
+                         class_weight: Optional[torch.Tensor] = None, dice_weight: float = 0.0,
+                         dice_smooth: float = 1.0):
         """-> (mean cross-entropy over the batch's pixels, correct-pixel count).
+        ``dice_weight`` = lambda > 0 adds ``lambda * dice`` to the loss (soft Dice over the valid
+        pixels of this call with smoothing ``dice_smooth``, ``csrc/head_math.h``; class weights
+        do not enter it); ``self.dice_table`` then holds the call's device table (``[32]`` the
+        Dice term, ``[33]`` the cross-entropy).  Not combined with ``bn_groups``.
         ``class_weight`` (fp32 ``[K]`` on x's device, kept alive by the caller until the
         backward has run): ``cross_entropy(weight=)`` — loss and gradients are normalised by the
         weight sum of the valid pixels instead of their count, the hit count is unweighted, and
@@ -1017,6 +1045,10 @@ class UNetEngine:
         BatchNorm statistics; the running statistics are updated once per micro-batch, in
         order, after the forward (bit-for-bit the update sequence of G forwards)."""
         G = self.bn_groups if self.enc[0].bn1.bn.training else 0
+        if dice_weight < 0 or dice_smooth <= 0:
+            raise ValueError("dice_weight must be >= 0 and dice_smooth > 0")
+        if G >= 1 and dice_weight > 0:
+            raise ValueError("the soft-Dice term is not combined with BN groups (bn_window)")
         if G >= 1:
             if x.shape[0] % G:
                 raise ValueError(f"bn_groups={G} must divide the batch ({x.shape[0]})")
@@ -1029,7 +1061,8 @@ class UNetEngine:
                     or class_weight.shape[0] != wh.shape[0] or class_weight.device != a.device):
                 raise ValueError(f"class_weight must be fp32 [{wh.shape[0]}] on {a.device}")
             cw = class_weight.detach().contiguous()
-        out = _HeadCEFn.apply(a, wh, bh, y.contiguous(), ignore_index, self, s, cw)
+        out = _HeadCEFn.apply(a, wh, bh, y.contiguous(), ignore_index, self, s, cw,
+                              float(dice_weight), float(dice_smooth))
         if G >= 1:
             self.bn_defer_apply(G)
         return out

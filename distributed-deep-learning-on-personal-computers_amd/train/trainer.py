@@ -367,7 +367,9 @@ class Trainer:
         ctx = (torch.autocast("cuda", dtype=torch.bfloat16) if self.autocast
                else contextlib.nullcontext())
         with ctx:
-            loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight)
+            loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight,
+                                                        dice_weight=self.cfg.dice_weight,
+                                                        dice_smooth=self.cfg.dice_smooth)
         if before_backward is not None:
             before_backward()
         (loss * float(groups) if groups > 1 else loss).backward()
@@ -576,8 +578,8 @@ class Trainer:
         saves y1, a1, y2 per block regardless), and a window whose activations fit in half
         of the memory available to the allocator (measured once per window length)."""
         c = self.cfg
-        if n_micro < 2 or self.impl != "hip" or c.bn_window in (0, 1):
-            return 0
+        if n_micro < 2 or self.impl != "hip" or c.bn_window in (0, 1) or c.dice_weight > 0:
+            return 0          # (the Dice sums are per micro-batch: no batched window)
         key = (n_micro, c.bn_window, c.batch_per_gpu, c.tile, c.recompute)
         cache = self.__dict__.setdefault("_window_cache", {})
         if key in cache:
@@ -787,6 +789,10 @@ class Trainer:
                         rec.update(self.phases.read())
                     if self.optimizer.scheduled:
                         rec.update(self.optimizer.last_stats())
+                    terms = self.model.dice_terms() if c.dice_weight > 0 else None
+                    if terms is not None:
+                        # the two terms of the last micro-batch (`loss` is the meter's mean)
+                        rec["dice"], rec["ce"] = terms
                     log_t, log_step = now, self.step_count
                     self.logger.log(rec)
                 if c.ckpt_dir and c.ckpt_every and self.step_count % c.ckpt_every == 0:
