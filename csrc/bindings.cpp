@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "data_checks.h"
+#include "head_checks.h"
 #include "head_math.h"
 #include "tail_checks.h"
 #include "ops.h"
@@ -1276,6 +1277,28 @@ at::Tensor head_logits(const at::Tensor& a, const at::Tensor& Wh, const at::Tens
   return out;
 }
 
+// Evaluation: loss sum / hits / counted pixels and the confusion matrix of one batch, ADDED into
+// the caller's sums (fp64 [3]) and cm (int64 [K, K]); the row scratch comes from the caching
+// allocator and is consumed by the finalize of the same call
+void head_eval(const at::Tensor& a, const at::Tensor& Wh, const at::Tensor& bh, const at::Tensor& labels,
+               int64_t ignore_index, at::Tensor& sums, at::Tensor& cm, const c10::optional<at::Tensor>& bn4) {
+  CHECK_DEV(a);
+  checks::head_eval(a, Wh, bh, labels, sums, cm, bn4);
+  c10::DeviceGuard guard(a.device());
+  const int C = (int)a.size(-1), K = (int)Wh.size(0);
+  const long long P = a.numel() / C;
+  const float* pbn = bn4_ptr(bn4, C);
+  const int nb = head_eval_blocks(C, P, num_cus());
+  at::Tensor lrows = at::empty({nb}, a.options().dtype(at::kFloat));
+  at::Tensor crows = at::empty({nb, 256}, a.options().dtype(at::kInt));
+  // (an ignore_index outside int32 can equal no counted label)
+  const int ign = ignore_index >= 0 && ignore_index < K ? (int)ignore_index : -1;
+  head_eval_launch(bptr(a), Wh.data_ptr<float>(), bh.data_ptr<float>(), labels.data_ptr<int64_t>(), pbn,
+                   lrows.data_ptr<float>(), reinterpret_cast<uint32_t*>(crows.data_ptr<int>()), nb, P, C, K, ign,
+                   sums.data_ptr<double>(), cm.data_ptr<int64_t>(), cur_stream());
+  set_last_path(std::string("head_eval:") + head_variant(C) + (pbn != nullptr ? ":defer" : ""));
+}
+
 // ------------------------------------------------------------------------ optimizer / pack
 // the flat buffers of one Adam step: fp32, contiguous (the kernel walks raw pointers), one device
 namespace {
@@ -1801,6 +1824,8 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("meter_add(Tensor(a!) buf, Tensor loss, Tensor correct, float pixels, float count=1.) -> ()");
   m.def("head_grad_scale(Tensor out3, Tensor? gs=None) -> Tensor");
   m.def("head_logits(Tensor a, Tensor Wh, Tensor bh, Tensor? bn4=None) -> Tensor");
+  m.def("head_eval(Tensor a, Tensor Wh, Tensor bh, Tensor labels, int ignore_index, Tensor(a!) sums, "
+        "Tensor(b!) cm, Tensor? bn4=None) -> ()");
   m.def("adam_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, float b1, float b2, float eps, "
         "float wd, float step_size, float inv_sqrt_bc2) -> ()");
   m.def("adam_step_dev(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) scal, "
@@ -1866,6 +1891,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("head_grad_scale", &ddlpc::head_grad_scale);
   m.impl("meter_add", &ddlpc::meter_add);
   m.impl("head_logits", &ddlpc::head_logits);
+  m.impl("head_eval", &ddlpc::head_eval);
   m.impl("adam_step", &ddlpc::adam_step);
   m.impl("adam_step_dev", &ddlpc::adam_step_dev);
   m.impl("adam_step_sched", &ddlpc::adam_step_sched);

@@ -26,6 +26,7 @@
 #include "bn_math.h"
 #include "data_checks.h"
 #include "data_math.h"
+#include "head_checks.h"
 #include "head_math.h"
 #include "optim_math.h"
 #include "tail_checks.h"
@@ -827,6 +828,43 @@ Tensor head_logits(const Tensor& a, const Tensor& Wh, const Tensor& bh, const op
   return to_cf(l.reshape(s)).contiguous();
 }
 
+// the twin of head_eval: the activation formed as act8 does (one fma, ReLU, rounded to bf16),
+// fp32 logits (bias first, channels in order), the first maximum, fp64 sums; a pixel counts iff
+// 0 <= label < K and label != ignore_index
+void head_eval(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& labels, int64_t ignore_index,
+               Tensor& sums, Tensor& cm, const optional<Tensor>& bn4) {
+  checks::head_eval(a, Wh, bh, labels, sums, cm, bn4);
+  ddlpc::set_last_path("cpu");
+  const int64_t K = Wh.size(0), C = a.size(-1), P = a.numel() / C;
+  const Tensor af = f32(a).reshape({P, C}).contiguous(), lab = labels.reshape({-1});
+  const float *y = af.data_ptr<float>(), *W = Wh.data_ptr<float>(), *b = bh.data_ptr<float>();
+  const float* s4 = has(bn4) ? bn4->data_ptr<float>() : nullptr;
+  const int64_t* L = lab.data_ptr<int64_t>();
+  double* s = sums.data_ptr<double>();
+  int64_t* m = cm.data_ptr<int64_t>();
+  std::vector<float> f(C), z(K);
+  for (int64_t p = 0; p < P; ++p) {
+    const int64_t t = L[p];
+    if (t < 0 || t >= K || t == ignore_index) continue;
+    for (int64_t c = 0; c < C; ++c) {
+      const float v = y[p * C + c];
+      f[c] = s4 == nullptr ? v : (float)c10::BFloat16(std::fmax(std::fmaf(v, s4[2 * C + c], s4[3 * C + c]), 0.f));
+    }
+    int64_t am = 0;
+    for (int64_t k = 0; k < K; ++k) {
+      z[k] = b[k];
+      for (int64_t c = 0; c < C; ++c) z[k] = std::fmaf(f[c], W[k * C + c], z[k]);
+      if (z[k] > z[am]) am = k;                      // first maximum
+    }
+    double se = 0;
+    for (int64_t k = 0; k < K; ++k) se += std::exp((double)z[k] - (double)z[am]);
+    s[0] += (double)z[am] + std::log(se) - (double)z[t];
+    s[1] += am == t ? 1.0 : 0.0;
+    s[2] += 1.0;
+    m[t * K + am] += 1;
+  }
+}
+
 // ------------------------------------------------------------------------ optimizer / pack
 void adam_math(Tensor p, const Tensor& g, Tensor m, Tensor v, double b1, double b2, double eps, double wd,
                float step_size, float inv_sqrt_bc2) {
@@ -1392,6 +1430,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("meter_add", &meter_add);
   m.impl("head_grad_scale", &head_grad_scale);
   m.impl("head_logits", &head_logits);
+  m.impl("head_eval", &head_eval);
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_dev", &adam_step_dev);
   m.impl("adam_step_sched", &adam_step_sched);

@@ -30,6 +30,12 @@
 // kernel has a DICE instantiation that reads the table from LDS and adds
 // p_j (g_j - sum_c p_c g_c) dL to the CE dlogits before dA, dWh, dbh and the BN partials are
 // formed.  Without a table the kernels launched are exactly the ones without the term.
+//
+// Evaluation (head_eval): the validation loss sum, the hits, the counted pixels and the
+// confusion matrix of a batch from one read of the activation and the labels, accumulated into
+// the caller's device buffers — integer counters per wave in LDS, one row per workgroup, a
+// one-workgroup finalize; no gradient work.  With it no path of the project writes logits to HBM
+// unless the caller asks for logits (head_logits).
 #include "common.h"
 #include "data_math.h"
 #include "head_math.h"
@@ -1314,6 +1320,217 @@ __global__ __launch_bounds__(256) void head_dice_coefs_kernel(
   if (tid == 0) dice_finalize(tot + kDiceRow, tot, K, lambda, eps, out3, tab);
 }
 
+// ===================================================================== the evaluation head
+// head_eval: validation in one pass over the activation and the labels.  A pixel is counted iff
+// 0 <= label < K and label != ignore_index; a counted pixel adds its (unweighted) cross-entropy
+// to the loss sum and bumps one integer counter [label][pred], pred = the first maximum.  The
+// counters live in LDS, one 16 x 16 uint32 table per wave (waves never contend; the only
+// atomic is the LDS integer add of one lane per counted pixel), summed over the waves into one
+// row per workgroup at the end of the persistent loop.  head_eval_finalize_kernel sums the rows
+// (counters in int64, loss in fp64) and ADDS them into the caller's accumulators, so a
+// validation loop is launches only.  Integer counters: cm, and the hits (its trace) and the
+// count (its sum) taken from it, do not depend on the grid or on the order the waves ran in,
+// and stay exact at any pixel count a call accepts (< 2^31: a row cannot overflow).
+// No gradient work, no LDS staging, no BN statistics: the launch bounds are these kernels' own.
+//
+// New code is built without packed fp32 arithmetic (the shared f32x2 helpers then lower to two
+// scalar FMAs: the same values).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DDLPC_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DDLPC_NO_PK_F32                 // (a device feature: the host pass has no such attribute)
+#endif
+constexpr int EVAL_TAB = MAXK * MAXK;   // one table: [label][pred], 16 x 16 counters
+// head32_eval_kernel: 7 waves per SIMD (<= 72 VGPRs).  The deferred instantiation compiles to 70
+// VGPRs without scratch (under a bound of 8 waves, 64 VGPRs, it spilled 7), the plain one to 60
+constexpr int EVAL32_PER_CU = 7;
+constexpr int EVAL_SPLIT_PER_CU = 8;    // head_eval_kernel: workgroups per CU that size the grid
+
+// both words of the int64 label
+DDLPC_DEVICE bool eval_counted(int lo, int hi, int K, int ignore_index) {
+  return hi == 0 && (unsigned)lo < (unsigned)K && lo != ignore_index;
+}
+// (am is 16 only where no logit equals the maximum — NaN logits: the last slot of the row, in bounds)
+DDLPC_DEVICE void eval_bump(uint32_t* tab, int lab, int am) {
+  __hip_atomic_fetch_add(tab + lab * MAXK + min(am, MAXK - 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+DDLPC_DEVICE void eval_clear(uint32_t (&sCM)[4][EVAL_TAB]) {
+  for (int i = threadIdx.x; i < 4 * EVAL_TAB; i += 256) (&sCM[0][0])[i] = 0u;
+}
+// the workgroup's row of counters and its loss sum (after the barrier that ends the step loop)
+DDLPC_DEVICE void eval_rows(const uint32_t (&sCM)[4][EVAL_TAB], const float (&sred)[4],
+                            float* __restrict__ lossp, uint32_t* __restrict__ cmpart) {
+  const int tid = threadIdx.x;
+  cmpart[(long long)blockIdx.x * EVAL_TAB + tid] = (sCM[0][tid] + sCM[1][tid]) + (sCM[2][tid] + sCM[3][tid]);
+  if (tid == 0) {
+    float t = 0.f;
+    for (int wv = 0; wv < 4; ++wv) t += sred[wv];
+    lossp[blockIdx.x] = t;
+  }
+}
+
+// C = 32: head32_kernel's MFMA layout (lane = pixel n, channel group g; two logit MFMAs; max and
+// sum over a pixel's 4 lanes by the permlane swaps) and its HEAD32_D-deep load pipeline on a
+// persistent grid.  Row g = 0 of the wave owns the pixel: it adds the loss term and bumps the
+// counter.  The step loop is wave-uniform (the MFMAs run with every lane on); only the bump sits
+// under a lane mask.
+template <bool DEFER>
+__global__ __launch_bounds__(256, EVAL32_PER_CU) DDLPC_NO_PK_F32 void head32_eval_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int64_t* __restrict__ labels, float* __restrict__ lossp, uint32_t* __restrict__ cmpart,
+    long long P, int ignore_index, const float* __restrict__ bn4, int Kreal) {
+  constexpr int C = 32;
+  __shared__ uint32_t sCM[4][EVAL_TAB];
+  __shared__ float sred[4];
+  __shared__ __attribute__((aligned(16))) float sK[2][C];   // scale | shift
+  __shared__ Head32W sW[64];                       // the lanes' constant MFMA operands
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, g = lane >> 4;
+  if (tid < 64) sW[tid] = head32_weights(Wh, bh, Kreal, lane);
+  if (DEFER && tid < C) {
+    sK[0][tid] = bn4[2 * C + tid];
+    sK[1][tid] = bn4[3 * C + tid];
+  }
+  eval_clear(sCM);
+  __syncthreads();
+  uint32_t* tab = sCM[wave];
+  float ls = 0.f;
+  const long long steps = (P + 15) / 16;
+  const long long wstride = (long long)gridDim.x * 4;
+  const long long s0 = (long long)blockIdx.x * 4 + wave;
+  auto load = [&](long long st, uint4& yv, int2& lb) __attribute__((always_inline)) {
+    const long long px = st * 16 + n;
+    const long long pc = px < P ? px : 0;
+    yv = *reinterpret_cast<const uint4*>(a + pc * C + 8 * g);
+    lb = *reinterpret_cast<const int2*>(labels + pc);
+  };
+  uint4 qy[HEAD32_D];
+  int2 ql[HEAD32_D];
+#pragma unroll
+  for (int j = 0; j < HEAD32_D; ++j) load(s0 + j * wstride < steps ? s0 + j * wstride : s0, qy[j], ql[j]);
+#pragma unroll 1
+  for (long long sb = s0; sb < steps; sb += HEAD32_D * wstride) {   // wave-uniform trip count
+#pragma unroll
+    for (int j = 0; j < HEAD32_D; ++j) {
+      // (branch-free, slot refilled after its last use: see head32_kernel)
+      const long long s = sb + j * wstride;
+      const uint4 yv = qy[j];
+      const int2 lab = ql[j];
+      const bool valid = s < steps && s * 16 + n < P;
+      float sc[8], sh[8];
+      if (DEFER) {
+        const float4* kp = reinterpret_cast<const float4*>(&sK[0][0] + opaque_zero() + 8 * g);
+        const float4 a0 = kp[0], a1 = kp[1], c0 = kp[8], c1 = kp[9];
+        sc[0] = a0.x; sc[1] = a0.y; sc[2] = a0.z; sc[3] = a0.w; sc[4] = a1.x; sc[5] = a1.y; sc[6] = a1.z; sc[7] = a1.w;
+        sh[0] = c0.x; sh[1] = c0.y; sh[2] = c0.z; sh[3] = c0.w; sh[4] = c1.x; sh[5] = c1.y; sh[6] = c1.z; sh[7] = c1.w;
+      } else {
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) { sc[jj] = 0.f; sh[jj] = 0.f; }
+      }
+      float y8[8], m, e[4], se, zy;
+      int am;
+      uint4 fb;
+      f32x4_t z;
+      head32_softmax<DEFER>(yv, valid, sW + opaque_zero() + lane, sc, sh, y8, fb, z, m, e, se);
+      head32_pick(z, m, lab.x, g, zy, am);
+      const bool own = g == 0 && valid && eval_counted(lab.x, lab.y, Kreal, ignore_index);
+      ls += own ? m + __logf(se) - zy : 0.f;
+      if (own) eval_bump(tab, lab.x, am);
+      const long long sl = s + HEAD32_D * wstride;
+      load(sl < steps ? sl : s0, qy[j], ql[j]);
+    }
+  }
+  ls = row16_sum(ls);
+  if (lane == 0) sred[wave] = ls;
+  __syncthreads();
+  eval_rows(sCM, sred, lossp, cmpart);
+}
+
+// C in {8, 16, 64}: one lane per pixel (head_ce_fwd_kernel's form: logits_of, padded class slots
+// with bias -inf and zero weights, the weights in LDS), the same tables and rows.
+template <int C, int K, bool DEFER>
+__global__ __launch_bounds__(256) DDLPC_NO_PK_F32 void head_eval_kernel(
+    const bf16_t* __restrict__ a, const float* __restrict__ Wh, const float* __restrict__ bh,
+    const int64_t* __restrict__ labels, float* __restrict__ lossp, uint32_t* __restrict__ cmpart,
+    long long P, int ignore_index, const float* __restrict__ bn4, int Kreal) {
+  __shared__ __attribute__((aligned(16))) float sBNm[2 * C];
+  __shared__ float sW[K * C], sb[K];
+  __shared__ uint32_t sCM[4][EVAL_TAB];
+  __shared__ float sred[4];
+  load_head<C, K>(Wh, bh, Kreal, sW, sb);
+  const float* sBN = DEFER ? load_bn<C>(bn4, sBNm, false) : nullptr;
+  eval_clear(sCM);
+  __syncthreads();
+  uint32_t* tab = sCM[threadIdx.x >> 6];
+  float loss = 0.f;
+#pragma unroll 1
+  for (long long px = blockIdx.x * 256LL + threadIdx.x; px < P; px += gridDim.x * 256LL) {
+    float z[K];
+    logits_of<C, K, DEFER>(a + px * C, sW, sb, sBN, z);
+    const int2 lab = *reinterpret_cast<const int2*>(labels + px);
+    float m = z[0];
+    int am = 0;
+#pragma unroll
+    for (int k = 1; k < K; ++k)
+      if (z[k] > m) { m = z[k]; am = k; }          // first maximum (padded classes: -inf)
+    float se = 0.f, zy = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      se += __expf(z[k] - m);
+      zy = (k == lab.x) ? z[k] : zy;
+    }
+    if (eval_counted(lab.x, lab.y, Kreal, ignore_index)) {
+      loss += m + __logf(se) - zy;
+      eval_bump(tab, lab.x, am);
+    }
+  }
+  loss = wave_sum(loss);
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = loss;
+  __syncthreads();
+  eval_rows(sCM, sred, lossp, cmpart);
+}
+
+// One workgroup of 1024: quarter qt of the threads sums rows qt, qt + 4, ... of counter column
+// col in int64, the loss rows are summed in fp64 (ce_finalize's way), and the totals are ADDED
+// into the caller's accumulators — a plain load-add-store by the one workgroup, ordered against
+// the previous call's by the stream.  sums = [loss sum, hits, counted pixels]; hits and count
+// are the trace and the sum of this call's counters.
+__global__ __launch_bounds__(1024) void head_eval_finalize_kernel(
+    const float* __restrict__ lossp, const uint32_t* __restrict__ cmpart, int nb, int K,
+    double* __restrict__ sums, long long* __restrict__ cm) {
+  __shared__ long long part[4][EVAL_TAB];
+  __shared__ double lred[16];
+  const int tid = threadIdx.x, col = tid % EVAL_TAB, qt = tid / EVAL_TAB;
+  long long s = 0;
+  for (int r = qt; r < nb; r += 4) s += cmpart[(long long)r * EVAL_TAB + col];
+  part[qt][col] = s;
+  double l = 0;
+  for (int r = tid; r < nb; r += 1024) l += lossp[r];
+  l = wave_sum_d(l);
+  if ((tid & 63) == 0) lred[tid >> 6] = l;
+  __syncthreads();
+  if (tid < EVAL_TAB) {
+    const long long t = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    const int k = tid / MAXK, j = tid % MAXK;
+    const bool in = k < K && j < K;
+    if (in) cm[k * K + j] += t;
+    part[0][tid] = in ? t : 0;                       // (own slot: no other thread reads it before the barrier)
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0;
+    for (int w = 0; w < 16; ++w) t += lred[w];
+    long long hits = 0, count = 0;
+    for (int i = 0; i < EVAL_TAB; ++i) {
+      count += part[0][i];
+      hits += i / MAXK == i % MAXK ? part[0][i] : 0;
+    }
+    sums[0] += t;
+    sums[1] += (double)hits;
+    sums[2] += (double)count;
+  }
+}
+
 template <int C, int K, bool DEFER>
 __global__ __launch_bounds__(256) void head_logits_kernel(const bf16_t* __restrict__ a, const float* __restrict__ Wh,
                                    const float* __restrict__ bh, float* __restrict__ out,
@@ -1689,6 +1906,36 @@ void head_dice_coefs_launch(const float* loss_partial, const float* dice_partial
                             float lambda, float eps, float* out3, float* table, hipStream_t st) {
   hipLaunchKernelGGL(head_dice_coefs_kernel, dim3(1), dim3(256), 0, st, loss_partial, dice_partial, nblocks, K,
                      lambda, eps, out3, table);
+}
+
+// the evaluation head's grid: a function of the width, the pixel count and num_cus.  C = 32: the
+// resident workgroups of the compiled kernels (the occupancy query; the smaller of the two
+// instantiations) on every CU, capped by the 64-pixel workgroup steps
+int head_eval_blocks(int C, long long P, int num_cus) {
+  if (C == 32) {
+    static const int per_cu = std::min(head32_per_cu(reinterpret_cast<const void*>(&head32_eval_kernel<true>)),
+                                       head32_per_cu(reinterpret_cast<const void*>(&head32_eval_kernel<false>)));
+    return head32_grid(P, per_cu, num_cus);
+  }
+  return (int)std::max<long long>(1, std::min<long long>((P + 255) / 256, (long long)EVAL_SPLIT_PER_CU * num_cus));
+}
+
+void head_eval_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
+                      const float* bn4, float* loss_partial, uint32_t* cm_partial, int nblocks, long long P,
+                      int C, int K, int ignore_index, double* sums, int64_t* cm, hipStream_t st) {
+  if (C == 32 && K <= MAXK) {
+    if (bn4 != nullptr)
+      hipLaunchKernelGGL((head32_eval_kernel<true>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, labels,
+                         loss_partial, cm_partial, P, ignore_index, bn4, K);
+    else
+      hipLaunchKernelGGL((head32_eval_kernel<false>), dim3(nblocks), dim3(256), 0, st, a, Wh, bh, labels,
+                         loss_partial, cm_partial, P, ignore_index, bn4, K);
+  } else {
+    HEAD_SWITCH_D(C, K, bn4, hipLaunchKernelGGL((head_eval_kernel<CC, KK, DD>), dim3(nblocks), dim3(256), 0, st, a,
+                                                Wh, bh, labels, loss_partial, cm_partial, P, ignore_index, bn4, K));
+  }
+  hipLaunchKernelGGL(head_eval_finalize_kernel, dim3(1), dim3(1024), 0, st, loss_partial, cm_partial, nblocks, K,
+                     sums, reinterpret_cast<long long*>(cm));
 }
 
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits,

@@ -336,6 +336,14 @@ void head_dice_fwd_launch(const bf16_t* a, const float* Wh, const float* bh, con
                           const float* cw = nullptr);
 void head_dice_coefs_launch(const float* loss_partial, const float* dice_partial, int nblocks, int K,
                             float lambda, float eps, float* out3, float* table, hipStream_t st);
+// Evaluation head: unweighted cross-entropy sum, hits, counted pixels and the confusion matrix
+// cm[label][pred] of one batch in one pass, ADDED into sums (fp64 [3]) and cm (int64 [K][K]).
+// A pixel counts iff 0 <= label < K and label != ignore_index.  Row scratch: loss_partial
+// [nblocks] fp32, cm_partial [nblocks][256] uint32; nblocks from head_eval_blocks; P < 2^31
+int head_eval_blocks(int C, long long P, int num_cus);
+void head_eval_launch(const bf16_t* a, const float* Wh, const float* bh, const int64_t* labels,
+                      const float* bn4, float* loss_partial, uint32_t* cm_partial, int nblocks, long long P,
+                      int C, int K, int ignore_index, double* sums, int64_t* cm, hipStream_t st);
 void head_logits_launch(const bf16_t* a, const float* Wh, const float* bh, float* logits_nchw,
                         long long P, long long HW, int C, int K, const float* bn4, hipStream_t st);
 // whole-scene prediction: head + softmax of B windows (pairwise disjoint) blended into the

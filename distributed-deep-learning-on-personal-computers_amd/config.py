@@ -200,6 +200,9 @@ class TrainConfig:
                                          # the window, train-mode BN normalises per micro-batch):
                                          # 0 = off, k >= 2 = up to k micro-batches per pass,
                                          # -1 = auto (small accumulated micro-batches, HIP engine)
+    fused_eval: bool = True              # HIP engine: validation through the fused evaluation head
+                                         # (model.evaluate: loss, hits and confusion matrix in one
+                                         # head pass, no logits in HBM); False = logits + stock ops
     recompute: int = 0                   # HIP engine activation recompute in backward (SURVEY 5.7,
                                          # batches beyond HBM): 1 = each block's first conv output,
                                          # 2 = both conv outputs of blocks that hand out a

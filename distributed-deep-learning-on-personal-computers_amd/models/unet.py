@@ -199,6 +199,33 @@ class UNet(nn.Module):
         correct = (logits.detach().argmax(1) == y).sum()
         return loss, correct
 
+    @torch.no_grad()
+    def evaluate(self, x, y, ignore_index: int = -100, out=None):
+        """Validation sums of one batch -> ``(sums, cm)``: ``sums`` float64 ``[3]`` = the SUM of the
+        unweighted per-pixel cross-entropies, the correctly classified pixels and the counted
+        pixels; ``cm`` int64 ``[K, K]`` indexed ``[label][pred]`` (pred = the first maximum).  A
+        pixel counts iff ``0 <= label < K`` and ``label != ignore_index``; every other pixel
+        contributes to nothing.  ``out = (sums, cm)`` accumulates into existing buffers, so a
+        validation loop divides once at the end.  The HIP path is one fused head pass
+        (``head_eval``: no logits in HBM); the stock path composes the same four quantities."""
+        k = self.cfg.out_classes
+        sums, cm = out if out is not None else (torch.zeros(3, dtype=torch.float64, device=x.device),
+                                                torch.zeros(k, k, dtype=torch.int64, device=x.device))
+        if self._engine is not None:
+            self._engine.evaluate(x, y, sums, cm, ignore_index)
+            return sums, cm
+        logits = self.forward_torch(x).float()
+        counted = (y >= 0) & (y < k) & (y != ignore_index)
+        yc = torch.where(counted, y, torch.zeros_like(y))
+        ce = F.cross_entropy(logits, yc, reduction="none").double()
+        pred = logits.argmax(1)
+        sums += torch.stack([(ce * counted).sum(), ((pred == y) & counted).sum().double(),
+                             counted.sum().double()])
+        # (uncounted pixels land in an extra bin that is dropped)
+        idx = torch.where(counted, yc * k + pred, torch.full_like(yc, k * k))
+        cm += torch.bincount(idx.reshape(-1), minlength=k * k + 1)[:k * k].reshape(k, k)
+        return sums, cm
+
     def dice_terms(self):
         """``(dice, ce)`` of the last ``loss_and_correct`` call with ``dice_weight > 0`` (``None``
         before one): on the HIP path read from the head's device table, on the stock path kept

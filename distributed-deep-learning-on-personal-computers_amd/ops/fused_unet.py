@@ -1029,6 +1029,18 @@ class UNetEngine:
         a, s = self.features(x, defer_last=True)
         return _ops().head_logits(a, wh.detach().contiguous(), bh.detach(), bn4=s)
 
+    @torch.no_grad()
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, sums: torch.Tensor, cm: torch.Tensor,
+                 ignore_index: int = -100) -> None:
+        """Validation in one head pass (``head_eval``; no logits in HBM): ADDS the batch's
+        unweighted cross-entropy sum, hits and counted pixels to ``sums`` (float64 ``[3]``) and its
+        confusion matrix ``[label][pred]`` to ``cm`` (int64 ``[K, K]``), both on x's device.  A
+        pixel counts iff ``0 <= label < K`` and ``label != ignore_index``.  The features are the
+        ones of the non-differentiable ``forward`` and follow the model's train / eval mode."""
+        a, s = self.features(x, defer_last=True)
+        wh, bh = self._head_params()
+        _ops().head_eval(a, wh.detach().contiguous(), bh.detach(), y.contiguous(), ignore_index, sums, cm, bn4=s)
+
     def loss_and_correct(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int = -100,
                          class_weight: Optional[torch.Tensor] = None, dice_weight: float = 0.0,
                          dice_smooth: float = 1.0):

@@ -855,9 +855,16 @@ class Trainer:
         bs = batch or self.cfg.batch_per_gpu
         acc = torch.zeros(3, dtype=torch.float64, device=self.device)
         cm = torch.zeros(k * k, dtype=torch.float64, device=self.device)
+        # the engine's fused evaluation head (cfg.fused_eval): one head pass per batch adds into
+        # acc and an int64 matrix on the device, no logits in HBM and no host work in the loop
+        fused = self.cfg.fused_eval and self.model._engine is not None
+        cmi = torch.zeros(k, k, dtype=torch.int64, device=self.device) if fused else None
         idx_all = list(range(len(ds)))[self.rank::self.world]
         for i in range(0, len(idx_all), bs):
             x, y = self._to_device(*ds.get(idx_all[i:i + bs]))
+            if fused:
+                self.model.evaluate(x, y, out=(acc, cmi))
+                continue
             ctx = (torch.autocast("cuda", dtype=torch.bfloat16) if self.autocast
                    else contextlib.nullcontext())
             with ctx:
@@ -869,6 +876,8 @@ class Trainer:
                                 torch.tensor(float(y.numel()), device=self.device,
                                              dtype=torch.float64)])
             cm += torch.bincount((y * k + pred).reshape(-1), minlength=k * k).double()
+        if fused:
+            cm = cmi.reshape(-1).double()
         if dist.is_available() and dist.is_initialized():
             dist.all_reduce(acc)
             dist.all_reduce(cm)
