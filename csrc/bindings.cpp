@@ -17,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "codec_checks.h"
 #include "data_checks.h"
 #include "head_checks.h"
 #include "head_math.h"
@@ -1438,6 +1439,31 @@ void codec_decode_sum(at::Tensor out, const at::Tensor& q, const at::Tensor& sca
                           out.numel(), cur_stream());
 }
 
+// top-k sparsification with error feedback (topk.hip): residual <- residual + g, the k largest
+// magnitudes leave as (idx ascending, val) and are zeroed in the residual.  The select state, the
+// bin tables and the per-chunk counts are one int32 scratch from the caching allocator on the
+// current stream (cleared by the first kernel); nothing is read back.
+std::vector<at::Tensor> topk_encode(const at::Tensor& g, at::Tensor residual, int64_t k) {
+  CHECK_DEV(g); CHECK_DEV(residual);
+  checks::topk_encode(g, residual, k);
+  c10::DeviceGuard guard(g.device());
+  const int64_t n = g.numel();
+  at::Tensor idx = at::empty({k}, g.options().dtype(at::kInt));
+  at::Tensor val = at::empty({k}, g.options());
+  at::Tensor scratch = at::empty({(int64_t)topk_plan(n).scratch_ints}, g.options().dtype(at::kInt));
+  topk_encode_launch(g.data_ptr<float>(), residual.data_ptr<float>(), n, (int)k, idx.data_ptr<int>(),
+                     val.data_ptr<float>(), scratch.data_ptr<int>(), cur_stream());
+  return {idx, val};
+}
+
+void topk_decode_sum(at::Tensor out, const at::Tensor& idx, const at::Tensor& val, const at::Tensor& w) {
+  CHECK_DEV(out);
+  checks::topk_decode_sum(out, idx, val, w);
+  c10::DeviceGuard guard(out.device());
+  topk_decode_sum_launch(out.data_ptr<float>(), out.numel(), idx.data_ptr<int>(), val.data_ptr<float>(),
+                         w.data_ptr<float>(), (int)idx.size(0), (int)idx.size(1), cur_stream());
+}
+
 // ------------------------------------------------------------------------ misc
 at::Tensor bilinear_up2(const at::Tensor& x) {
   CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x);
@@ -1838,6 +1864,8 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("codec_absmax(Tensor x, Tensor seg) -> Tensor");
   m.def("codec_encode(Tensor x, Tensor seg, Tensor scales, int codec) -> Tensor");
   m.def("codec_decode_sum(Tensor(a!) out, Tensor q, Tensor scales, Tensor w, Tensor seg, int codec) -> ()");
+  m.def("topk_encode(Tensor g, Tensor(a!) residual, int k) -> Tensor[]");
+  m.def("topk_decode_sum(Tensor(a!) out, Tensor idx, Tensor val, Tensor w) -> ()");
   m.def("bilinear_up2(Tensor x) -> Tensor");
   m.def("bilinear_up2_bwd(Tensor dy) -> Tensor");
   m.def("to_nhwc_bf16(Tensor x, int cpad=1) -> Tensor");
@@ -1899,6 +1927,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("codec_absmax", &ddlpc::codec_absmax);
   m.impl("codec_encode", &ddlpc::codec_encode);
   m.impl("codec_decode_sum", &ddlpc::codec_decode_sum);
+  m.impl("topk_encode", &ddlpc::topk_encode);
+  m.impl("topk_decode_sum", &ddlpc::topk_decode_sum);
   m.impl("bilinear_up2", &ddlpc::bilinear_up2);
   m.impl("bilinear_up2_bwd", &ddlpc::bilinear_up2_bwd);
   m.impl("to_nhwc_bf16", &ddlpc::to_nhwc_bf16);

@@ -17,13 +17,17 @@
 #include <ATen/Parallel.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "bn_math.h"
+#include "codec_checks.h"
 #include "data_checks.h"
 #include "data_math.h"
 #include "head_checks.h"
@@ -1041,6 +1045,54 @@ void codec_decode_sum(Tensor out, const Tensor& q, const Tensor& scales, const T
   }
 }
 
+// top-k with error feedback (the contract of parallel/codec.py): threshold by selection
+// (nth_element on the magnitude keys), then one walk in index order
+std::vector<Tensor> topk_encode(const Tensor& g, Tensor residual, int64_t k) {
+  checks::topk_encode(g, residual, k);
+  const int64_t n = g.numel();
+  residual.add_(g);                                               // a = e + g, one fp32 add
+  float* a = residual.data_ptr<float>();
+  auto key = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u & 0x7fffffffu; };
+  std::vector<uint32_t> keys(n);
+  for (int64_t i = 0; i < n; ++i) keys[i] = key(a[i]);
+  std::nth_element(keys.begin(), keys.begin() + (k - 1), keys.end(), std::greater<uint32_t>());
+  const uint32_t T = keys[k - 1];                                 // the k-th largest key
+  int64_t m = k;                                                  // equal keys to take
+  for (int64_t i = 0; i < n; ++i) m -= key(a[i]) > T;
+  Tensor idx = at::empty({k}, g.options().dtype(at::kInt)), val = at::empty({k}, g.options());
+  int* ip = idx.data_ptr<int>();
+  float* vp = val.data_ptr<float>();
+  int64_t slot = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t ki = key(a[i]);
+    if (ki > T || (ki == T && m > 0)) {
+      m -= ki == T;
+      ip[slot] = (int)i;
+      std::memcpy(vp + slot, a + i, 4);                           // bits preserved
+      ++slot;
+      a[i] = 0.f;
+    }
+  }
+  return {idx, val};
+}
+
+void topk_decode_sum(Tensor out, const Tensor& idx, const Tensor& val, const Tensor& w) {
+  checks::topk_decode_sum(out, idx, val, w);
+  const int64_t n = out.numel(), world = idx.size(0), k = idx.size(1);
+  float* o = out.data_ptr<float>();
+  std::fill(o, o + n, 0.f);
+  for (int64_t r = 0; r < world; ++r) {
+    const int* ip = idx.data_ptr<int>() + r * k;
+    const float* vp = val.data_ptr<float>() + r * k;
+    const float wr = w.data_ptr<float>()[r];
+    for (int64_t j = 0; j < k; ++j) {
+      TORCH_CHECK(ip[j] >= 0 && ip[j] < n, "topk_decode_sum: index out of range");
+      const volatile float prod = wr * vp[j];                     // two roundings, never an fma
+      o[ip[j]] = o[ip[j]] + prod;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------ misc
 Tensor bilinear_up2(const Tensor& x) {
   const Tensor xc = to_cf(f32(x)).contiguous();
@@ -1438,6 +1490,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("codec_absmax", &codec_absmax);
   m.impl("codec_encode", &codec_encode);
   m.impl("codec_decode_sum", &codec_decode_sum);
+  m.impl("topk_encode", &topk_encode);
+  m.impl("topk_decode_sum", &topk_decode_sum);
   m.impl("bilinear_up2", &bilinear_up2);
   m.impl("bilinear_up2_bwd", &bilinear_up2_bwd);
   m.impl("to_nhwc_bf16", &to_nhwc_bf16);

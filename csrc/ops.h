@@ -400,6 +400,28 @@ void codec_decode_sum_launch(float* out, const void* q, const float* scales, con
                              const int64_t* seg, int nseg, int world, int codec, long long n,
                              hipStream_t st);
 
+// top-k sparsification with error feedback (topk.hip): radix select on the 31-bit magnitude key,
+// ordered compaction, tile-owned scatter-sum.  Every workgroup owns a fixed chunk (kTopkChunk
+// elements of the segment, kTopkTile of the dense output), so grids and results depend on n alone.
+constexpr int kTopkChunk = 8192;               // elements per workgroup: select, count, compact
+constexpr int kTopkTile = 4096;                // floats of one scatter-sum tile (16 KB of LDS)
+constexpr int kTopkBins = 2048;                // widest digit (11 bits); passes take 11 / 10 / 10 bits
+constexpr int kTopkPasses = 3;
+struct TopkPlan {                              // torch-free planner, a function of n alone
+  int chunks;                                  // select / count / compact grid = ceil(n / kTopkChunk)
+  long long scratch_ints;                      // int32 scratch: state[4] | bins[passes][kTopkBins] | counts[chunks][2]
+};
+TopkPlan topk_plan(long long n);
+// tiles of the scatter-sum for an output whose first element lies `mis` floats (0..3) past a
+// 16-byte boundary: the tiles are anchored on that boundary
+int topk_tiles(long long n, int mis);
+// residual <- a = residual + g; idx[k] ascending, val[k] = a[idx]; residual[idx] <- +0.0
+void topk_encode_launch(const float* g, float* residual, long long n, int k, int* idx, float* val,
+                        int* scratch, hipStream_t st);
+// out[n] = sum over r in rank order of w[r] * val[r][.] scattered at idx[r][.] (ascending rows)
+void topk_decode_sum_launch(float* out, long long n, const int* idx, const float* val,
+                            const float* w, int world, int k, hipStream_t st);
+
 // ---------------------------------------------------------------- deterministic reductions
 int reduce_rows_chunks(int R);
 void reduce_rows_launch(const float* in, int R, long long N, double* tmp, double* sums,

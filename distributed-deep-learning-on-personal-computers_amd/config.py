@@ -21,7 +21,7 @@ from dataclasses import dataclass, field, fields
 import math
 from typing import Any, Dict, List, Optional, Sequence, Union
 
-GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax")
+GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax", "topk")
 CODEC_SCALES = ("global", "bucket", "tensor")
 REDUCE_OPS = ("mean", "sum", "reference")
 UP_MODES = ("conv_transpose", "bilinear")
@@ -154,8 +154,12 @@ class TrainConfig:
     bucket_plan: str = "readiness"       # readiness: cuts placed by the backward readiness
                                          # model (parallel/bucket_plan.py) | size: size only
     reduce: str = "mean"                 # mean | sum | reference (the W=2 "sum" parity mode)
-    grad_codec: str = "none"             # none | fp16_absmax | int8_absmax (ref.py:25)
+    grad_codec: str = "none"             # none | fp16_absmax | int8_absmax (ref.py:25) | topk
+                                         # (top-k sparsification with error feedback)
     codec_scale: str = "bucket"          # global (reference parity) | bucket | tensor
+    topk_ratio: float = 0.01             # topk: share of each bucket's entries sent per exchange,
+                                         # k = min(n, max(1, ceil(n * ratio))); the rest stays in
+                                         # a per-rank residual for the next exchange
     wire_dtype: str = "fp32"             # fp32 all-reduce | bf16 transport, fp32 accumulate
     overlap_comm: bool = True
     broadcast_buffers: bool = False      # BN running stats from rank 0 (reference: off)
@@ -227,6 +231,11 @@ class TrainConfig:
             # the stock-op path (impl="torch", or impl="auto" with dtype="fp32")
             raise ValueError("impl='hip' computes in bf16; use dtype='bf16', or impl='torch' / "
                              "'auto' for fp32 compute")
+        if not 0.0 < self.topk_ratio <= 1.0:
+            raise ValueError("topk_ratio must satisfy 0 < topk_ratio <= 1")
+        if self.grad_codec == "topk" and (self.codec_scale != "bucket" or self.wire_dtype != "fp32"):
+            raise ValueError("grad_codec='topk' selects per bucket and sends fp32 values: it needs "
+                             "codec_scale='bucket' and wire_dtype='fp32'")
         if self.accum_steps < 1 or self.batch_per_gpu < 1:
             raise ValueError("accum_steps and batch_per_gpu must be >= 1")
         if self.crops_per_epoch < 0:

@@ -46,3 +46,21 @@ def decode_sum_segments(out: torch.Tensor, payloads: Sequence[torch.Tensor],
     w = torch.tensor(list(weights), dtype=torch.float32, device=out.device)
     ext.codec_decode_sum(out, q, s, w, seg, CODEC_ID[codec])
     return out
+
+
+def topk_encode(g: torch.Tensor, residual: torch.Tensor, k: int
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k with error feedback on one bucket segment (``parallel.codec.topk_encode`` is the
+    contract): ``residual += g``; the ``k`` largest magnitudes leave as ``(idx int32 ascending,
+    val)`` and become +0.0 in the residual.  GPU: radix select + ordered compaction
+    (csrc/topk.hip), no host read."""
+    idx, val = _ext.ops().topk_encode(g, residual, k)
+    return idx, val
+
+
+def topk_decode_sum(out: torch.Tensor, idx: Sequence[torch.Tensor], val: Sequence[torch.Tensor],
+                    weights: Sequence[float]):
+    """out = sum_r weights[r] * val[r] scattered at idx[r], in rank order; the rest +0.0."""
+    w = torch.tensor(list(weights), dtype=torch.float32, device=out.device)
+    _ext.ops().topk_decode_sum(out, torch.stack(list(idx)), torch.stack(list(val)), w)
+    return out

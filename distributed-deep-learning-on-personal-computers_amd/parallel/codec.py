@@ -21,11 +21,17 @@ The reference's ``float32`` mode is broken (NameError) and is n
 ``grad_codec="none"`` is the lossless path.  An all-zero gradient (``max_grad == 0``), a
 NameError in the reference, encodes to zeros here.
 
+``grad_codec="topk"`` is not the reference's: top-k sparsification with error feedback (Deep
+Gradient Compression / memory SGD).  Each rank keeps a residual, sends the ``k`` largest
+magnitudes of ``residual + gradient`` per bucket as (index, value) pairs and keeps the rest for
+the next exchange (``topk_encode`` / ``topk_decode_sum`` below; HIP kernels in csrc/topk.hip).
+
 On GPU the encode is ONE fused HIP kernel pass (absmax reduce + quantize; ``ops.codec``)
 and the decode+sum another; this module is the torch oracle used on CPU and in tests.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -73,6 +79,39 @@ def decode_segments_accumulate(acc: torch.Tensor, q: torch.Tensor, scales: torch
                                weight: float = 1.0):
     for (a, b), s in zip(segments, scales):
         acc[a:b] += decode(q[a:b], s, codec) * weight
+
+
+def topk_count(n: int, ratio: float) -> int:
+    """Entries sent of an ``n``-element bucket at ``ratio``: ``min(n, max(1, ceil(n * ratio)))``."""
+    return min(n, max(1, math.ceil(n * ratio)))
+
+
+def topk_encode(g: torch.Tensor, residual: torch.Tensor, k: int
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k sparsification with error feedback (``grad_codec="topk"``), the contract of the
+    ``topk_encode`` operator.  ``a = residual + g`` (one fp32 add) replaces the residual;
+    ``key = bits(a) & 0x7fffffff`` as an unsigned integer (every NaN above +Inf above every
+    finite value, as for the absmax); ranked by key descending, then index ascending, the
+    first ``k`` are sent as ``idx`` (int32, ascending) and ``val = a[idx]`` (bits kept) and
+    become ``+0.0`` in the residual, which keeps everything that was not sent."""
+    residual.add_(g)
+    key = residual.view(torch.int32) & 0x7FFFFFFF              # non-negative: signed order = unsigned
+    order = torch.sort(key, descending=True, stable=True).indices[:k]
+    idx = torch.sort(order).values
+    val = residual[idx].clone()
+    residual[idx] = 0.0
+    return idx.to(torch.int32), val
+
+
+def topk_decode_sum(out: torch.Tensor, idx: Sequence[torch.Tensor], val: Sequence[torch.Tensor],
+                    weights: Sequence[float]) -> torch.Tensor:
+    """``out = sum over ranks r, in rank order, of weights[r] * val[r] scattered at idx[r]``:
+    every element starts at +0.0, each rank adds ``fl(w * val)`` (two roundings, no fma),
+    elements nobody sent stay +0.0."""
+    out.zero_()
+    for i, v, w in zip(idx, val, weights):
+        out[i.long()] += v * torch.tensor(w, dtype=torch.float32, device=v.device)
+    return out
 
 
 def reference_weights(world_size: int) -> List[float]:

@@ -24,6 +24,12 @@ MI355X design:
   reference's skewed weights; for W=2 that is a plain sum, SURVEY.md §2.6);
 * optional lossy codec (fp16/int8 absmax, ref.py:25) as an all-gather of packed payloads
   + scales, decoded and summed in rank order (``parallel.codec``; fused HIP kernels on GPU);
+* optional top-k sparsification with error feedback (``grad_codec="topk"``): a flat fp32
+  residual the size of the gradient buffer; per bucket ``topk_encode`` adds the gradient into
+  its residual slice and takes the k = ``topk_ratio`` * n largest magnitudes out of it as
+  (index, value) pairs — 8 bytes per sent entry on the wire — which are all-gathered and
+  scatter-summed in rank order at ``finish()`` (csrc/topk.hip); what was not sent stays in the
+  residual for the next exchange.  The residual is not checkpointed: a resume starts from zero;
 * optional bf16 wire format (``wire_dtype="bf16"``): half the bytes of the fp32
   all-reduce — an all-to-all of bf16 chunks (the reduce-scatter's transport) launched
   asynchronously from backward, then in ``finish()`` a rank-ordered fp32 sum of the owned
@@ -62,9 +68,15 @@ class GradBucketReducer:
     def __init__(self, flat: FlatParams, group=None, bucket_mb: float = 8.0,
                  reduce: str = "mean", grad_codec: str = "none", codec_scale: str = "bucket",
                  overlap: bool = True, use_hooks: bool = True, wire_dtype: str = "fp32",
-                 proxy: int = 0, cuts: Optional[List[int]] = None):
+                 proxy: int = 0, cuts: Optional[List[int]] = None, topk_ratio: float = 0.01):
         if wire_dtype not in ("fp32", "bf16"):
             raise ValueError(f"wire_dtype={wire_dtype!r}")
+        if grad_codec == "topk" and (codec_scale != "bucket" or wire_dtype != "fp32"):
+            raise ValueError("grad_codec='topk' needs codec_scale='bucket' and wire_dtype='fp32'")
+        if not 0.0 < topk_ratio <= 1.0:
+            raise ValueError(f"topk_ratio={topk_ratio!r} not in (0, 1]")
+        self.topk_ratio = topk_ratio
+        self.residual: Optional[torch.Tensor] = None    # topk error feedback, made on first use
         self.flat = flat
         self.wire_dtype = wire_dtype
         self.group = group
@@ -120,6 +132,9 @@ class GradBucketReducer:
             for p in flat.order:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad_ready))
         self.stats = {"buckets": len(self.buckets), "launched_in_backward": 0}
+        if grad_codec == "topk":                 # entries sent per exchange, over all buckets
+            self.stats["topk_k"] = sum(C.topk_count(b.end - b.start, topk_ratio)
+                                       for b in self.buckets)
         # readiness calibration (``start_calibration``): per-parameter gradient-complete times
         # of one synchronised step, relative to its backward start (Trainer.calibrate_bucket_plan)
         self._index = {id(p): i for i, p in enumerate(flat.order)}
@@ -258,9 +273,19 @@ class GradBucketReducer:
             b.work = dist.all_reduce(g, group=self.group, async_op=True)
             return
         # lossy codec: encode -> all_gather(payload, scales) -> decode+sum at finish()
-        segs = self._codec_segments(b)
         from ..ops import codec_ops
-        b.payload, b.scales = codec_ops.encode_segments(g, segs, self.codec)
+        if self.codec == "topk":
+            # (payload, scales) = (idx, val) of the k entries taken out of residual + gradient
+            if self.residual is None:
+                self.residual = torch.zeros_like(self.flat.grad_buf)
+            k = C.topk_count(g.numel(), self.topk_ratio)
+            b.payload, b.scales = codec_ops.topk_encode(g, self.residual[b.start:b.end], k)
+            if self.backend == "gloo" and g.is_cuda:
+                # gloo is a host transport: it gets host tensors (GPU tensors are for RCCL)
+                b.payload, b.scales = b.payload.cpu(), b.scales.cpu()
+        else:
+            segs = self._codec_segments(b)
+            b.payload, b.scales = codec_ops.encode_segments(g, segs, self.codec)
         b.gathered = ([torch.empty_like(b.payload) for _ in range(self.world)],
                       [torch.empty_like(b.scales) for _ in range(self.world)])
         w1 = dist.all_gather(b.gathered[0], b.payload, group=self.group, async_op=True)
@@ -381,11 +406,14 @@ class GradBucketReducer:
     def _decode_bucket(self, b: _Bucket):
         from ..ops import codec_ops
         g = self._seg(b)
-        segs = self._codec_segments(b)
         weights = (C.reference_weights(self.world) if self.reduce == "reference"
                    else [self.weight] * self.world)
-        codec_ops.decode_sum_segments(g, b.gathered[0], b.gathered[1], segs, self.codec,
-                                      weights)
+        if self.codec == "topk":
+            idx, val = ([t.to(g.device) for t in ts] for ts in b.gathered)
+            codec_ops.topk_decode_sum(g, idx, val, weights)
+        else:
+            codec_ops.decode_sum_segments(g, b.gathered[0], b.gathered[1],
+                                          self._codec_segments(b), self.codec, weights)
         b.gathered = b.payload = b.scales = None
 
     def _finish_global_codec(self):

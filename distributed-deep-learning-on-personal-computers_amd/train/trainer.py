@@ -181,6 +181,7 @@ class Trainer:
             cuts = self.bucket_plan.cuts
         return GradBucketReducer(self.flat, bucket_mb=bucket_mb, reduce=c.reduce,
                                  grad_codec=c.grad_codec, codec_scale=c.codec_scale,
+                                 topk_ratio=c.topk_ratio,
                                  overlap=c.overlap_comm, use_hooks=(self.impl != "hip"),
                                  wire_dtype=c.wire_dtype,
                                  proxy=c.comm_proxy if self.world == 1 else 0, cuts=cuts)

@@ -22,6 +22,9 @@ BUILD = os.path.join(ROOT, "build", "hip")
 LIB = os.path.join(OUT_DIR, "libddlpc_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
+# units compiled without the packed fp32 VALU forms (v_pk_add/mul/fma_f32): their results must be
+# bit-exact against a scalar oracle, one separately rounded operation per element
+NO_PACKED_FP32 = ("topk.hip",)
 
 
 def torch_paths():
@@ -65,6 +68,8 @@ def build(verbose=False, jobs=None, force=False):
                 flags = ["-x", "c++"] + [f for f in flags if not f.startswith("--offload-arch")]
             elif s.endswith(".cpp"):
                 flags = ["-x", "hip"] + flags
+            elif os.path.basename(s) in NO_PACKED_FP32:
+                flags += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
             todo.append((s, o, flags))
     jobs = jobs or min(len(todo) or 1, int(os.environ.get("MAX_JOBS", os.cpu_count() or 4)), 16)
     if todo:
