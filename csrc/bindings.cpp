@@ -21,6 +21,7 @@
 #include "data_checks.h"
 #include "head_checks.h"
 #include "head_math.h"
+#include "lamb_checks.h"
 #include "tail_checks.h"
 #include "ops.h"
 #include "optim_math.h"
@@ -1368,6 +1369,58 @@ void adam_step_sched(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor
                     scal.data_ptr<float>(), cur_stream());
 }
 
+// graph-capturable LAMB step (lamb.hip): the scalars of the scheduled Adam, a trust ratio per
+// tensor.  scal = device float[8] (the table of lamb_math.h, scal[0] = steps taken, advanced here).
+// The kernels address memory by the chunk table's values, so those are checked on the host: one
+// small blocking copy per table, remembered as pack_codes remembers its list (the tensors
+// themselves and their version counters).  A table's first call must therefore not be captured.
+namespace {
+struct LambTablesSeen {
+  at::Tensor chunks, tensors;
+  uint32_t vc = 0, vt = 0;
+  int64_t n = -1;
+};
+void check_lamb_tables(const at::Tensor& chunks, const at::Tensor& tensors, int64_t n) {
+  // (never freed: a device tensor must not be destroyed while the process exits)
+  thread_local LambTablesSeen* seen = new LambTablesSeen();
+  const bool versioned = !chunks.is_inference() && !tensors.is_inference();
+  if (versioned && seen->chunks.defined() && seen->chunks.is_same(chunks) && seen->tensors.is_same(tensors) &&
+      seen->vc == chunks._version() && seen->vt == tensors._version() && seen->n == n)
+    return;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+              "lamb_step: the first step with a chunk table checks its values on the host and "
+              "cannot be captured; run one step before the capture");
+  const at::Tensor ch = chunks.cpu(), tn = tensors.cpu();
+  checks::lamb_tables(ch.data_ptr<int64_t>(), ch.size(0), tn.data_ptr<int64_t>(), tn.size(0), n);
+  if (versioned) {
+    seen->chunks = chunks;
+    seen->tensors = tensors;
+    seen->vc = chunks._version();
+    seen->vt = tensors._version();
+    seen->n = n;
+  }
+}
+}  // namespace
+
+void lamb_step(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor scal,
+               const at::Tensor& chunks, const at::Tensor& tensors, at::Tensor partial, at::Tensor ratio,
+               at::Tensor norms, double lr, double b1, double b2, double eps, double wd, double max_norm,
+               int64_t sched_kind, int64_t warmup, int64_t total, double lr_min, double power) {
+  CHECK_DEV(p);
+  const int64_t C = checks::lamb_step(p, g, m, v, scal, chunks, tensors, partial, ratio, norms, sched_kind,
+                                      warmup, total);
+  c10::DeviceGuard guard(p.device());
+  check_lamb_tables(chunks, tensors, p.numel());
+  const SchedArgs a{lr, b1, b2, wd, max_norm, lr_min, power, warmup, total, (int)sched_kind, 0};
+  const LambHyper h{(float)b1, (float)b2, (float)eps, (float)wd};
+  lamb_step_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+                   scal.data_ptr<float>(), reinterpret_cast<const long long*>(chunks.data_ptr<int64_t>()), (int)C,
+                   reinterpret_cast<const long long*>(tensors.data_ptr<int64_t>()), (int)tensors.size(0),
+                   partial.data_ptr<double>(), ratio.data_ptr<float>(), norms.data_ptr<float>(), a, h,
+                   cur_stream());
+}
+
 void weight_pack(const at::Tensor& entries, int64_t n, int64_t max_elems) {
   CHECK_DEV(entries); CHECK_CONTIG(entries);
   TORCH_CHECK(entries.scalar_type() == at::kLong && n >= 0 && entries.numel() == n * 6,
@@ -1860,6 +1913,11 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("adam_step_sched(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) scal, "
         "Tensor(e!) partial, float lr, float b1, float b2, float eps, float wd, bool decoupled, "
         "float max_norm, int sched_kind, int warmup, int total, float lr_min, float power) -> ()");
+  // chunks int64 [C][3], tensors int64 [T][3] (csrc/lamb_math.h); partial double[3 C]
+  m.def("lamb_step(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor(d!) scal, Tensor chunks, "
+        "Tensor tensors, Tensor(e!) partial, Tensor(f!) ratio, Tensor(g!) norms, float lr, float b1, float b2, "
+        "float eps, float wd, float max_norm, int sched_kind, int warmup, int total, float lr_min, "
+        "float power) -> ()");
   m.def("weight_pack(Tensor entries, int n, int max_elems) -> ()");
   m.def("codec_absmax(Tensor x, Tensor seg) -> Tensor");
   m.def("codec_encode(Tensor x, Tensor seg, Tensor scales, int codec) -> Tensor");
@@ -1923,6 +1981,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("adam_step", &ddlpc::adam_step);
   m.impl("adam_step_dev", &ddlpc::adam_step_dev);
   m.impl("adam_step_sched", &ddlpc::adam_step_sched);
+  m.impl("lamb_step", &ddlpc::lamb_step);
   m.impl("weight_pack", &ddlpc::weight_pack);
   m.impl("codec_absmax", &ddlpc::codec_absmax);
   m.impl("codec_encode", &ddlpc::codec_encode);

@@ -32,6 +32,7 @@
 #include "data_math.h"
 #include "head_checks.h"
 #include "head_math.h"
+#include "lamb_checks.h"
 #include "optim_math.h"
 #include "tail_checks.h"
 
@@ -959,6 +960,100 @@ void adam_step_sched(Tensor p, const Tensor& g, Tensor m, Tensor v, Tensor scal,
   });
 }
 
+// the LAMB step of csrc/lamb.hip: the same chunk table walked in the same order, the element
+// functions, scalars and ratio rule of lamb_math.h, and the kernels' summation order (256 thread
+// sums per chunk / per tensor, then the halving tree), so the results are the kernels' bit for bit
+namespace {
+double tree256(double* red) {
+  for (int s = kLambThreads / 2; s > 0; s >>= 1)
+    for (int k = 0; k < s; ++k) red[k] += red[k + s];
+  return red[0];
+}
+
+// the elements of a chunk of `len` floats in the order thread k of the kernels visits them
+template <class F>
+void chunk_thread_elems(int64_t len, int k, F f) {
+  const int64_t q = len >> 2;
+  if (k < q)
+    for (int j = 0; j < 4; ++j) f(4 * k + j);
+  if (k < (len & 3)) f(4 * q + k);
+}
+}  // namespace
+
+void lamb_step(Tensor p, const Tensor& g, Tensor m, Tensor v, Tensor scal, const Tensor& chunks,
+               const Tensor& tensors, Tensor partial, Tensor ratio, Tensor norms, double lr, double b1, double b2,
+               double eps, double wd, double max_norm, int64_t sched_kind, int64_t warmup, int64_t total,
+               double lr_min, double power) {
+  const int64_t C = checks::lamb_step(p, g, m, v, scal, chunks, tensors, partial, ratio, norms, sched_kind,
+                                      warmup, total);
+  const int64_t Tn = tensors.size(0);
+  const int64_t* ch = chunks.data_ptr<int64_t>();
+  const int64_t* tn = tensors.data_ptr<int64_t>();
+  checks::lamb_tables(ch, C, tn, Tn, p.numel());
+  float* P = p.data_ptr<float>();
+  const float* G = g.data_ptr<float>();
+  float* M = m.data_ptr<float>();
+  float* V = v.data_ptr<float>();
+  float* s = scal.data_ptr<float>();
+  double* part = partial.data_ptr<double>();
+  double* gpart = part + 2 * C;
+  const SchedArgs a{lr, b1, b2, wd, max_norm, lr_min, power, warmup, total, (int)sched_kind, 0};
+  const LambHyper h{(float)b1, (float)b2, (float)eps, (float)wd};
+  // a workgroup's sums over one chunk: f(i, acc) adds element i's terms to the thread's sums
+  auto chunk_sums = [&](int64_t c, int nsum, double* out, auto f) {
+    double red[2][kLambThreads];
+    for (int k = 0; k < kLambThreads; ++k) {
+      double acc[2] = {0.0, 0.0};
+      chunk_thread_elems(ch[3 * c + 2], k, [&](int64_t e) { f(ch[3 * c + 1] + e, acc); });
+      red[0][k] = acc[0];
+      red[1][k] = acc[1];
+    }
+    for (int q = 0; q < nsum; ++q) out[q] = tree256(red[q]);
+  };
+  // a workgroup's strided sums of `count` values at src[stride j]
+  auto strided_sum = [&](const double* src, int64_t count, int64_t stride) {
+    double red[kLambThreads];
+    for (int k = 0; k < kLambThreads; ++k) {
+      red[k] = 0.0;
+      for (int64_t j = k; j < count; j += kLambThreads) red[k] += src[stride * j];
+    }
+    return tree256(red);
+  };
+  const bool clip = max_norm > 0.0 && C > 0;
+  if (clip)
+    at::parallel_for(0, C, 16, [&](int64_t lo, int64_t hi) {
+      for (int64_t c = lo; c < hi; ++c)
+        chunk_sums(c, 1, gpart + c, [&](int64_t i, double* acc) { acc[0] += (double)G[i] * (double)G[i]; });
+    });
+  lamb_scalars(s, a, clip ? strided_sum(gpart, C, 1) : 0.0);
+  if (C == 0) return;
+  const float ibc1 = s[1], isb2 = s[2], coef = s[5];
+  auto wd_of = [&](int64_t c) { return tn[3 * ch[3 * c] + 2] != 0 ? h.wd : 0.f; };
+  at::parallel_for(0, C, 16, [&](int64_t lo, int64_t hi) {
+    for (int64_t c = lo; c < hi; ++c) {
+      const float wdt = wd_of(c);
+      chunk_sums(c, 2, part + 2 * c, [&](int64_t i, double* acc) {
+        lamb_moments(G[i], coef, h, M[i], V[i]);
+        const float u = lamb_u(P[i], M[i], V[i], ibc1, isb2, h.eps, wdt);
+        acc[0] += (double)P[i] * (double)P[i];
+        acc[1] += (double)u * (double)u;
+      });
+    }
+  });
+  float* R = ratio.data_ptr<float>();
+  float* N = norms.data_ptr<float>();
+  for (int64_t t = 0; t < Tn; ++t)
+    lamb_ratio(strided_sum(part + 2 * tn[3 * t], tn[3 * t + 1], 2), strided_sum(part + 2 * tn[3 * t] + 1, tn[3 * t + 1], 2),
+               tn[3 * t + 2] != 0, R + t, N + 2 * t);
+  at::parallel_for(0, C, 16, [&](int64_t lo, int64_t hi) {
+    for (int64_t c = lo; c < hi; ++c) {
+      const float wdt = wd_of(c), step = mul_rn(s[3], R[ch[3 * c]]);
+      for (int64_t i = ch[3 * c + 1]; i < ch[3 * c + 1] + ch[3 * c + 2]; ++i)
+        P[i] = lamb_apply(P[i], lamb_u(P[i], M[i], V[i], ibc1, isb2, h.eps, wdt), step);
+    }
+  });
+}
+
 // fp32 OIHW / IOHW parameters -> bf16 kernel layouts (see csrc/misc.hip weight_pack_kernel):
 // entries [n][6] = (src*, fwd*, dgrad* | 0, kind | Cout << 32, Cin | taps << 32, CinW | CoutW << 32)
 void weight_pack(const Tensor& entries, int64_t n, int64_t max_elems) {
@@ -1486,6 +1581,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("adam_step", &adam_step);
   m.impl("adam_step_dev", &adam_step_dev);
   m.impl("adam_step_sched", &adam_step_sched);
+  m.impl("lamb_step", &lamb_step);
   m.impl("weight_pack", &weight_pack);
   m.impl("codec_absmax", &codec_absmax);
   m.impl("codec_encode", &codec_encode);

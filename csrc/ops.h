@@ -381,6 +381,13 @@ void sched_scalars_launch(float* scal, const double* partial, int nb, const Sche
 void adam_sched_launch(float* p, const float* g, float* m, float* v, long long n, float b1,
                        float b2, float eps, float wd, bool decoupled, const float* scal,
                        hipStream_t st);
+// the LAMB step (lamb.hip): per-tensor trust ratios over the chunk table of lamb_math.h.
+// chunks int64 [nchunks][3], tensors int64 [ntensors][3], partial double[3 nchunks] ({sum p^2,
+// sum u^2} per chunk, then the chunks' sums of g^2), ratio float[ntensors], norms float[2 ntensors]
+struct LambHyper;                  // lamb_math.h
+void lamb_step_launch(float* p, const float* g, float* m, float* v, float* scal, const long long* chunks,
+                      int nchunks, const long long* tensors, int ntensors, double* partial, float* ratio,
+                      float* norms, const SchedArgs& a, const LambHyper& h, hipStream_t st);
 struct PackEntry {                 // one conv weight to pack into bf16 kernel layouts
   const float* src;                // OIHW fp32  (or IOHW for transposed conv)
   bf16_t* fwd;                     // conv: [co][tap][CinW]; convT: [(sub, co)][Cin]

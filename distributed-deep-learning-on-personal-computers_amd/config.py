@@ -29,6 +29,7 @@ DATA_KINDS = ("synthetic", "vaihingen_dir", "scene_dir")
 AUGMENT_MODES = ("none", "flip", "d4")
 CLASS_WEIGHT_MODES = ("median_freq",)
 LR_SCHEDULES = ("constant", "poly", "cosine")
+OPTIMIZERS = ("adam", "lamb")
 
 
 def parse_class_weights(spec: Union[None, str, Sequence[float]], classes: int):
@@ -145,6 +146,11 @@ class TrainConfig:
     lr_poly_power: float = 0.9           # poly: (1 - u)^power
     max_grad_norm: float = 0.0           # > 0: clip the global gradient norm (clip_grad_norm_)
     decoupled_weight_decay: bool = False  # True = AdamW (p *= 1 - lr_t wd), False = L2 into g
+    optimizer: str = "adam"              # adam | lamb (ops/lamb.py, csrc/lamb.hip: a trust ratio
+                                         # ||p|| / ||u|| per tensor, the decay inside u; schedule,
+                                         # warm-up and max_grad_norm apply to both)
+    lamb_exclude_1d: bool = True         # lamb: biases and BatchNorm weights get neither decay nor
+                                         # a trust ratio; False = every tensor is adapted and decayed
     dtype: str = "bf16"                  # compute dtype on GPU (fp32 master weights); "fp32"
                                          # (the reference's precision) = stock ops, no autocast
     seed: int = 0
@@ -249,6 +255,11 @@ class TrainConfig:
             raise ValueError("lr_min must not exceed lr")
         if not self.lr_poly_power > 0:
             raise ValueError("lr_poly_power must be > 0")
+        if self.optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer={self.optimizer!r} not in {OPTIMIZERS}")
+        if self.optimizer == "lamb" and self.decoupled_weight_decay:
+            raise ValueError("optimizer='lamb' keeps its weight decay inside the update u; "
+                             "decoupled_weight_decay applies to adam only")
         for name in ("gain_jitter", "bias_jitter"):
             if not 0.0 <= getattr(self, name) <= 1.0:
                 raise ValueError(f"{name} must be in [0, 1]")

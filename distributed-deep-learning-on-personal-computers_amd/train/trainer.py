@@ -35,6 +35,7 @@ from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset
 from ..models.unet import UNet
 from ..ops import _ext
 from ..ops.adam import FlatAdam
+from ..ops.lamb import FlatLamb
 from ..parallel import (GradBucketReducer, assert_replicas_identical, broadcast_buffers,
                         broadcast_module, broadcast_tensors, flatten_module, init_distributed)
 from ..utils.metrics import DeviceMeter, RunLogger, dump_pngs
@@ -78,9 +79,15 @@ class Trainer:
             _ext.ops()                               # fail loudly if kernels are missing
             model.to_hip()
             model._engine.recompute = int(cfg.recompute)
-        self.optimizer = FlatAdam(self.flat, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps,
-                                  weight_decay=cfg.weight_decay,
-                                  use_hip=(self.impl == "hip"), **self._schedule_args())
+        if cfg.optimizer == "lamb":
+            sched = {k: v for k, v in self._schedule_args().items() if k != "decoupled"}
+            self.optimizer = FlatLamb(self.flat, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps,
+                                      weight_decay=cfg.weight_decay, use_hip=(self.impl == "hip"),
+                                      exclude_1d=cfg.lamb_exclude_1d, **sched)
+        else:
+            self.optimizer = FlatAdam(self.flat, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps,
+                                      weight_decay=cfg.weight_decay,
+                                      use_hip=(self.impl == "hip"), **self._schedule_args())
         if self.impl == "hip":
             self.optimizer.weight_pack = model._engine.pack_weights
         # optional CU reservation for collectives (persistent grids sized to num_cus - k).

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Time the optimizer step on the default model's flat buffer (about 8.7 M fp32 parameters):
 ``adam_step_dev`` against ``adam_step_sched`` with clipping off and on (coupled and decoupled
-decay), interleaved in one process.  Each variant is timed with device events over ``--inner``
+decay) and against ``lamb_step`` (clipping off and on, on the model's flat layout of 64-float
+aligned tensors), interleaved in one process.  Each variant is timed with device events over ``--inner``
 back-to-back calls, ``--repeats`` times round-robin after a warm-up; the median per call is
 reported with the bytes each variant must move (7 streams of n floats for Adam, one more read of
-g for the norm) and the HBM rate that implies.  Prints one JSON line (docs/PERF.md records it).
+g for the norm; 10 for LAMB: 6 in the moments pass, 4 in the apply pass) and the HBM rate that implies.  Prints one JSON line (docs/PERF.md records it).
 """
 import argparse
 import json
@@ -28,12 +29,23 @@ def main():
     from ddlpc.ops import _ext
     from ddlpc.ops.adam import grad_sqnorm_blocks
     o = _ext.ops()
-    n = a.n or sum(p.numel() for p in UNet(out_classes=6).parameters())
+    from ddlpc.ops.lamb import lamb_tables
+    shapes = [(a.n,)] if a.n else [tuple(p.shape) for p in reversed(list(UNet(out_classes=6).parameters()))]
+    n = sum(torch.Size(s).numel() for s in shapes)
+    spans, nflat = [], 0                  # FlatParams' layout: 64-float aligned tensors
+    for s in shapes:
+        spans.append((nflat, nflat + torch.Size(s).numel()))
+        nflat += (torch.Size(s).numel() + 63) // 64 * 64
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    p = torch.randn(n, generator=g).to(dev)
-    grad = (torch.randn(n, generator=g) * 1e-2).to(dev)
-    m, v = torch.zeros_like(p), torch.zeros_like(p)
+    pf = torch.randn(nflat, generator=g).to(dev)
+    gf = (torch.randn(nflat, generator=g) * 1e-2).to(dev)
+    mf, vf = torch.zeros_like(pf), torch.zeros_like(pf)
+    p, grad, m, v = pf[:n], gf[:n], mf[:n], vf[:n]          # the Adam variants: n elements, as before
+    chunks, tensors = (t.to(dev) for t in lamb_tables(spans, [len(s) > 1 for s in shapes]))
+    lpartial = torch.zeros(3 * chunks.shape[0], dtype=torch.float64, device=dev)
+    lscal, ratio = torch.zeros(8, device=dev), torch.zeros(tensors.shape[0], device=dev)
+    norms = torch.zeros(tensors.shape[0], 2, device=dev)
     scal3, scal8 = torch.zeros(3, device=dev), torch.zeros(8, device=dev)
     partial = torch.zeros(grad_sqnorm_blocks(n), dtype=torch.float64, device=dev)
     hp = (1e-3, 0.9, 0.999, 1e-8)
@@ -41,11 +53,16 @@ def main():
     def sched(wd, decoupled, max_norm):
         return lambda: o.adam_step_sched(p, grad, m, v, scal8, partial, *hp, wd, decoupled, max_norm, 2, 100,
                                          100000, 1e-5, 0.9)
+    def lamb(max_norm):
+        return lambda: o.lamb_step(pf, gf, mf, vf, lscal, chunks, tensors, lpartial, ratio, norms, *hp, 0.01,
+                                   max_norm, 2, 100, 100000, 1e-5, 0.9)
     variants = {
         "adam_step_dev": (lambda: o.adam_step_dev(p, grad, m, v, scal3, *hp, 0.0), 7),
         "adam_step_sched": (sched(0.0, False, 0.0), 7),
         "adam_step_sched clip": (sched(0.0, False, 1.0), 8),
         "adam_step_sched clip adamw": (sched(0.01, True, 1.0), 8),
+        "lamb_step": (lamb(0.0), 10),
+        "lamb_step clip": (lamb(1.0), 11),
     }
     times = {k: [] for k in variants}
     for r in range(a.warmup + a.repeats):

@@ -14,6 +14,8 @@
 // coordinates at the extremes its validity predicate admits (no signed overflow: UBSan)
 // and of csrc/bn_math.h, the BatchNorm / gradient-tail recipe: the slab permutation is a
 // bijection, stats4 at its edge inputs, the three summation orders at the regime borders
+// and of csrc/lamb_math.h, the LAMB step's recipe: the scalar table over schedules and steps, the
+// trust-ratio rule at zero, infinite and NaN norms, the element functions where u must be 0
 // over the geometry range the U-Net uses (2-D 8^2..1024^2, 3-D 8^3..128^3, batch 1..256), the
 // U-Net's channel pairs in both directions, BN groups 1 / 2 / 4, with and without the
 // prologues and the BN-backward epilogue, at 8, 248 and 256 CUs, asserting the invariants the
@@ -40,6 +42,7 @@
 
 #include "../csrc/bn_math.h"
 #include "../csrc/data_math.h"
+#include "../csrc/lamb_math.h"
 #include "../csrc/ops.h"
 
 using namespace ddlpc;
@@ -700,6 +703,45 @@ static void print_row(const Case& c, int cus) {
   }
 }
 
+// ------------------------------------------------------------------ lamb_math.h
+static void sweep_lamb_math() {
+  for (int kind : {SCHED_CONSTANT, SCHED_POLY, SCHED_COSINE})
+    for (double max_norm : {0.0, 0.5})
+      for (float taken : {0.f, 1.f, 4.f, 9.f, 10.f, 1e6f}) {
+        const SchedArgs a{1e-3, 0.9, 0.999, 0.01, max_norm, 1e-5, 0.9, 5, 10, kind, 0};
+        for (double sq : {0.0, 1e-30, 4.0, 1e60}) {
+          float s[8] = {taken, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
+          lamb_scalars(s, a, sq);
+          EXPECT(s[0] == taken + 1.f || taken == 1e6f, "t advances");
+          EXPECT(s[1] >= 1.f && s[2] >= 1.f && s[1] < HUGE_VALF && s[2] < HUGE_VALF, "bias corrections %g %g", s[1], s[2]);
+          EXPECT(s[3] == (float)sched_lr(a, (double)taken + 1.0) && s[3] > 0.f && s[3] <= 1e-3f, "lr_t %g", s[3]);
+          EXPECT(max_norm > 0.0 ? s[4] == (float)std::sqrt(sq) && s[5] > 0.f && s[5] <= 1.f : s[4] == 0.f && s[5] == 1.f,
+                 "norm %g coef %g", s[4], s[5]);
+          EXPECT((s[5] < 1.f) == (max_norm > 0.0 && sq >= 4.0) && s[6] == 0.f && s[7] == 0.f, "clipped only above max_norm");
+        }
+      }
+  const double inf = HUGE_VAL, nan = std::nan("");
+  float r, n[2];
+  lamb_ratio(16.0, 4.0, true, &r, n);
+  EXPECT(r == 2.f && n[0] == 4.f && n[1] == 2.f, "ratio %g", r);
+  for (auto& c : {std::pair<double, double>{0.0, 4.0}, {4.0, 0.0}, {0.0, 0.0}, {inf, 4.0}, {4.0, inf}, {nan, 4.0}, {4.0, nan}}) {
+    lamb_ratio(c.first, c.second, true, &r, n);
+    EXPECT(r == 1.f, "ratio 1 at norms^2 (%g, %g), got %g", c.first, c.second, r);
+  }
+  lamb_ratio(16.0, 4.0, false, &r, n);
+  EXPECT(r == 1.f && n[0] == 4.f && n[1] == 2.f, "an excluded tensor: ratio 1, norms kept");
+  // zero gradient on zero moments without decay: u = 0 and p keeps its bits, whatever the step
+  const LambHyper h{0.9f, 0.999f, 1e-8f, 0.01f};
+  for (float p : {0.f, -0.f, 1.5f, -3e-39f, 3e38f}) {
+    float m = 0.f, v = 0.f;
+    lamb_moments(0.f, 0.25f, h, m, v);
+    const float u = lamb_u(p, m, v, 10.f, 31.6f, h.eps, 0.f);
+    EXPECT(m == 0.f && v == 0.f && u == 0.f, "u = 0");
+    EXPECT(std::memcmp(&p, &(const float&)lamb_apply(p, u, 3e38f), 4) == 0 || p == 0.f, "p unchanged");
+    EXPECT(lamb_u(p, m, v, 10.f, 31.6f, h.eps, h.wd) == h.wd * p, "u = wd p");
+  }
+}
+
 static void print_table() {
   std::printf("# op | shape | num_cus | path | grid | splits/ksplit | tile   (tools/host_sanitize.cpp --table)\n");
   for (int cus : {256, 8})
@@ -721,6 +763,7 @@ int main(int argc, char** argv) {
   sweep_reductions();
   sweep_data_math();
   sweep_bn_math();
+  sweep_lamb_math();
   std::printf("host_sanitize: %lld planner checks passed (ASan + UBSan)\n", g_checks);
   return 0;
 }
