@@ -1517,6 +1517,101 @@ void topk_decode_sum(at::Tensor out, const at::Tensor& idx, const at::Tensor& va
                          w.data_ptr<float>(), (int)idx.size(0), (int)idx.size(1), cur_stream());
 }
 
+// low-rank codec (powersgd.hip).  The kernels address memory by the tables' values, so those are
+// checked on the host: one small blocking copy per (tables, buffer sizes, rank), remembered with
+// the tensors themselves and their version counters as lamb_step remembers its table.  The list is
+// one per process behind a mutex — a reducer projects on the autograd thread and finishes on the
+// main one, and both must find what the other has checked — and holds a reference to every table
+// it has seen (at most 256, then it starts over; a reducer has three entries per bucket), so a
+// table's memory cannot be handed to another tensor while its entry stands.  A table's first call
+// must therefore not be captured; after it nothing is read back.
+namespace {
+struct PsgdSeen {
+  at::Tensor low, raw;
+  uint32_t vl = 0, vr = 0;
+  int64_t ng, np, nq, rank;
+  PsgdCounts counts;
+};
+PsgdCounts psgd_counts(const char* op, const at::Tensor& low, const at::Tensor* raw, checks::PsgdSizes s,
+                       int64_t rank) {
+  // (never freed: a device tensor must not be destroyed while the process exits)
+  static std::vector<PsgdSeen>* seen = new std::vector<PsgdSeen>();
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  const bool versioned = !low.is_inference() && !(raw && raw->is_inference());
+  if (versioned)
+    for (const PsgdSeen& e : *seen)
+      if (e.low.is_same(low) && e.vl == low._version() && e.raw.defined() == (raw != nullptr) &&
+          (!raw || (e.raw.is_same(*raw) && e.vr == raw->_version())) && e.ng == s.ng && e.np == s.np &&
+          e.nq == s.nq && e.rank == rank)
+        return e.counts;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess && cap == hipStreamCaptureStatusNone, op,
+              ": the first call with a table checks its values on the host and cannot be captured; "
+              "run one exchange before the capture");
+  const at::Tensor lh = low.cpu(), rh = raw ? raw->cpu() : at::Tensor();
+  const PsgdCounts c = checks::psgd_tables(op, lh.data_ptr<int>(), lh.size(0), raw ? rh.data_ptr<int>() : nullptr,
+                                           raw ? rh.size(0) : 0, s.ng, s.np, s.nq, rank);
+  if (versioned) {
+    if (seen->size() >= 256) seen->clear();
+    seen->push_back(PsgdSeen{low, raw ? *raw : at::Tensor(), (uint32_t)low._version(), raw ? (uint32_t)raw->_version() : 0u, s.ng, s.np,
+                             s.nq, rank, c});
+  }
+  return c;
+}
+}  // namespace
+
+void psgd_project(const at::Tensor& g, at::Tensor e, const at::Tensor& q, at::Tensor wire_p, const at::Tensor& low,
+                  const at::Tensor& raw, int64_t rank, double w) {
+  CHECK_DEV(g);
+  const checks::PsgdSizes s = checks::psgd_project(g, e, q, wire_p, low, raw, rank);
+  c10::DeviceGuard guard(g.device());
+  const PsgdCounts c = psgd_counts("psgd_project", low, &raw, s, rank);
+  psgd_project_launch(g.data_ptr<float>(), e.data_ptr<float>(), q.data_ptr<float>(), wire_p.data_ptr<float>(),
+                      low.data_ptr<int>(), (int)low.size(0), raw.data_ptr<int>(), (int)raw.size(0), (int)rank,
+                      (float)w, c, cur_stream());
+}
+
+void psgd_orthonormalize(at::Tensor wire_p, const at::Tensor& low, int64_t rank) {
+  CHECK_DEV(wire_p);
+  const checks::PsgdSizes s = checks::psgd_orthonormalize(wire_p, low, rank);
+  c10::DeviceGuard guard(wire_p.device());
+  psgd_counts("psgd_orthonormalize", low, nullptr, s, rank);
+  psgd_orthonormalize_launch(wire_p.data_ptr<float>(), low.data_ptr<int>(), (int)low.size(0), (int)rank,
+                             cur_stream());
+}
+
+void psgd_backproject(const at::Tensor& e, const at::Tensor& wire_p, at::Tensor q_loc, at::Tensor wire_q,
+                      const at::Tensor& low, int64_t rank, double w) {
+  CHECK_DEV(e);
+  const checks::PsgdSizes s = checks::psgd_backproject(e, wire_p, q_loc, wire_q, low, rank);
+  c10::DeviceGuard guard(e.device());
+  const PsgdCounts c = psgd_counts("psgd_backproject", low, nullptr, s, rank);
+  psgd_backproject_launch(e.data_ptr<float>(), wire_p.data_ptr<float>(), q_loc.data_ptr<float>(),
+                          wire_q.data_ptr<float>(), low.data_ptr<int>(), (int)low.size(0), (int)rank, (float)w, c,
+                          cur_stream());
+}
+
+void psgd_residual(at::Tensor e, const at::Tensor& wire_p, const at::Tensor& q_loc, const at::Tensor& low,
+                   int64_t rank) {
+  CHECK_DEV(e);
+  const checks::PsgdSizes s = checks::psgd_residual(e, wire_p, q_loc, low, rank);
+  c10::DeviceGuard guard(e.device());
+  const PsgdCounts c = psgd_counts("psgd_residual", low, nullptr, s, rank);
+  psgd_residual_launch(e.data_ptr<float>(), wire_p.data_ptr<float>(), q_loc.data_ptr<float>(), low.data_ptr<int>(),
+                       (int)low.size(0), (int)rank, c, cur_stream());
+}
+
+void psgd_decode(at::Tensor g, const at::Tensor& wire_p, const at::Tensor& wire_q, const at::Tensor& low,
+                 const at::Tensor& raw, int64_t rank) {
+  CHECK_DEV(g);
+  const checks::PsgdSizes s = checks::psgd_decode(g, wire_p, wire_q, low, raw, rank);
+  c10::DeviceGuard guard(g.device());
+  const PsgdCounts c = psgd_counts("psgd_decode", low, &raw, s, rank);
+  psgd_decode_launch(g.data_ptr<float>(), wire_p.data_ptr<float>(), wire_q.data_ptr<float>(), low.data_ptr<int>(),
+                     (int)low.size(0), raw.data_ptr<int>(), (int)raw.size(0), (int)rank, c, cur_stream());
+}
+
 // ------------------------------------------------------------------------ misc
 at::Tensor bilinear_up2(const at::Tensor& x) {
   CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x);
@@ -1924,6 +2019,15 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("codec_decode_sum(Tensor(a!) out, Tensor q, Tensor scales, Tensor w, Tensor seg, int codec) -> ()");
   m.def("topk_encode(Tensor g, Tensor(a!) residual, int k) -> Tensor[]");
   m.def("topk_decode_sum(Tensor(a!) out, Tensor idx, Tensor val, Tensor w) -> ()");
+  // low int32 [T][5] = (offset, n, m, p_off, q_off), raw int32 [R][3] = (offset, length, wire_off)
+  // (csrc/powersgd_math.h)
+  m.def("psgd_project(Tensor g, Tensor(a!) e, Tensor q, Tensor(b!) wire_p, Tensor low, Tensor raw, int rank, "
+        "float w) -> ()");
+  m.def("psgd_orthonormalize(Tensor(a!) wire_p, Tensor low, int rank) -> ()");
+  m.def("psgd_backproject(Tensor e, Tensor wire_p, Tensor(a!) q_loc, Tensor(b!) wire_q, Tensor low, int rank, "
+        "float w) -> ()");
+  m.def("psgd_residual(Tensor(a!) e, Tensor wire_p, Tensor q_loc, Tensor low, int rank) -> ()");
+  m.def("psgd_decode(Tensor(a!) g, Tensor wire_p, Tensor wire_q, Tensor low, Tensor raw, int rank) -> ()");
   m.def("bilinear_up2(Tensor x) -> Tensor");
   m.def("bilinear_up2_bwd(Tensor dy) -> Tensor");
   m.def("to_nhwc_bf16(Tensor x, int cpad=1) -> Tensor");
@@ -1988,6 +2092,11 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("codec_decode_sum", &ddlpc::codec_decode_sum);
   m.impl("topk_encode", &ddlpc::topk_encode);
   m.impl("topk_decode_sum", &ddlpc::topk_decode_sum);
+  m.impl("psgd_project", &ddlpc::psgd_project);
+  m.impl("psgd_orthonormalize", &ddlpc::psgd_orthonormalize);
+  m.impl("psgd_backproject", &ddlpc::psgd_backproject);
+  m.impl("psgd_residual", &ddlpc::psgd_residual);
+  m.impl("psgd_decode", &ddlpc::psgd_decode);
   m.impl("bilinear_up2", &ddlpc::bilinear_up2);
   m.impl("bilinear_up2_bwd", &ddlpc::bilinear_up2_bwd);
   m.impl("to_nhwc_bf16", &ddlpc::to_nhwc_bf16);

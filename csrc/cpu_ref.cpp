@@ -1188,6 +1188,118 @@ void topk_decode_sum(Tensor out, const Tensor& idx, const Tensor& val, const Ten
   }
 }
 
+// the low-rank codec of csrc/powersgd.hip: the same tables and checks, plain loops, psgd_dot /
+// psgd_inv_norm of powersgd_math.h; the two GEMMs accumulate in fp32 (rows / columns ascending),
+// the Gram-Schmidt sums in double
+void psgd_project(const Tensor& g, Tensor e, const Tensor& q, Tensor wire_p, const Tensor& low, const Tensor& raw,
+                  int64_t rank, double w) {
+  const checks::PsgdSizes s = checks::psgd_project(g, e, q, wire_p, low, raw, rank);
+  const int* lo = low.data_ptr<int>();
+  const int* ra = raw.data_ptr<int>();
+  checks::psgd_tables("psgd_project", lo, low.size(0), ra, raw.size(0), s.ng, s.np, s.nq, rank);
+  const float* G = g.data_ptr<float>();
+  const float* Q = q.data_ptr<float>();
+  float* E = e.data_ptr<float>();
+  float* W = wire_p.data_ptr<float>();
+  const float wf = (float)w;
+  const int r = (int)rank;
+  for (int64_t t = 0; t < low.size(0); ++t) {
+    const int64_t off = lo[5 * t], n = lo[5 * t + 1], m = lo[5 * t + 2];
+    const float* qt = Q + lo[5 * t + 4];
+    for (int64_t i = 0; i < n; ++i) {
+      float acc[kPsgdMaxRank] = {0.f};
+      for (int64_t k = 0; k < m; ++k) {
+        const float a = add_rn(E[off + i * m + k], G[off + i * m + k]);
+        E[off + i * m + k] = a;
+        for (int j = 0; j < r; ++j) acc[j] = __builtin_fmaf(a, qt[k * r + j], acc[j]);
+      }
+      for (int j = 0; j < r; ++j) W[lo[5 * t + 3] + i * r + j] = mul_rn(wf, acc[j]);
+    }
+  }
+  for (int64_t k = 0; k < raw.size(0); ++k)
+    for (int64_t i = 0; i < ra[3 * k + 1]; ++i) W[ra[3 * k + 2] + i] = mul_rn(wf, G[ra[3 * k] + i]);
+}
+
+void psgd_orthonormalize(Tensor wire_p, const Tensor& low, int64_t rank) {
+  const checks::PsgdSizes s = checks::psgd_orthonormalize(wire_p, low, rank);
+  const int* lo = low.data_ptr<int>();
+  checks::psgd_tables("psgd_orthonormalize", lo, low.size(0), nullptr, 0, s.ng, s.np, s.nq, rank);
+  const int r = (int)rank;
+  for (int64_t t = 0; t < low.size(0); ++t) {
+    const int64_t n = lo[5 * t + 1];
+    float* P = wire_p.data_ptr<float>() + lo[5 * t + 3];
+    for (int i = 0; i < r; ++i) {
+      double s2 = 0.0;
+      for (int64_t row = 0; row < n; ++row) s2 += (double)P[row * r + i] * (double)P[row * r + i];
+      const float sc = psgd_inv_norm(s2);
+      for (int64_t row = 0; row < n; ++row) P[row * r + i] = s2 == 0.0 ? 0.f : mul_rn(P[row * r + i], sc);
+      for (int k = i + 1; k < r; ++k) {
+        double dd = 0.0;
+        for (int64_t row = 0; row < n; ++row) dd += (double)P[row * r + i] * (double)P[row * r + k];
+        const float d = (float)dd;
+        for (int64_t row = 0; row < n; ++row) P[row * r + k] = __builtin_fmaf(-d, P[row * r + i], P[row * r + k]);
+      }
+    }
+  }
+}
+
+void psgd_backproject(const Tensor& e, const Tensor& wire_p, Tensor q_loc, Tensor wire_q, const Tensor& low,
+                      int64_t rank, double w) {
+  const checks::PsgdSizes s = checks::psgd_backproject(e, wire_p, q_loc, wire_q, low, rank);
+  const int* lo = low.data_ptr<int>();
+  checks::psgd_tables("psgd_backproject", lo, low.size(0), nullptr, 0, s.ng, s.np, s.nq, rank);
+  const float* E = e.data_ptr<float>();
+  const float wf = (float)w;
+  const int r = (int)rank;
+  for (int64_t t = 0; t < low.size(0); ++t) {
+    const int64_t off = lo[5 * t], n = lo[5 * t + 1], m = lo[5 * t + 2];
+    const float* P = wire_p.data_ptr<float>() + lo[5 * t + 3];
+    float* QL = q_loc.data_ptr<float>() + lo[5 * t + 4];
+    float* QW = wire_q.data_ptr<float>() + lo[5 * t + 4];
+    for (int64_t c = 0; c < m; ++c) {
+      float acc[kPsgdMaxRank] = {0.f};
+      for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < r; ++j) acc[j] = __builtin_fmaf(E[off + i * m + c], P[i * r + j], acc[j]);
+      for (int j = 0; j < r; ++j) {
+        QL[c * r + j] = acc[j];
+        QW[c * r + j] = mul_rn(wf, acc[j]);
+      }
+    }
+  }
+}
+
+// out[low-rank tensors] <- P Q^T (decode) or out - P Q^T (residual)
+void psgd_tiles(float* out, const float* wire_p, const float* qv, const int* lo, int64_t Tn, int r, bool resid) {
+  for (int64_t t = 0; t < Tn; ++t) {
+    const int64_t off = lo[5 * t], n = lo[5 * t + 1], m = lo[5 * t + 2];
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t c = 0; c < m; ++c) {
+        const float v = psgd_dot(wire_p + lo[5 * t + 3] + i * r, 1, qv + lo[5 * t + 4] + c * r, 1, r);
+        float& o = out[off + i * m + c];
+        o = resid ? sub_rn(o, v) : v;
+      }
+  }
+}
+
+void psgd_residual(Tensor e, const Tensor& wire_p, const Tensor& q_loc, const Tensor& low, int64_t rank) {
+  const checks::PsgdSizes s = checks::psgd_residual(e, wire_p, q_loc, low, rank);
+  const int* lo = low.data_ptr<int>();
+  checks::psgd_tables("psgd_residual", lo, low.size(0), nullptr, 0, s.ng, s.np, s.nq, rank);
+  psgd_tiles(e.data_ptr<float>(), wire_p.data_ptr<float>(), q_loc.data_ptr<float>(), lo, low.size(0), (int)rank, true);
+}
+
+void psgd_decode(Tensor g, const Tensor& wire_p, const Tensor& wire_q, const Tensor& low, const Tensor& raw,
+                 int64_t rank) {
+  const checks::PsgdSizes s = checks::psgd_decode(g, wire_p, wire_q, low, raw, rank);
+  const int* lo = low.data_ptr<int>();
+  const int* ra = raw.data_ptr<int>();
+  checks::psgd_tables("psgd_decode", lo, low.size(0), ra, raw.size(0), s.ng, s.np, s.nq, rank);
+  float* G = g.data_ptr<float>();
+  psgd_tiles(G, wire_p.data_ptr<float>(), wire_q.data_ptr<float>(), lo, low.size(0), (int)rank, false);
+  for (int64_t k = 0; k < raw.size(0); ++k)
+    for (int64_t i = 0; i < ra[3 * k + 1]; ++i) G[ra[3 * k] + i] = wire_p.data_ptr<float>()[ra[3 * k + 2] + i];
+}
+
 // ------------------------------------------------------------------------ misc
 Tensor bilinear_up2(const Tensor& x) {
   const Tensor xc = to_cf(f32(x)).contiguous();
@@ -1588,6 +1700,11 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("codec_decode_sum", &codec_decode_sum);
   m.impl("topk_encode", &topk_encode);
   m.impl("topk_decode_sum", &topk_decode_sum);
+  m.impl("psgd_project", &psgd_project);
+  m.impl("psgd_orthonormalize", &psgd_orthonormalize);
+  m.impl("psgd_backproject", &psgd_backproject);
+  m.impl("psgd_residual", &psgd_residual);
+  m.impl("psgd_decode", &psgd_decode);
   m.impl("bilinear_up2", &bilinear_up2);
   m.impl("bilinear_up2_bwd", &bilinear_up2_bwd);
   m.impl("to_nhwc_bf16", &to_nhwc_bf16);

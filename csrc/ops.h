@@ -429,6 +429,25 @@ void topk_encode_launch(const float* g, float* residual, long long n, int k, int
 void topk_decode_sum_launch(float* out, long long n, const int* idx, const float* val,
                             const float* w, int world, int k, hipStream_t st);
 
+// low-rank gradient codec (powersgd.hip; tables, item geometry and counts: powersgd_math.h).  low
+// int32 [T][5], raw int32 [R][3] on the device, checked on the host (codec_checks.h) before any
+// launch; c = the tables' item counts, from that check.  One launch each, grid = items.
+struct PsgdCounts;
+// e <- A = e + g on the low-rank tensors; wire_p[P] = w (A q_prev); wire_p[raw] = w g
+void psgd_project_launch(const float* g, float* e, const float* q, float* wire_p, const int* low, int T,
+                         const int* raw, int R, int r, float w, const PsgdCounts& c, hipStream_t st);
+// every P block of wire_p <- its orthonormal basis (modified Gram-Schmidt, fp64 sums)
+void psgd_orthonormalize_launch(float* wire_p, const int* low, int T, int r, hipStream_t st);
+// q_loc = A^T P-hat (A in e), wire_q = w q_loc
+void psgd_backproject_launch(const float* e, const float* wire_p, float* q_loc, float* wire_q, const int* low,
+                             int T, int r, float w, const PsgdCounts& c, hipStream_t st);
+// e <- e - P-hat q_loc^T
+void psgd_residual_launch(float* e, const float* wire_p, const float* q_loc, const int* low, int T, int r,
+                          const PsgdCounts& c, hipStream_t st);
+// g <- P-hat Q^T on the low-rank tensors, g <- wire_p[raw] on the raw spans
+void psgd_decode_launch(float* g, const float* wire_p, const float* wire_q, const int* low, int T, const int* raw,
+                        int R, int r, const PsgdCounts& c, hipStream_t st);
+
 // ---------------------------------------------------------------- deterministic reductions
 int reduce_rows_chunks(int R);
 void reduce_rows_launch(const float* in, int R, long long N, double* tmp, double* sums,

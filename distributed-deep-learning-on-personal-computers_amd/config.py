@@ -21,7 +21,7 @@ from dataclasses import dataclass, field, fields
 import math
 from typing import Any, Dict, List, Optional, Sequence, Union
 
-GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax", "topk")
+GRAD_CODECS = ("none", "fp16_absmax", "int8_absmax", "topk", "powersgd")
 CODEC_SCALES = ("global", "bucket", "tensor")
 REDUCE_OPS = ("mean", "sum", "reference")
 UP_MODES = ("conv_transpose", "bilinear")
@@ -161,11 +161,14 @@ class TrainConfig:
                                          # model (parallel/bucket_plan.py) | size: size only
     reduce: str = "mean"                 # mean | sum | reference (the W=2 "sum" parity mode)
     grad_codec: str = "none"             # none | fp16_absmax | int8_absmax (ref.py:25) | topk
-                                         # (top-k sparsification with error feedback)
+                                         # (top-k sparsification with error feedback) | powersgd
+                                         # (low-rank factors with error feedback, all-reduced)
     codec_scale: str = "bucket"          # global (reference parity) | bucket | tensor
     topk_ratio: float = 0.01             # topk: share of each bucket's entries sent per exchange,
                                          # k = min(n, max(1, ceil(n * ratio))); the rest stays in
                                          # a per-rank residual for the next exchange
+    powersgd_rank: int = 4               # powersgd: rank r (1..16) of the two factors P (n x r), Q (m x r)
+                                         # every weight gradient is sent as; one rank for the run
     wire_dtype: str = "fp32"             # fp32 all-reduce | bf16 transport, fp32 accumulate
     overlap_comm: bool = True
     broadcast_buffers: bool = False      # BN running stats from rank 0 (reference: off)
@@ -242,6 +245,14 @@ class TrainConfig:
         if self.grad_codec == "topk" and (self.codec_scale != "bucket" or self.wire_dtype != "fp32"):
             raise ValueError("grad_codec='topk' selects per bucket and sends fp32 values: it needs "
                              "codec_scale='bucket' and wire_dtype='fp32'")
+        if not 1 <= self.powersgd_rank <= 16:
+            raise ValueError("powersgd_rank must satisfy 1 <= powersgd_rank <= 16")
+        if self.grad_codec == "powersgd" and (self.codec_scale != "bucket" or self.wire_dtype != "fp32"):
+            raise ValueError("grad_codec='powersgd' factors per bucket and sends fp32 values: it needs "
+                             "codec_scale='bucket' and wire_dtype='fp32'")
+        if self.grad_codec == "powersgd" and self.comm_proxy:
+            raise ValueError("grad_codec='powersgd' is not combined with comm_proxy (the proxy stands in "
+                             "for a plain fp32 all-reduce only)")
         if self.accum_steps < 1 or self.batch_per_gpu < 1:
             raise ValueError("accum_steps and batch_per_gpu must be >= 1")
         if self.crops_per_epoch < 0:

@@ -64,3 +64,31 @@ def topk_decode_sum(out: torch.Tensor, idx: Sequence[torch.Tensor], val: Sequenc
     w = torch.tensor(list(weights), dtype=torch.float32, device=out.device)
     _ext.ops().topk_decode_sum(out, torch.stack(list(idx)), torch.stack(list(val)), w)
     return out
+
+
+# Low-rank codec (``parallel.codec.powersgd_*`` is the contract; csrc/powersgd.hip).  ``low`` /
+# ``raw`` are the plan's tables on the buffers' device; a caller passes the SAME table tensors on
+# every call, so the GPU binding checks their values on the host once.  One launch per call.
+def psgd_project(g, e, q, wire_p, low, raw, rank: int, w: float):
+    """``e += g`` on the low-rank tensors, ``wire_p[P] = w (e q)``, ``wire_p[raw] = w g``."""
+    _ext.ops().psgd_project(g, e, q, wire_p, low, raw, rank, w)
+
+
+def psgd_orthonormalize(wire_p, low, rank: int):
+    """Every ``P`` block of ``wire_p`` in place: modified Gram-Schmidt, fp64 sums."""
+    _ext.ops().psgd_orthonormalize(wire_p, low, rank)
+
+
+def psgd_backproject(e, wire_p, q_loc, wire_q, low, rank: int, w: float):
+    """``q_loc = e^T P_hat``, ``wire_q = w q_loc``."""
+    _ext.ops().psgd_backproject(e, wire_p, q_loc, wire_q, low, rank, w)
+
+
+def psgd_residual(e, wire_p, q_loc, low, rank: int):
+    """``e -= P_hat q_loc^T``."""
+    _ext.ops().psgd_residual(e, wire_p, q_loc, low, rank)
+
+
+def psgd_decode(g, wire_p, wire_q, low, raw, rank: int):
+    """``g = P_hat Q^T`` on the low-rank tensors, ``g = wire_p[raw]`` on the raw spans."""
+    _ext.ops().psgd_decode(g, wire_p, wire_q, low, raw, rank)

@@ -30,6 +30,16 @@ MI355X design:
   (index, value) pairs — 8 bytes per sent entry on the wire — which are all-gathered and
   scatter-summed in rank order at ``finish()`` (csrc/topk.hip); what was not sent stays in the
   residual for the next exchange.  The residual is not checkpointed: a resume starts from zero;
+* optional low-rank codec with error feedback (``grad_codec="powersgd"``, Vogels et al. 2019):
+  every weight gradient of a bucket, viewed as an n x m matrix, travels as two thin factors
+  P (n x r) and Q (m x r), r = ``powersgd_rank``, summed by two plain all-reduces — the cost per
+  rank does not grow with the world size; biases and BatchNorm weights ride along as they are.
+  The first all-reduce (P) is launched from backward, ``finish()`` orthonormalises P, forms Q and
+  the residual and launches every bucket's second all-reduce before it waits for the first of
+  them (csrc/powersgd.hip; the contract is ``parallel.codec.powersgd_*``).  The residual and
+  the warm start ``q_prev`` are not checkpointed: a resume restarts both.  ``q_prev`` is never
+  re-seeded: a weight whose residual + gradient is exactly zero on every rank in one exchange
+  gets Q = 0 and is not sent again (``parallel.codec.powersgd_decode``);
 * optional bf16 wire format (``wire_dtype="bf16"``): half the bytes of the fp32
   all-reduce — an all-to-all of bf16 chunks (the reduce-scatter's transport) launched
   asynchronously from backward, then in ``finish()`` a rank-ordered fp32 sum of the owned
@@ -52,7 +62,7 @@ from .flat import FlatParams
 
 class _Bucket:
     __slots__ = ("idx", "start", "end", "params", "pending", "work", "payload", "scales",
-                 "gathered", "launched", "wire", "ev")
+                 "gathered", "launched", "wire", "ev", "psgd")
 
     def __init__(self, idx, start, end, params):
         self.idx, self.start, self.end, self.params = idx, start, end, params
@@ -62,21 +72,40 @@ class _Bucket:
         self.launched = False
         self.wire = None                 # bf16 wire buffers (send, recv, owned chunk, out)
         self.ev = None                   # comm proxy: (ready, start, end) events
+        self.psgd = None                 # low-rank codec: plan, tables and buffers
+
+
+class _PowerSGDState:
+    """Per bucket: the plan, its tables on the gradient's device, the two wire buffers, the
+    warm start ``q_prev`` and this rank's ``q_loc`` (made on first use; gloo with GPU tensors:
+    host copies of the wire buffers too)."""
+    __slots__ = ("plan", "low", "raw", "wire_p", "wire_q", "q_prev", "q_loc", "host_p", "host_q")
+
+    def __init__(self, plan):
+        self.plan = plan
+        self.low = self.raw = self.wire_p = self.wire_q = self.q_prev = self.q_loc = None
+        self.host_p = self.host_q = None
 
 
 class GradBucketReducer:
     def __init__(self, flat: FlatParams, group=None, bucket_mb: float = 8.0,
                  reduce: str = "mean", grad_codec: str = "none", codec_scale: str = "bucket",
                  overlap: bool = True, use_hooks: bool = True, wire_dtype: str = "fp32",
-                 proxy: int = 0, cuts: Optional[List[int]] = None, topk_ratio: float = 0.01):
+                 proxy: int = 0, cuts: Optional[List[int]] = None, topk_ratio: float = 0.01,
+                 powersgd_rank: int = 4, powersgd_seed: int = 0):
         if wire_dtype not in ("fp32", "bf16"):
             raise ValueError(f"wire_dtype={wire_dtype!r}")
         if grad_codec == "topk" and (codec_scale != "bucket" or wire_dtype != "fp32"):
             raise ValueError("grad_codec='topk' needs codec_scale='bucket' and wire_dtype='fp32'")
         if not 0.0 < topk_ratio <= 1.0:
             raise ValueError(f"topk_ratio={topk_ratio!r} not in (0, 1]")
+        if grad_codec == "powersgd" and (codec_scale != "bucket" or wire_dtype != "fp32"):
+            raise ValueError("grad_codec='powersgd' needs codec_scale='bucket' and wire_dtype='fp32'")
+        if not 1 <= powersgd_rank <= C.POWERSGD_MAX_RANK:
+            raise ValueError(f"powersgd_rank={powersgd_rank!r} not in 1..{C.POWERSGD_MAX_RANK}")
+        self.powersgd_rank, self.powersgd_seed = int(powersgd_rank), int(powersgd_seed)
         self.topk_ratio = topk_ratio
-        self.residual: Optional[torch.Tensor] = None    # topk error feedback, made on first use
+        self.residual: Optional[torch.Tensor] = None    # topk / powersgd error feedback, made on first use
         self.flat = flat
         self.wire_dtype = wire_dtype
         self.group = group
@@ -135,6 +164,12 @@ class GradBucketReducer:
         if grad_codec == "topk":                 # entries sent per exchange, over all buckets
             self.stats["topk_k"] = sum(C.topk_count(b.end - b.start, topk_ratio)
                                        for b in self.buckets)
+        if grad_codec == "powersgd":             # floats on the wire per exchange and rank, over all buckets
+            for b in self.buckets:
+                b.psgd = _PowerSGDState(C.powersgd_plan(flat, b.params, b.start, self.powersgd_rank))
+            self.stats["powersgd_wire_floats"] = sum(b.psgd.plan.wire_p + b.psgd.plan.wire_q
+                                                     for b in self.buckets)
+            self.stats["powersgd_dense_floats"] = sum(b.psgd.plan.dense for b in self.buckets)
         # readiness calibration (``start_calibration``): per-parameter gradient-complete times
         # of one synchronised step, relative to its backward start (Trainer.calibrate_bucket_plan)
         self._index = {id(p): i for i, p in enumerate(flat.order)}
@@ -274,6 +309,13 @@ class GradBucketReducer:
             return
         # lossy codec: encode -> all_gather(payload, scales) -> decode+sum at finish()
         from ..ops import codec_ops
+        if self.codec == "powersgd":
+            # step 1: e <- e + g, wire_p = w (e q_prev) | w g[raw]; its all-reduce runs under backward
+            st = self._psgd_buffers(b)
+            codec_ops.psgd_project(g, self.residual[b.start:b.end], st.q_prev, st.wire_p, st.low, st.raw,
+                                   self.powersgd_rank, self.weight)
+            b.work = ("psgd", self._psgd_all_reduce(st.wire_p, st.host_p))
+            return
         if self.codec == "topk":
             # (payload, scales) = (idx, val) of the k entries taken out of residual + gradient
             if self.residual is None:
@@ -291,6 +333,55 @@ class GradBucketReducer:
         w1 = dist.all_gather(b.gathered[0], b.payload, group=self.group, async_op=True)
         w2 = dist.all_gather(b.gathered[1], b.scales, group=self.group, async_op=True)
         b.work = (w1, w2)
+
+    def _psgd_buffers(self, b: _Bucket) -> _PowerSGDState:
+        st, dev = b.psgd, self.flat.grad_buf.device
+        if st.wire_p is None:
+            if self.residual is None:
+                self.residual = torch.zeros_like(self.flat.grad_buf)
+            st.low, st.raw = st.plan.low.to(dev), st.plan.raw.to(dev)
+            st.wire_p = torch.zeros(st.plan.wire_p, dtype=torch.float32, device=dev)
+            st.wire_q = torch.zeros(st.plan.wire_q, dtype=torch.float32, device=dev)
+            st.q_loc = torch.zeros_like(st.wire_q)
+            st.q_prev = C.powersgd_init_q(st.plan, self.powersgd_seed, b.idx).to(dev)
+            if self.backend == "gloo" and dev.type == "cuda":
+                # gloo is a host transport: it gets host tensors (GPU tensors are for RCCL)
+                st.host_p = torch.empty(st.plan.wire_p, dtype=torch.float32, pin_memory=True)
+                st.host_q = torch.empty(st.plan.wire_q, dtype=torch.float32, pin_memory=True)
+        return st
+
+    def _psgd_all_reduce(self, wire: torch.Tensor, host: Optional[torch.Tensor]):
+        """-> (work, host copy or None) of the asynchronous SUM of one wire buffer."""
+        if host is not None:
+            host.copy_(wire)
+            return dist.all_reduce(host, group=self.group, async_op=True), host
+        return dist.all_reduce(wire, group=self.group, async_op=True), None
+
+    @staticmethod
+    def _psgd_wait(work, wire: torch.Tensor):
+        w, host = work
+        w.wait()
+        if host is not None:
+            wire.copy_(host)
+
+    def _finish_powersgd(self):
+        """Steps 2-4 of every bucket and its second all-reduce, and only then the waits and the
+        decodes: the second round of collectives overlaps across the buckets."""
+        from ..ops import codec_ops
+        r = self.powersgd_rank
+        for b in self.buckets:
+            st, e = b.psgd, self.residual[b.start:b.end]
+            self._psgd_wait(b.work[1], st.wire_p)
+            codec_ops.psgd_orthonormalize(st.wire_p, st.low, r)
+            codec_ops.psgd_backproject(e, st.wire_p, st.q_loc, st.wire_q, st.low, r, self.weight)
+            codec_ops.psgd_residual(e, st.wire_p, st.q_loc, st.low, r)
+            b.work = ("psgd", self._psgd_all_reduce(st.wire_q, st.host_q))
+        for b in self.buckets:
+            st = b.psgd
+            self._psgd_wait(b.work[1], st.wire_q)
+            codec_ops.psgd_decode(self._seg(b), st.wire_p, st.wire_q, st.low, st.raw, r)
+            st.q_prev, st.wire_q = st.wire_q, st.q_prev       # the reduced Q is the next warm start
+            b.work = None
 
     PROXY_BLOCKS = 16                    # RCCL-like channel count
 
@@ -382,6 +473,10 @@ class GradBucketReducer:
         for b in self.buckets:
             if not b.launched:
                 self._launch(b)
+        if self.codec == "powersgd":
+            self._finish_powersgd()
+            self._sync = False
+            return
         for b in self.buckets:                      # bf16 wire: all-gathers in bucket order
             if isinstance(b.work, tuple) and b.work[0] == "a2a":
                 self._finish_bf16(b)

@@ -113,6 +113,9 @@ class Trainer:
                          and cfg.dtype == "bf16")
         self.meter = DeviceMeter(self.device)
         self.logger = RunLogger(cfg.log_dir, self.rank, cfg.grad_codec)
+        if self.reducer is not None and cfg.grad_codec == "powersgd":
+            # the codec's size per exchange, once: powersgd_wire_floats, powersgd_dense_floats
+            self.logger.log({k: v for k, v in self.reducer.stats.items() if k.startswith("powersgd")})
         if cfg.trace_ranges:
             enable_ranges(True)
         self.phases = PhaseTimer(self.device) if cfg.phase_timers else None
@@ -189,6 +192,7 @@ class Trainer:
         return GradBucketReducer(self.flat, bucket_mb=bucket_mb, reduce=c.reduce,
                                  grad_codec=c.grad_codec, codec_scale=c.codec_scale,
                                  topk_ratio=c.topk_ratio,
+                                 powersgd_rank=c.powersgd_rank, powersgd_seed=c.seed,
                                  overlap=c.overlap_comm, use_hooks=(self.impl != "hip"),
                                  wire_dtype=c.wire_dtype,
                                  proxy=c.comm_proxy if self.world == 1 else 0, cuts=cuts)

@@ -105,7 +105,7 @@ class RunLogger:
             os.makedirs(log_dir, exist_ok=True)
             self.jsonl = open(os.path.join(log_dir, "metrics.jsonl"), "a")
             name = {"none": "float32", "fp16_absmax": "float16", "int8_absmax": "int8",
-                    "topk": "topk"}[codec]
+                    "topk": "topk", "powersgd": "powersgd"}[codec]
             self.otus_path = os.path.join(log_dir, f"otus_{name}.txt")
 
     def header(self, batch_per_gpu: int, world: int, accum: int, width_divisor: int):

@@ -24,7 +24,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 # units compiled without the packed fp32 VALU forms (v_pk_add/mul/fma_f32): their results must be
 # bit-exact against a scalar oracle, one separately rounded operation per element
-NO_PACKED_FP32 = ("topk.hip",)
+NO_PACKED_FP32 = ("topk.hip", "powersgd.hip")
 
 
 def torch_paths():

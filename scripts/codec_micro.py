@@ -5,7 +5,11 @@
   and decode also on their own; the encode's residual is re-filled outside the timed window
   so every repeat selects from the same data;
 * next to them the int8 codec's ``codec_absmax`` + ``codec_encode`` + ``codec_decode_sum``
-  (csrc/misc.hip) on the same bucket.
+  (csrc/misc.hip) on the same bucket;
+* the low-rank codec on the flagship model's whole gradient buffer (the default ``TrainConfig``
+  model, ``--mb`` buckets, ``--rank``): the five ``psgd_*`` kernels of every bucket, no
+  collective (csrc/powersgd.hip), each of the five also on its own; next to it, on the same
+  buffer and buckets, ``topk_encode`` + ``topk_decode_sum`` at ratio 0.01 and a plain device copy.
 
 Each variant is timed with device events over ``--inner`` back-to-back calls, ``--repeats``
 times round-robin after a warm-up; the median, min and max per call are reported, with the
@@ -26,12 +30,54 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 RATIOS = (0.001, 0.01, 0.1)
 
 
+def powersgd_variants(variants, o, dev, mb, rank, gen):
+    """The flagship model's gradient buffer in the reducer's buckets: the five psgd_* kernels of
+    every bucket (together and one by one), top-k at 0.01 and a device copy on the same buffer."""
+    from ddlpc.config import TrainConfig
+    from ddlpc.models.unet import UNet
+    from ddlpc.parallel import codec as C
+    from ddlpc.parallel.flat import FlatParams
+    from ddlpc.parallel.reducer import GradBucketReducer
+    flat = FlatParams([p for p in UNet.from_config(TrainConfig().model).to(dev).parameters() if p.requires_grad])
+    red = GradBucketReducer(flat, bucket_mb=mb, grad_codec="powersgd", powersgd_rank=rank)
+    g = flat.grad_buf
+    g.copy_((torch.randn(g.numel(), generator=gen) * 1e-3).to(dev))
+    sts = [(b, red._psgd_buffers(b)) for b in red.buckets]
+    e, out, w = red.residual, torch.empty_like(g), torch.full((2,), 0.5, device=dev)
+    steps = {
+        "project": lambda b, s: o.psgd_project(g[b.start:b.end], e[b.start:b.end], s.q_prev, s.wire_p, s.low, s.raw, rank, 0.5),
+        "orthonormalize": lambda b, s: o.psgd_orthonormalize(s.wire_p, s.low, rank),
+        "backproject": lambda b, s: o.psgd_backproject(e[b.start:b.end], s.wire_p, s.q_loc, s.wire_q, s.low, rank, 0.5),
+        "residual": lambda b, s: o.psgd_residual(e[b.start:b.end], s.wire_p, s.q_loc, s.low, rank),
+        "decode": lambda b, s: o.psgd_decode(g[b.start:b.end], s.wire_p, s.wire_q, s.low, s.raw, rank),
+    }
+
+    def exchange(names=tuple(steps)):
+        for name in names:
+            for b, s in sts:
+                steps[name](b, s)
+
+    def topk():
+        for b, _ in sts:
+            k = C.topk_count(b.end - b.start, 0.01)
+            i, v = o.topk_encode(g[b.start:b.end], e[b.start:b.end], k)
+            o.topk_decode_sum(out[b.start:b.end], torch.stack([i, i]), torch.stack([v, v]), w)
+    exchange()                                      # (the tables' check on the host)
+    variants[f"model powersgd r{rank} exchange"] = exchange
+    for name in steps:
+        variants[f"model powersgd r{rank} {name}"] = lambda name=name: exchange((name,))
+    variants["model topk 0.01 encode+decode_sum"] = topk
+    variants["model device copy"] = lambda: out.copy_(g)
+    return {"floats": g.numel(), "buckets": len(sts), **{k: v for k, v in red.stats.items() if "powersgd" in k}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mb", type=float, default=8.0, help="bucket size (fp32 gradient MB)")
+    ap.add_argument("--rank", type=int, default=4, help="powersgd rank")
     ap.add_argument("--trace", action="store_true", help="a few calls of each variant, no timing")
     a = ap.parse_args()
     from ddlpc.ops import _ext
@@ -84,6 +130,7 @@ def main():
     variants["int8 absmax+encode"] = int8_enc
     variants["int8 decode_sum"] = int8_dec
     variants["int8 absmax+encode+decode_sum"] = int8_both
+    model = powersgd_variants(variants, o, dev, a.mb, a.rank, gen)
 
     if a.trace:
         for fn in variants.values():
@@ -105,7 +152,7 @@ def main():
             if r >= a.warmup:
                 times[name].append(e0_.elapsed_time(e1_) * 1e3 / a.inner)
     res = {"n": n, "world": world, "repeats": a.repeats, "inner": a.inner,
-           "device": torch.cuda.get_device_name(0), "wire_bytes_per_rank": wire}
+           "device": torch.cuda.get_device_name(0), "wire_bytes_per_rank": wire, "model": model}
     for name, t in times.items():
         t = sorted(t)
         res[name] = {"median_us": round(statistics.median(t), 2), "min_us": round(t[0], 2),
