@@ -21,6 +21,7 @@
 #include "data_checks.h"
 #include "head_checks.h"
 #include "head_math.h"
+#include "label_checks.h"
 #include "lamb_checks.h"
 #include "tail_checks.h"
 #include "ops.h"
@@ -1911,6 +1912,31 @@ std::vector<at::Tensor> scene_finalize(const at::Tensor& acc, int64_t K,
   return {pred, cm};
 }
 
+// label_dist2 (radius < 0) and label_erode: one launch, no scratch, no host read
+at::Tensor label_boundary(const at::Tensor& labels, int64_t K, int64_t ignore_index, int64_t radius,
+                          int64_t fill) {
+  CHECK_DEV(labels);
+  c10::DeviceGuard guard(labels.device());
+  const int64_t H = labels.size(-2), W = labels.size(-1), B = labels.dim() == 3 ? labels.size(0) : 1;
+  TORCH_CHECK(B <= 65535 && label_tiles((int)H) <= 65535, "labels: too many images or tile rows for one grid");
+  at::Tensor out = at::empty_like(labels, labels.options().dtype(radius < 0 ? at::kInt : labels.scalar_type()));
+  if (labels.numel() > 0)
+    label_boundary_launch(labels.data_ptr(), labels.scalar_type() == at::kByte, (int)B, (int)H, (int)W,
+                          (int)K, (int)ignore_index, (int)radius, (int)fill, out.data_ptr(), cur_stream());
+  return out;
+}
+
+at::Tensor label_dist2(const at::Tensor& labels, int64_t K, int64_t ignore_index) {
+  checks::label_dist2(labels, K, ignore_index);
+  return label_boundary(labels, K, ignore_index, -1, 0);
+}
+
+at::Tensor label_erode(const at::Tensor& labels, int64_t K, int64_t ignore_index, int64_t radius,
+                       int64_t fill) {
+  checks::label_erode(labels, K, ignore_index, radius, fill);
+  return label_boundary(labels, K, ignore_index, radius, fill);
+}
+
 // -> the CU count grids are sized for after reserving k CUs (k < 0: query only)
 int64_t set_cu_reserve(int64_t k) {
   if (k >= 0) g_cu_reserve = (int)std::min<int64_t>(k, std::max(0, phys_cus() - 8));
@@ -2047,6 +2073,10 @@ TORCH_LIBRARY(ddlpc, m) {
   m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
         "Tensor? bn4=None, Tensor? codes=None) -> ()");
   m.def("scene_finalize(Tensor acc, int K, Tensor? labels=None, int ignore_index=-100) -> Tensor[]");
+  // label_math.h: squared distance to the nearest valid pixel of another class (truncated at 16,
+  // 257 = far, 0 = invalid pixel), and the labels with the band d2 <= radius^2 rewritten to fill
+  m.def("label_dist2(Tensor labels, int K, int ignore_index) -> Tensor");
+  m.def("label_erode(Tensor labels, int K, int ignore_index, int radius, int fill) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
@@ -2109,5 +2139,7 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("window_gather", &ddlpc::window_gather);
   m.impl("head_predict_accum", &ddlpc::head_predict_accum);
   m.impl("scene_finalize", &ddlpc::scene_finalize);
+  m.impl("label_dist2", &ddlpc::label_dist2);
+  m.impl("label_erode", &ddlpc::label_erode);
   m.impl("comm_proxy", &ddlpc::comm_proxy);
 }

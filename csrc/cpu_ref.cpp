@@ -32,6 +32,8 @@
 #include "data_math.h"
 #include "head_checks.h"
 #include "head_math.h"
+#include "label_checks.h"
+#include "label_math.h"
 #include "lamb_checks.h"
 #include "optim_math.h"
 #include "tail_checks.h"
@@ -1653,6 +1655,69 @@ std::vector<Tensor> scene_finalize(const Tensor& acc, int64_t K, const optional<
   return {pred, cm};
 }
 
+// the twin of label_boundary_kernel (boundary.hip): the same 32 x 32 tiles inside 64 x 64 stages,
+// the same words ne[row][class], the same walk over dy (label_math.h).  radius < 0: d2 (int32 out)
+template <typename T>
+void label_boundary_t(const T* lab, int64_t B, int64_t H, int64_t W, int K, int ignore_index, int radius,
+                      int fill, void* out) {
+  const int64_t ty = (H + kLabelTile - 1) / kLabelTile, tx = (W + kLabelTile - 1) / kLabelTile;
+  at::parallel_for(0, B * ty * tx, 1, [&](int64_t t0, int64_t t1) {
+    std::vector<uint64_t> ne(kLabelStage * kLabelMaxK);
+    for (int64_t t = t0; t < t1; ++t) {
+      const int64_t img = t / (ty * tx) * H * W;
+      const int64_t y0 = t / tx % ty * kLabelTile, x0 = t % tx * kLabelTile;
+      const T* lp = lab + img;
+      for (int r = 0; r < kLabelStage; ++r) {
+        const int64_t sy = y0 - kLabelR + r;
+        uint64_t valid = 0, plane[4] = {0, 0, 0, 0};
+        for (int c = 0; c < kLabelStage; ++c) {
+          const int64_t sx = x0 - kLabelR + c;
+          if (sy < 0 || sy >= H || sx < 0 || sx >= W) continue;
+          const int cls = label_class((long long)lp[sy * W + sx], K, ignore_index);
+          if (cls < 0) continue;
+          valid |= 1ull << c;
+          for (int j = 0; j < 4; ++j) plane[j] |= (uint64_t)((cls >> j) & 1) << c;
+        }
+        for (int k = 0; k < kLabelMaxK; ++k) ne[r * kLabelMaxK + k] = other_mask(valid, plane, k);
+      }
+      for (int64_t oy = y0; oy < std::min(H, y0 + kLabelTile); ++oy)
+        for (int64_t ox = x0; ox < std::min(W, x0 + kLabelTile); ++ox) {
+          const T l = lp[oy * W + ox];
+          const int cls = label_class((long long)l, K, ignore_index);
+          const int d2 = label_dist2_at(ne.data(), (int)(oy - y0) + kLabelR, (int)(ox - x0) + kLabelR, cls,
+                                        radius < 0 ? kLabelR : radius);
+          if (radius < 0)
+            static_cast<int*>(out)[img + oy * W + ox] = d2;
+          else
+            static_cast<T*>(out)[img + oy * W + ox] = label_eroded(cls, d2, radius) ? (T)fill : l;
+        }
+    }
+  });
+}
+
+Tensor label_boundary(const Tensor& labels, int64_t K, int64_t ignore_index, int64_t radius, int64_t fill) {
+  const int64_t H = labels.size(-2), W = labels.size(-1), B = labels.dim() == 3 ? labels.size(0) : 1;
+  Tensor out = at::empty_like(labels, labels.options().dtype(radius < 0 ? at::kInt : labels.scalar_type()));
+  if (labels.numel() == 0) return out;
+  if (labels.scalar_type() == at::kByte)
+    label_boundary_t(labels.data_ptr<uint8_t>(), B, H, W, (int)K, (int)ignore_index, (int)radius, (int)fill,
+                     out.data_ptr());
+  else
+    label_boundary_t(labels.data_ptr<int64_t>(), B, H, W, (int)K, (int)ignore_index, (int)radius, (int)fill,
+                     out.data_ptr());
+  return out;
+}
+
+Tensor label_dist2(const Tensor& labels, int64_t K, int64_t ignore_index) {
+  checks::label_dist2(labels, K, ignore_index);
+  return label_boundary(labels, K, ignore_index, -1, 0);
+}
+
+Tensor label_erode(const Tensor& labels, int64_t K, int64_t ignore_index, int64_t radius, int64_t fill) {
+  checks::label_erode(labels, K, ignore_index, radius, fill);
+  return label_boundary(labels, K, ignore_index, radius, fill);
+}
+
 }  // namespace
 }  // namespace ddlpc_cpu
 
@@ -1717,4 +1782,6 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("warp_params", &warp_params);
   m.impl("head_predict_accum", &head_predict_accum);
   m.impl("scene_finalize", &scene_finalize);
+  m.impl("label_dist2", &label_dist2);
+  m.impl("label_erode", &label_erode);
 }

@@ -364,6 +364,13 @@ void window_gather_launch(const uint8_t* scene, const int* origins, int B, int S
 void scene_finalize_launch(const float* acc, long long P, int K, int KA, const uint8_t* labels,
                            int ignore_index, uint8_t* pred, int64_t* cm, hipStream_t st);
 
+// ---------------------------------------------------------------- label boundaries (boundary.hip)
+int label_tiles(int n);               // 32-pixel tiles along one side: the grid is tiles(W) x tiles(H) x B
+// labels [B][H][W], uint8 (u8) or int64.  radius < 0: out = d2, int32 [B][H][W] (label_math.h);
+// radius 0..16: out = the labels with every valid pixel at d2 <= radius^2 rewritten to fill
+void label_boundary_launch(const void* labels, bool u8, int B, int H, int W, int K, int ignore_index,
+                           int radius, int fill, void* out, hipStream_t st);
+
 // ---------------------------------------------------------------- optimizer / packing
 void adam_launch(float* p, const float* g, float* m, float* v, long long n, float b1, float b2,
                  float eps, float wd, float step_size, float inv_sqrt_bc2, hipStream_t st,

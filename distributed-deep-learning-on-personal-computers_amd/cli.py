@@ -26,6 +26,9 @@ the training split's labels) trains with ``CrossEntropyLoss(weight=...)``, fused
 kernels — the validation loss stays unweighted, the per-class IoU shows the effect;
 ``--dice-weight 1 --dice-smooth 1`` adds a soft-Dice term to the training loss (cross-entropy +
 lambda * dice, formed inside the head kernels);
+``validate --eval-erode 3`` and ``predict --eval-erode 3`` score the ISPRS "eroded boundaries" sheet
+(labels within 3 px of a class border count for nothing; eroded on the device, ``ops/boundary.py``),
+``train --train-erode r`` keeps that band out of the training loss;
 ``config`` prints the resolved configuration (handy for writing a YAML to start from).
 """
 from __future__ import annotations

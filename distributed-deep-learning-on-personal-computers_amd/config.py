@@ -127,6 +127,12 @@ class TrainConfig:
     # stays the plain cross-entropy).  dice_smooth: the eps of numerator and denominator
     dice_weight: float = 0.0
     dice_smooth: float = 1.0
+    # boundary erosion of the labels, on the device (ops/boundary.py; 2-D): every labelled pixel
+    # within this many pixels (Euclidean, 0..16) of another class becomes an ignored pixel.
+    # eval_erode: in validate and predict (3 = the ISPRS "eroded boundaries" score sheet; 0 = full
+    # reference); train_erode: in front of the training loss (label noise at object outlines)
+    eval_erode: int = 0
+    train_erode: int = 0
     # ---- optimisation ----------------------------------------------------------
     batch_per_gpu: int = 1               # batch_size, ref.py:686
     accum_steps: int = 1                 # frequency_sending_gradients, ref.py:685
@@ -283,6 +289,13 @@ class TrainConfig:
         if self.dice_weight > 0 and self.bn_window > 1:
             raise ValueError("dice_weight > 0 is not combined with bn_window > 1 (the Dice sums are per "
                              "micro-batch; bn_window=-1 or 0 runs the micro-batches one by one)")
+        for name in ("eval_erode", "train_erode"):
+            if not (isinstance(getattr(self, name), int) and 0 <= getattr(self, name) <= 16):
+                raise ValueError(f"{name} must be an integer in 0..16 (pixels)")
+        if self.model.dims == 3 and (self.eval_erode or self.train_erode):
+            raise ValueError("eval_erode and train_erode are 2-D only (model.dims == 2)")
+        if self.model.out_classes > 16 and (self.eval_erode or self.train_erode):
+            raise ValueError("eval_erode and train_erode support at most 16 classes")
         if isinstance(self.class_weights, (list, tuple)):      # a YAML / JSON list
             self.class_weights = ",".join(repr(float(v)) for v in self.class_weights)
         cw = parse_class_weights(self.class_weights, self.model.out_classes)

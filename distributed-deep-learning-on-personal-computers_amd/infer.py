@@ -39,7 +39,9 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-BLENDS = ("core", "cosine")
+from .ops import boundary
+
+BLENDS =("core", "cosine")
 TTA_CODES = {"none": (0,), "flip": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
 
 
@@ -287,9 +289,13 @@ class ScenePredictor:
             dst[..., K] += w2[ys:ye, xs:xe]
 
     @torch.no_grad()
-    def finalize(self, acc: torch.Tensor, labels=None, ignore_index: int = -100):
+    def finalize(self, acc: torch.Tensor, labels=None, ignore_index: int = -100, erode: int = 0):
         """Accumulator -> (class map uint8 ``[H, W]`` on the host, confusion matrix int64
-        ``[K, K]`` on the host — ``cm[label, pred]`` — or None without labels)."""
+        ``[K, K]`` on the host — ``cm[label, pred]`` — or None without labels).  ``erode`` = r > 0
+        counts the "eroded boundaries" sheet: the scene's labels within r pixels of another
+        class are rewritten to 255 on the device, once, before they are counted."""
+        if not 0 <= erode <= boundary.MAX_RADIUS:
+            raise ValueError(f"erode must be in 0..{boundary.MAX_RADIUS}, got {erode}")
         lab = None
         if labels is not None:
             lab = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
@@ -297,12 +303,14 @@ class ScenePredictor:
                 raise ValueError(f"labels must be uint8 {tuple(acc.shape[:2])}, got "
                                  f"{lab.dtype} {tuple(lab.shape)}")
             lab = lab.to(acc.device).contiguous()
+            if erode:
+                lab = boundary.erode_labels(lab, self.classes, erode, ignore_index)
         pred, cm = self.ops.scene_finalize(acc, self.classes, lab, ignore_index)
         return pred.cpu(), (cm.cpu() if lab is not None else None)
 
-    def predict(self, scene, labels=None, ignore_index: int = -100):
+    def predict(self, scene, labels=None, ignore_index: int = -100, erode: int = 0):
         """-> (class map, confusion matrix or None): ``finalize(accumulate(scene), labels)``."""
-        return self.finalize(self.accumulate(scene), labels, ignore_index)
+        return self.finalize(self.accumulate(scene), labels, ignore_index, erode)
 
     @torch.no_grad()
     def proba(self, scene) -> torch.Tensor:
@@ -352,7 +360,9 @@ def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[st
     ``<stem>.png`` (class indices), ``<stem>_color.png`` (Vaihingen palette, 6 classes) and
     optionally ``<stem>_proba.npy`` (fp16 ``[K, H, W]``), appends one line per scene to
     ``out_dir/predict.jsonl`` and returns the summary.  ``tta`` (``none``, ``flip``, ``d4``)
-    averages every window over the symmetries of the square (test-time augmentation).  Under
+    averages every window over the symmetries of the square (test-time augmentation).
+    ``cfg.eval_erode`` = r > 0 leaves the labels within r pixels of a class border out of the
+    confusion matrix (the "eroded boundaries" sheet; every record carries ``eval_erode``).  Under
     ``torchrun`` scenes are sharded ``i % world == rank``; only the confusion matrix (and the
     pixel count) is all-reduced."""
     import torch.distributed as dist
@@ -392,11 +402,11 @@ def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[st
             lab = np.load(labels[i]).astype("uint8") if labels is not None else None
             t0 = time.perf_counter()
             acc = sp.accumulate(scene)
-            pred, cm = sp.finalize(acc, lab)
+            pred, cm = sp.finalize(acc, lab, erode=cfg.eval_erode)
             ms = (time.perf_counter() - t0) * 1e3
             H, W = int(pred.shape[0]), int(pred.shape[1])
             rec = {"name": os.path.basename(images[i]), "H": H, "W": W, "windows": sp.windows,
-                   "ms": ms, "tta": tta}
+                   "ms": ms, "tta": tta, "eval_erode": cfg.eval_erode}
             if cm is not None:
                 m = metrics_of(cm)
                 rec.update(pixel_acc=m["pixel_acc"], iou=m["iou"])
@@ -418,5 +428,5 @@ def predict(cfg, checkpoint: str, inputs: str, out_dir: str, device: Optional[st
         total = total.cpu()
     summary: Dict[str, object] = {"scenes": len(images), "pixels": int(total[K * K])}
     if labels is not None:
-        summary.update(metrics_of(total[:K * K].reshape(K, K)))
+        summary.update(metrics_of(total[:K * K].reshape(K, K)), eval_erode=cfg.eval_erode)
     return summary

@@ -33,7 +33,7 @@ import torch.distributed as dist
 from ..config import TrainConfig, median_freq_weights, parse_class_weights
 from ..data import SceneCropDataset, ShardedSampler, SyntheticTiles, TileDataset, join_batches
 from ..models.unet import UNet
-from ..ops import _ext
+from ..ops import _ext, boundary
 from ..ops.adam import FlatAdam
 from ..ops.lamb import FlatLamb
 from ..parallel import (GradBucketReducer, assert_replicas_identical, broadcast_buffers,
@@ -378,6 +378,10 @@ class Trainer:
         skip it): the caller arms the reducer (``_arm``) and passes ``before_backward``."""
         ctx = (torch.autocast("cuda", dtype=torch.bfloat16) if self.autocast
                else contextlib.nullcontext())
+        if self.cfg.train_erode:
+            # the border band of the micro-batch's labels is ignored by the loss: one launch on the
+            # labels at hand, inside a captured step too (no host read)
+            y = boundary.erode_labels(y, self.cfg.model.out_classes, self.cfg.train_erode)
         with ctx:
             loss, correct = self.model.loss_and_correct(x, y, class_weight=self.class_weight,
                                                         dice_weight=self.cfg.dice_weight,
@@ -858,13 +862,18 @@ class Trainer:
 
         ``val_loss`` is always the UNWEIGHTED mean cross-entropy, whatever ``class_weights``
         the training loss uses: that is the figure that stays comparable between runs.  The
-        effect of class weights shows in the per-class IoU (``val_iou``)."""
+        effect of class weights shows in the per-class IoU (``val_iou``).
+
+        ``cfg.eval_erode = r > 0`` scores the "eroded boundaries" sheet: every labelled pixel
+        within r pixels of another class (of the batch's labels, eroded on the device) counts
+        for nothing; the result carries ``eval_erode`` so a figure says which sheet it is."""
         ds = dataset if dataset is not None else self.test_set
         if ds is None or len(ds) == 0:
             return {}
         self.model.eval()
         k = self.cfg.model.out_classes
         bs = batch or self.cfg.batch_per_gpu
+        erode = self.cfg.eval_erode
         acc = torch.zeros(3, dtype=torch.float64, device=self.device)
         cm = torch.zeros(k * k, dtype=torch.float64, device=self.device)
         # the engine's fused evaluation head (cfg.fused_eval): one head pass per batch adds into
@@ -874,6 +883,8 @@ class Trainer:
         idx_all = list(range(len(ds)))[self.rank::self.world]
         for i in range(0, len(idx_all), bs):
             x, y = self._to_device(*ds.get(idx_all[i:i + bs]))
+            if erode:
+                y = boundary.erode_labels(y, k, erode)
             if fused:
                 self.model.evaluate(x, y, out=(acc, cmi))
                 continue
@@ -882,6 +893,16 @@ class Trainer:
             with ctx:
                 logits = self.model(x)
             logits = logits.float()
+            if erode:
+                # the stock sums with the band left out (-100 = cross_entropy's ignore value; a
+                # band pixel equals no prediction and lands in a dropped extra bin)
+                counted = y != -100
+                loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum")
+                pred = logits.argmax(1)
+                acc += torch.stack([loss.double(), (pred == y).sum().double(), counted.sum().double()])
+                idx = torch.where(counted, y * k + pred, torch.full_like(y, k * k))
+                cm += torch.bincount(idx.reshape(-1), minlength=k * k + 1)[:k * k].double()
+                continue
             loss = torch.nn.functional.cross_entropy(logits, y, reduction="sum")
             pred = logits.argmax(1)
             acc += torch.stack([loss.double(), (pred == y).sum().double(),
@@ -902,7 +923,7 @@ class Trainer:
         miou = [v for v, ok in zip(iou, valid) if ok]
         a = acc.tolist()
         return {"val_loss": a[0] / max(a[2], 1), "val_pixel_acc": a[1] / max(a[2], 1),
-                "val_iou": iou, "val_miou": sum(miou) / max(len(miou), 1)}
+                "val_iou": iou, "val_miou": sum(miou) / max(len(miou), 1), "eval_erode": erode}
 
     # ------------------------------------------------------------------ checkpoint
     def save(self, path: Optional[str] = None) -> Optional[str]:
