@@ -97,8 +97,10 @@ std::string last_path() { return g_last_path; }
 //   CONVT_WGRAD_WIDE (default: unset = convt_wgrad_wide_rule): the transposed-conv weight
 //   gradient's 256-column-tile kernel; 0 = never, 1 = wherever its shape constraints hold
 //   (scripts/conv_micro.py --passes twgradbn --ab, tests/test_convt_wgrad_wide_gpu.py)
+//   ELASTIC_LDS (default 1): elastic_gather's first spline stage once per block in LDS; 0 = the
+//   direct tensor product per pixel, kept for scripts/crop_micro.py's A/B (docs/PERF.md)
 namespace {
-const char* const kKnobs[] = {"CROP_LDS_T", "WINDOW_LDS_T", "CONVT_WGRAD_WIDE"};
+const char* const kKnobs[] = {"CROP_LDS_T", "WINDOW_LDS_T", "CONVT_WGRAD_WIDE", "ELASTIC_LDS"};
 bool knob_registered(const std::string& name) {
   for (const char* k : kKnobs)
     if (k[0] != 0 && name == k) return true;
@@ -1808,6 +1810,42 @@ std::vector<at::Tensor> warp_params(const at::Tensor& idx, const at::Tensor& cum
   return {wparams, color};
 }
 
+// virtual sample numbers -> the elastic control lattices int32 [B, grid + 3, grid + 3, 2] of (dy, dx)
+// in Q8 pixels (counter-based: data_math.h)
+at::Tensor elastic_field(const at::Tensor& idx, int64_t seed, int64_t amp, int64_t grid) {
+  checks::elastic_field(idx, amp, grid);
+  CHECK_DEV(idx); CHECK_CONTIG(idx);
+  const int64_t B = idx.numel();
+  c10::DeviceGuard guard(idx.device());
+  at::Tensor ctrl = at::empty({B, grid + 3, grid + 3, 2}, idx.options().dtype(at::kInt));
+  if (B > 0)
+    elastic_field_launch(idx.data_ptr<int64_t>(), (int)B, (uint32_t)(seed & 0xffffffff), (int)amp, (int)grid,
+                         ctrl.data_ptr<int>(), cur_stream());
+  return ctrl;
+}
+
+// warp_gather at coordinates displaced by the cubic B-spline of each sample's control lattice
+// (the recipe: data_math.h; the kernel: deform.hip) -> {x bf16 [B, T, T, cpad], y int64}
+std::vector<at::Tensor> elastic_gather(const at::Tensor& scenes, const at::Tensor& labels,
+                                       const at::Tensor& table, const at::Tensor& wparams,
+                                       const c10::optional<at::Tensor>& color, const at::Tensor& ctrl,
+                                       const at::Tensor& spline, int64_t tile, int64_t cpad) {
+  const int64_t grid = checks::elastic_gather(scenes, labels, table, wparams, color, ctrl, spline, tile, cpad);
+  const float* pc = gather_device_args("elastic_gather", scenes, labels, table, wparams, color, tile);
+  CHECK_DEV(ctrl); CHECK_CONTIG(ctrl); CHECK_DEV(spline); CHECK_CONTIG(spline);
+  const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0);
+  c10::DeviceGuard guard(scenes.device());
+  at::Tensor y = at::empty({B, tile, tile}, scenes.options().dtype(at::kLong));
+  at::Tensor x = at::empty({B, tile, tile, cpad}, scenes.options().dtype(at::kBFloat16));
+  if (B > 0)
+    elastic_gather_launch(scenes.data_ptr<uint8_t>(), labels.data_ptr<uint8_t>(), table.data_ptr<int64_t>(),
+                          (int)n, (long long)labels.size(0), wparams.data_ptr<int64_t>(), pc,
+                          ctrl.data_ptr<int>(), (int)grid, spline.data_ptr<int>(), (int)B, (int)in_ch,
+                          (int)tile, (int)cpad, knob("ELASTIC_LDS", 1) != 0, bptr_mut(x),
+                          y.data_ptr<int64_t>(), cur_stream());
+  return {x, y};
+}
+
 // ------------------------------------------------------------------------ scene prediction
 // test-time augmentation: the symmetry codes of a call (int32 [S], 1 <= S <= 8, distinct values
 // in 0..7; checks::codes) -> S and the codes packed 3 bits each (without codes: S = 1, code 0, no
@@ -2068,6 +2106,9 @@ TORCH_LIBRARY(ddlpc, m) {
         "int tile, int cpad) -> Tensor[]");
   m.def("warp_params(Tensor idx, Tensor cum, Tensor table, Tensor steps, Tensor rot, int seed, int tile, "
         "int mode, float gain_jitter, float bias_jitter) -> Tensor[]");
+  m.def("elastic_field(Tensor idx, int seed, int amp, int grid) -> Tensor");
+  m.def("elastic_gather(Tensor scenes, Tensor labels, Tensor table, Tensor wparams, Tensor? color, "
+        "Tensor ctrl, Tensor spline, int tile, int cpad) -> Tensor[]");
   m.def("window_gather(Tensor scene, Tensor origins, int tile, int cpad, Tensor? codes=None) -> Tensor");
   // (the windows of one call must be pairwise disjoint: acc is updated without atomics)
   m.def("head_predict_accum(Tensor a, Tensor Wh, Tensor bh, Tensor origins, Tensor win, Tensor(a!) acc, "
@@ -2136,6 +2177,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CUDA, m) {
   m.impl("crop_params", &ddlpc::crop_params);
   m.impl("warp_gather", &ddlpc::warp_gather);
   m.impl("warp_params", &ddlpc::warp_params);
+  m.impl("elastic_field", &ddlpc::elastic_field);
+  m.impl("elastic_gather", &ddlpc::elastic_gather);
   m.impl("window_gather", &ddlpc::window_gather);
   m.impl("head_predict_accum", &ddlpc::head_predict_accum);
   m.impl("scene_finalize", &ddlpc::scene_finalize);

@@ -1475,10 +1475,18 @@ std::vector<Tensor> crop_params(const Tensor& idx, const Tensor& cum, const Tens
   return {params, color};
 }
 
-// the rows of warp_gather (arguments checked by the caller); bounded: a row must pass warp_row_valid
+// the elastic stage of gather_rows: the lattices [B, grid + 3, grid + 3, 2] and the loaded spline rows
+struct ElasticArgs {
+  const int* ctrl;
+  int grid;
+  std::vector<SplineRow> rows;
+};
+
+// the rows of warp_gather (arguments checked by the caller); bounded: a row must pass warp_row_valid;
+// el: the coordinate is elastic_coord of the sample's displacement instead of warp_coord
 std::vector<Tensor> gather_rows(const Tensor& scenes, const Tensor& labels, const Tensor& table,
                                 const Tensor& wparams, const optional<Tensor>& color, int64_t tile,
-                                int64_t cpad, bool bounded) {
+                                int64_t cpad, bool bounded, const ElasticArgs* el = nullptr) {
   const int64_t in_ch = scenes.size(1), B = wparams.size(0), n = table.size(0), P = labels.size(0);
   const bool has_color = has(color);
   const Tensor cc = has_color ? color->contiguous() : Tensor();
@@ -1510,7 +1518,12 @@ std::vector<Tensor> gather_rows(const Tensor& scenes, const Tensor& labels, cons
         yp[e] = -100;
         if (valid) {
           const Index2<int> s = d4_forward(code, (int)tile, oy, ox);
-          const Index2<long long> p = warp_coord(cy, cx, A, Bm, (int)tile, s.a, s.b);
+          Index2<long long> p = warp_coord(cy, cx, A, Bm, (int)tile, s.a, s.b);
+          if (el != nullptr) {
+            const int g3 = el->grid + 3;
+            const Index2<int> d = elastic_displace(el->ctrl + b * g3 * g3 * 2, el->grid, el->rows[s.a], el->rows[s.b]);
+            p = elastic_coord(cy, cx, A, Bm, (int)tile, s.a, s.b, d.a, d.b);
+          }
           const int64_t iy = warp_tap(p.a), ix = warp_tap(p.b);
           const float wy = warp_weight(p.a), wx = warp_weight(p.b);
           const int64_t r0 = off + reflect_fast(iy, H) * W, r1 = off + reflect_fast(iy + 1, H) * W;
@@ -1578,6 +1591,31 @@ std::vector<Tensor> warp_params(const Tensor& idx, const Tensor& cum, const Tens
     color_jitter(draw(key, 4), draw(key, 5), (float)gain_jitter, (float)bias_jitter, op + 2 * i);
   }
   return {wparams, color};
+}
+
+Tensor elastic_field(const Tensor& idx, int64_t seed, int64_t amp, int64_t grid) {
+  checks::elastic_field(idx, amp, grid);
+  const Tensor ix = idx.contiguous();
+  const int64_t B = ix.numel(), per = 2 * (grid + 3) * (grid + 3);
+  const int64_t* ip = ix.data_ptr<int64_t>();
+  Tensor ctrl = at::empty({B, grid + 3, grid + 3, 2}, idx.options().dtype(at::kInt));
+  int* cp = ctrl.data_ptr<int>();
+  for (int64_t e = 0; e < B * per; ++e) {
+    const int64_t b = e / per, r = e - b * per;
+    cp[e] = elastic_control(sample_key((uint32_t)(seed & 0xffffffff), (uint64_t)ip[b]), (int)(r >> 1), (int)(r & 1),
+                            (int)amp);
+  }
+  return ctrl;
+}
+
+std::vector<Tensor> elastic_gather(const Tensor& scenes, const Tensor& labels, const Tensor& table,
+                                   const Tensor& wparams, const optional<Tensor>& color, const Tensor& ctrl,
+                                   const Tensor& spline, int64_t tile, int64_t cpad) {
+  const int64_t grid = checks::elastic_gather(scenes, labels, table, wparams, color, ctrl, spline, tile, cpad);
+  const Tensor cc = ctrl.contiguous(), sc = spline.contiguous();
+  ElasticArgs el{cc.data_ptr<int>(), (int)grid, std::vector<SplineRow>((size_t)tile)};
+  for (int64_t i = 0; i < tile; ++i) el.rows[(size_t)i] = spline_row(sc.data_ptr<int>() + 5 * i, (int)grid);
+  return gather_rows(scenes, labels, table, wparams, color, tile, cpad, true, &el);
 }
 
 void head_predict_accum(const Tensor& a, const Tensor& Wh, const Tensor& bh, const Tensor& origins,
@@ -1780,6 +1818,8 @@ TORCH_LIBRARY_IMPL(ddlpc, CPU, m) {
   m.impl("crop_params", &crop_params);
   m.impl("warp_gather", &warp_gather);
   m.impl("warp_params", &warp_params);
+  m.impl("elastic_field", &elastic_field);
+  m.impl("elastic_gather", &elastic_gather);
   m.impl("head_predict_accum", &head_predict_accum);
   m.impl("scene_finalize", &scene_finalize);
   m.impl("label_dist2", &label_dist2);

@@ -79,6 +79,29 @@ inline void warp_gather(T scenes, T labels, T table, T wparams, OptT color, int6
   TORCH_CHECK(scenes.size(1) >= 1 && scenes.size(1) <= cpad, "1 <= in_ch <= cpad");
 }
 
+inline void elastic_field(T idx, int64_t amp, int64_t grid) {
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
+  TORCH_CHECK(grid >= 1 && grid <= 16, "1 <= grid <= 16");
+  TORCH_CHECK(amp >= 0 && amp <= (1 << 20), "0 <= amp <= 2^20");
+  TORCH_CHECK(idx.numel() * 2 * (grid + 3) * (grid + 3) < (1LL << 31), "too many samples");
+}
+
+// warp_gather's arguments, ctrl int32 [B, g + 3, g + 3, 2] (1 <= g <= 16), spline int32 [tile, 5];
+// tile <= 4096 keeps elastic_coord's v2, u2 inside int32 -> g
+inline int64_t elastic_gather(T scenes, T labels, T table, T wparams, OptT color, T ctrl, T spline, int64_t tile,
+                              int64_t cpad) {
+  warp_gather(scenes, labels, table, wparams, color, tile, cpad);
+  TORCH_CHECK(tile <= 4096, "elastic_gather: tile <= 4096");
+  TORCH_CHECK(ctrl.scalar_type() == at::kInt && ctrl.dim() == 4 && ctrl.size(0) == wparams.size(0) &&
+              ctrl.size(1) == ctrl.size(2) && ctrl.size(1) >= 4 && ctrl.size(1) <= 19 && ctrl.size(3) == 2,
+              "ctrl must be int32 [B, g + 3, g + 3, 2], 1 <= g <= 16");
+  TORCH_CHECK(spline.scalar_type() == at::kInt && spline.dim() == 2 && spline.size(0) == tile && spline.size(1) == 5,
+              "spline must be int32 [tile, 5] (cell, w0, w1, w2, w3)");
+  TORCH_CHECK(ctrl.device() == scenes.device() && spline.device() == scenes.device(),
+              "elastic_gather: tensors on different devices");
+  return ctrl.size(1) - 3;
+}
+
 // crop_params and warp_params: virtual sample numbers idx, cumulative counts cum [n + 1], table
 inline void params_args(const char* op, T idx, T cum, T table, int64_t tile, int64_t mode) {
   TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");

@@ -41,6 +41,29 @@
 //     clamp, bf16; label: nearest.  A row that fails scene_row_valid or warp_row_valid reads
 //     nothing (zero image, labels -100).  (A, Bm) = (ONE, 0), cy = (2 y0 + tile - 1) * 32768 is
 //     crop_gather's (y0, x0) crop, bit for bit.
+//   * elastic_field + elastic_gather: a smooth random deformation in front of warp_gather's
+//     coordinate, in the frame (a, b) of d4_forward (so zoom and rotation scale and turn it with
+//     the crop).  Integers only on the device.
+//       spline table  int32 [tile, 5] of (cell, w0..w3) rows, built on the host in float64
+//         (data/scenes.py spline_table): cell = ((2 a + 1) grid) // (2 tile), u = the remainder /
+//         (2 tile), w_i = rint(4096 B_i(u)) of the uniform cubic B-spline basis, the rounding
+//         difference added to the largest weight: sum w = 4096, every w >= 0 (w <= 2731).  One
+//         table serves rows and columns.  It is device data: spline_row loads a row so that these
+//         invariants hold whatever it contains (cell into [0, grid - 1], the weights into a
+//         partition of 4096) — a valid row is unchanged.
+//       control lattice  int32 [grid + 3, grid + 3, 2] per sample, (dy, dx) in Q8 output pixels:
+//         elastic_control = ((s4 * amp) >> 8), s4 = the four bytes of mix(key ^ mix(2 point + axis
+//         + 0x27D4EB2F)) summed - 510 (Irwin-Hall, std sqrt(21845)), point = j (grid + 3) + i, amp =
+//         rint(sigma_px 65536 / sqrt(21845)) from the host, 0 <= amp <= 2^20 (|s4 amp| < 2^29).
+//         A function of (seed, s, grid, amp) only.  The gather clamps every value to +-2^17.
+//       displacement  two rounded separable stages (spline_stage), each inside int32 (|sum| <=
+//         4096 * 2^17 = 2^29): T[j] = (sum_i w_b[i] c[cell_a + j][cell_b + i] + 2048) >> 12, d =
+//         (sum_j w_a[j] T[j] + 2048) >> 12 per axis; |T|, |d| <= 2^17; a constant lattice gives d =
+//         c exactly.
+//       coordinate  elastic_coord: ay = a ONE + 256 dy, bx = b ONE + 256 dx, v2 = 2 ay - (tile - 1)
+//         ONE, u2 likewise (int32 for tile <= 4096: |v2| < 2^29), py = cy + ((Bm u2 + A v2) >> 17),
+//         px = cx + ((A u2 - Bm v2) >> 17): with d = 0 warp_coord bit for bit.  Everything behind
+//         the coordinate is warp_gather's, unchanged.
 #pragma once
 
 #include <stdint.h>
@@ -193,6 +216,72 @@ DDLPC_HDI float u8_unit(uint32_t u8) { return div_rn((float)u8, 255.0f); }
 // clamp(round(v * gain) + bias, 0, 1)
 DDLPC_HDI float color_clamp(float v, float gain, float bias) {
   return fminf(fmaxf(add_rn(mul_rn(v, gain), bias), 0.f), 1.f);
+}
+
+// ---- elastic deformation
+constexpr int kSplineOne = 4096;          // the spline weights' fixed point: sum w = kSplineOne
+constexpr int kCtrlMax = 1 << 17;         // control values are clamped to +- this (Q8: 512 pixels)
+constexpr int kElasticMaxGrid = 16, kElasticMaxTile = 4096, kElasticMaxAmp = 1 << 20;
+
+// c = (s4 * amp) >> 8,  s4 = b0 + b1 + b2 + b3 - 510 of h = mix(key ^ mix(2 point + axis + 0x27D4EB2F))
+DDLPC_HDI int elastic_control(uint32_t key, int point, int axis, int amp) {
+  const uint32_t h = mix32(key ^ mix32((uint32_t)(2 * point + axis) + 0x27D4EB2Fu));
+  const int s4 = (int)((h & 255u) + ((h >> 8) & 255u) + ((h >> 16) & 255u) + (h >> 24)) - 510;
+  return (s4 * amp) >> 8;
+}
+
+DDLPC_HDI int ctrl_clamp(int c) { return c < -kCtrlMax ? -kCtrlMax : c > kCtrlMax ? kCtrlMax : c; }
+
+struct SplineRow {
+  int cell, w[4];
+};
+
+// a row of the spline table as the stages may use it: cell in [0, grid - 1], w >= 0, sum w = 4096
+// (w0, w1, w2 clamped in turn to what is left of 4096, w3 the rest): a valid row unchanged
+DDLPC_HDI SplineRow spline_row(const int* __restrict__ row, int grid) {
+  SplineRow r;
+  r.cell = row[0] < 0 ? 0 : row[0] > grid - 1 ? grid - 1 : row[0];
+  int left = kSplineOne;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int w = row[1 + i] < 0 ? 0 : row[1 + i] > left ? left : row[1 + i];
+    r.w[i] = w;
+    left -= w;
+  }
+  r.w[3] = left;
+  return r;
+}
+
+// (w0 c0 + w1 c1 + w2 c2 + w3 c3 + 2048) >> 12: one rounded stage of the spline
+DDLPC_HDI int spline_stage(const int* w, int c0, int c1, int c2, int c3) {
+  return (w[0] * c0 + w[1] * c1 + w[2] * c2 + w[3] * c3 + 2048) >> 12;
+}
+
+// the displacement (dy, dx) of pixel (a, b) from one sample's lattice [grid + 3, grid + 3, 2]:
+// stage 1 along b on the four lattice rows cell_a + j, stage 2 along a
+DDLPC_HDI Index2<int> elastic_displace(const int* __restrict__ lattice, int grid, const SplineRow& ra,
+                                       const SplineRow& rb) {
+  int T[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int* c = lattice + ((ra.cell + j) * (grid + 3) + rb.cell) * 2;
+#pragma unroll
+    for (int ax = 0; ax < 2; ++ax)
+      T[j][ax] = spline_stage(rb.w, ctrl_clamp(c[ax]), ctrl_clamp(c[2 + ax]), ctrl_clamp(c[4 + ax]),
+                              ctrl_clamp(c[6 + ax]));
+  }
+  return {spline_stage(ra.w, T[0][0], T[1][0], T[2][0], T[3][0]),
+          spline_stage(ra.w, T[0][1], T[1][1], T[2][1], T[3][1])};
+}
+
+// warp_coord of the displaced pixel (a + dy / 256, b + dx / 256), tile <= 4096, |dy|, |dx| <= 2^17:
+// v2, u2 fit int32, the products int64 (|.| <= 2^50).  |py|, |px| < 2^46 + 2^34.  -> (py, px)
+DDLPC_HDI Index2<long long> elastic_coord(long long cy, long long cx, int A, int Bm, int tile, int a, int b,
+                                          int dy, int dx) {
+  const int ay = a * 65536 + dy * 256, bx = b * 65536 + dx * 256;
+  const int v2 = 2 * ay - (tile - 1) * 65536, u2 = 2 * bx - (tile - 1) * 65536;
+  return {cy + (((long long)Bm * u2 + (long long)A * v2) >> 17),
+          cx + (((long long)A * u2 - (long long)Bm * v2) >> 17)};
 }
 
 // top = p00 + (p01 - p00) * wx,  bot = p10 + (p11 - p10) * wx,  val = top + (bot - top) * wy

@@ -519,6 +519,13 @@ void warp_params_launch(const int64_t* idx, int B, const int64_t* cum, const int
 void warp_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
                         long long total_px, const int64_t* wparams, const float* color, int B,
                         int in_ch, int tile, int cpad, bf16_t* x, int64_t* y, hipStream_t st);
+// elastic deformation (deform.hip): ctrl int32 [B, grid + 3, grid + 3, 2], spline int32 [tile, 5]
+void elastic_field_launch(const int64_t* idx, int B, uint32_t seed, int amp, int grid, int* ctrl,
+                          hipStream_t st);
+void elastic_gather_launch(const uint8_t* src, const uint8_t* lab, const int64_t* table, int n,
+                           long long total_px, const int64_t* wparams, const float* color,
+                           const int* ctrl, int grid, const int* spline, int B, int in_ch, int tile,
+                           int cpad, bool two_stage, bf16_t* x, int64_t* y, hipStream_t st);
 
 void bn_running_apply_launch(float* rm, float* rv, const float* slots, int K, int C, long long stride,
                              float momentum, int64_t* nbt, hipStream_t st);

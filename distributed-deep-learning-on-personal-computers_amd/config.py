@@ -118,6 +118,10 @@ class TrainConfig:
     zoom_min: float = 1.0                # per-sample zoom, log-uniform in [zoom_min, zoom_max]:
     zoom_max: float = 1.0                # > 1 magnifies; 0.25 <= zoom_min <= zoom_max <= 4
     rotate_deg: float = 0.0              # per-sample angle, uniform in +- this many degrees (<= 180)
+    # elastic deformation of the crops (elastic_field / elastic_gather: a cubic B-spline over a
+    # per-sample lattice of random displacements); sigma 0 keeps the crop / warp kernels
+    elastic_sigma: float = 0.0           # standard deviation of a control point, pixels (<= 32)
+    elastic_grid: int = 3                # control cells per tile side, 1..16
     # CrossEntropyLoss(weight=...) of the training loss (validation stays unweighted):
     # None | "w0,w1,..." (out_classes non-negative numbers, not all zero; a YAML list too)
     # | "median_freq" (from the training split's label histogram; real data only)
@@ -284,6 +288,10 @@ class TrainConfig:
             raise ValueError("zoom_min and zoom_max must satisfy 0.25 <= zoom_min <= zoom_max <= 4")
         if not 0.0 <= self.rotate_deg <= 180.0:
             raise ValueError("rotate_deg must be in [0, 180]")
+        if not 0.0 <= self.elastic_sigma <= 32.0 or not 1 <= self.elastic_grid <= 16:
+            raise ValueError("elastic_sigma must be in [0, 32] and elastic_grid in 1..16")
+        if self.elastic_sigma > 0.0 and self.tile > 4096:
+            raise ValueError("elastic_sigma needs tile <= 4096")
         if not self.dice_weight >= 0 or not self.dice_smooth > 0:
             raise ValueError("dice_weight must be >= 0 and dice_smooth > 0")
         if self.dice_weight > 0 and self.bn_window > 1:
@@ -323,7 +331,8 @@ class TrainConfig:
     def augmented(self) -> bool:
         """Batches go through the augmenting crop (or warp) kernels."""
         return self.augment != "none" or self.gain_jitter != 0.0 or self.bias_jitter != 0.0 or \
-            self.zoom_min != 1.0 or self.zoom_max != 1.0 or self.rotate_deg != 0.0
+            self.zoom_min != 1.0 or self.zoom_max != 1.0 or self.rotate_deg != 0.0 or \
+            self.elastic_sigma != 0.0
 
     # ---- (de)serialisation ---------------------------------------------------------
     def to_dict(self) -> Dict[str, Any]:

@@ -25,10 +25,17 @@ differing sizes; here they are trained on as they are:
   built here (``zoom_steps``, ``rotation_table``) and ``warp_gather`` reads bilinear image
   taps and nearest labels at 16.16 fixed-point affine coordinates, in the same single pass.
   With zoom 1 and rotation 0 (the defaults) the crop kernels run, unchanged.
+* elastic deformation (``elastic_sigma`` / ``elastic_grid``): the U-Net paper's smooth random
+  displacement field.  ``elastic_field`` draws a ``(grid + 3)^2`` lattice of control
+  displacements per sample (standard deviation ``elastic_sigma`` pixels), ``elastic_gather`` is
+  ``warp_gather`` at pixels moved by the lattice's cubic B-spline (integer weights from
+  ``spline_table``), still one gather kernel per batch.  With sigma 0 (the default) nothing
+  changes.
 
-``crop_params_reference`` / ``crop_gather_reference`` and ``warp_params_reference`` /
-``warp_gather_reference`` are the numpy twins of the kernels (the same bits); they serve
-``layout="nchw"`` and are the oracle of the tests.
+``crop_params_reference`` / ``crop_gather_reference``, ``warp_params_reference`` /
+``warp_gather_reference`` and ``elastic_field_reference`` / ``elastic_gather_reference`` are the
+numpy twins of the kernels (the same bits); they serve ``layout="nchw"`` and are the oracle of
+the tests.
 """
 from __future__ import annotations
 
@@ -47,6 +54,9 @@ ONE = 65536                              # 1.0 in the warp kernels' 16.16 fixed 
 WARP_TABLE = 256                         # entries of the zoom and of the rotation table
 WARP_MAX_COEF = 2 ** 20                  # warp_gather: |A|, |Bm| <= this (a step of 16 pixels)
 WARP_MAX_CENTRE = 2 ** 46                # ... and |cy|, |cx| < this
+SPLINE_ONE = 4096                        # elastic_gather: the spline weights of a pixel sum to this
+ELASTIC_MAX_CTRL = 2 ** 17               # ... control displacements are clamped to +- this (Q8 pixels)
+ELASTIC_MAX_GRID, ELASTIC_MAX_TILE, ELASTIC_MAX_SIGMA = 16, 4096, 32.0
 
 
 # ---------------------------------------------------------------------- the numpy twins
@@ -204,11 +214,12 @@ def warp_params_reference(idx, cum, table, steps, rot, seed: int, tile: int, mod
     return torch.from_numpy(np.stack([sc, cy, cx, code, A, Bm], 1).astype(np.int64)), color
 
 
-def warp_gather_reference(scenes, labels, table, wparams, color, tile: int
+def warp_gather_reference(scenes, labels, table, wparams, color, tile: int, field=None
                           ) -> Tuple[torch.Tensor, torch.Tensor]:
     """numpy twin of the ``warp_gather`` kernels: float32 NCHW (before the bf16 rounding) and
     int64 labels.  Bilinear image taps and nearest labels at the affine coordinates of
-    csrc/data.hip; every float32 operation rounds on its own."""
+    csrc/data.hip; every float32 operation rounds on its own.  ``field`` (int64 [B, tile, tile, 2],
+    the Q8 displacement of frame pixel (a, b): ``elastic_gather_reference``) moves the pixel first."""
     scenes = torch.as_tensor(scenes).cpu().numpy()
     labels = torch.as_tensor(labels).cpu().numpy()
     table = torch.as_tensor(table).cpu().numpy().reshape(-1, 3)
@@ -231,9 +242,15 @@ def warp_gather_reference(scenes, labels, table, wparams, color, tile: int
             a = tile - 1 - a
         if code & 1:
             c = tile - 1 - c
-        v2, u2 = 2 * a - (tile - 1), 2 * c - (tile - 1)
-        py = cy + ((Bm * u2 + A * v2) >> 1)
-        px = cx + ((A * u2 - Bm * v2) >> 1)
+        if field is None:
+            v2, u2 = 2 * a - (tile - 1), 2 * c - (tile - 1)
+            py = cy + ((Bm * u2 + A * v2) >> 1)
+            px = cx + ((A * u2 - Bm * v2) >> 1)
+        else:
+            v2 = 2 * (a * ONE + (field[b, a, c, 0] << 8)) - (tile - 1) * ONE
+            u2 = 2 * (c * ONE + (field[b, a, c, 1] << 8)) - (tile - 1) * ONE
+            py = cy + ((Bm * u2 + A * v2) >> 17)
+            px = cx + ((A * u2 - Bm * v2) >> 17)
         iy, ix = py >> 16, px >> 16
         wy = (py & 65535).astype(_F) * _F(2.0 ** -16)
         wx = (px & 65535).astype(_F) * _F(2.0 ** -16)
@@ -251,6 +268,77 @@ def warp_gather_reference(scenes, labels, table, wparams, color, tile: int
         y[b] = labels[off:off + H * W].reshape(H, W)[_reflect((py + 32768) >> 16, H),
                                                      _reflect((px + 32768) >> 16, W)]
     return torch.from_numpy(x).permute(0, 3, 1, 2).contiguous(), torch.from_numpy(y)
+
+
+# ---------------------------------------------------------------------- elastic deformation
+# A smooth random displacement of the crop's pixels (the recipe: csrc/data_math.h): a cubic
+# B-spline over a per-sample lattice of random control displacements.  The spline reaches the
+# kernels as an integer table built here in float64; the lattice is a counter-based hash.
+def spline_table(tile: int, grid: int) -> np.ndarray:
+    """int32 [tile, 5] of ``(cell, w0, w1, w2, w3)``: pixel centre ``a + 1/2`` lies in cell
+    ``((2a + 1) grid) // (2 tile)`` at fraction ``u``; ``w_i = rint(4096 B_i(u))`` of the uniform
+    cubic B-spline basis, the rounding difference added to the largest weight (lowest index on a
+    tie): every row sums to 4096 and has no negative weight."""
+    if tile < 1 or not 1 <= grid <= ELASTIC_MAX_GRID:
+        raise ValueError(f"spline_table needs tile >= 1 and 1 <= grid <= {ELASTIC_MAX_GRID}")
+    num = (2 * np.arange(tile, dtype=np.int64) + 1) * grid
+    cell = num // (2 * tile)
+    u = (num - 2 * tile * cell).astype(np.float64) / (2 * tile)
+    basis = np.stack([(1 - u) ** 3, 3 * u ** 3 - 6 * u ** 2 + 4, -3 * u ** 3 + 3 * u ** 2 + 3 * u + 1, u ** 3], 1) / 6
+    w = np.rint(SPLINE_ONE * basis).astype(np.int64)
+    w[np.arange(tile), np.argmax(w, 1)] += SPLINE_ONE - w.sum(1)
+    return np.concatenate([cell[:, None], w], 1).astype(np.int32)
+
+
+def elastic_amp(sigma: float) -> int:
+    """The lattice's integer amplitude for control points of ``sigma`` pixels standard deviation:
+    ``rint(sigma * 65536 / sqrt(21845))`` (21845 = the variance of a sum of four bytes)."""
+    if not 0.0 <= sigma <= ELASTIC_MAX_SIGMA:
+        raise ValueError(f"elastic sigma must be in [0, {ELASTIC_MAX_SIGMA}] pixels")
+    return int(np.rint(np.float64(sigma) * 65536.0 / np.sqrt(21845.0)))
+
+
+def elastic_field_reference(idx, seed: int, amp: int, grid: int) -> torch.Tensor:
+    """numpy twin of the ``elastic_field`` kernels: int32 [B, grid + 3, grid + 3, 2] control
+    displacements ``(dy, dx)`` in Q8 pixels, a function of ``(seed, sample number, grid, amp)``."""
+    s = np.asarray(torch.as_tensor(idx, dtype=torch.int64).reshape(-1).cpu().numpy()).astype(np.uint64)
+    skey = _mix32(np.array([(seed & 0xFFFFFFFF) ^ 0xC2B2AE35], dtype=np.uint64))
+    hi = _mix32(((s >> np.uint64(32)) + np.uint64(0x85EBCA6B)) & _M32)
+    key = _mix32(_mix32(skey ^ (s & _M32)) ^ hi)
+    counter = np.arange(2 * (grid + 3) ** 2, dtype=np.uint64)        # 2 point + axis
+    h = _mix32(key[:, None] ^ _mix32((counter + np.uint64(0x27D4EB2F)) & _M32)[None])
+    s4 = sum(((h >> np.uint64(k)) & np.uint64(255)).astype(np.int64) for k in (0, 8, 16, 24)) - 510
+    return torch.from_numpy(((s4 * int(amp)) >> 8).astype(np.int32).reshape(-1, grid + 3, grid + 3, 2))
+
+
+def elastic_displacement(ctrl, spline) -> np.ndarray:
+    """int64 [B, tile, tile, 2]: the Q8 displacement ``(dy, dx)`` of every frame pixel (a, b) —
+    control values clamped to +-2^17, table rows loaded as ``spline_row`` of csrc/data_math.h
+    does (the identity on a ``spline_table``), then the two rounded stages: along b, along a."""
+    c = np.clip(torch.as_tensor(ctrl).cpu().numpy().astype(np.int64), -ELASTIC_MAX_CTRL, ELASTIC_MAX_CTRL)
+    t = torch.as_tensor(spline).cpu().numpy().astype(np.int64)
+    g3 = c.shape[1]
+    cell, left, w = np.clip(t[:, 0], 0, g3 - 4), np.full(len(t), SPLINE_ONE), []
+    for i in range(3):
+        w.append(np.clip(t[:, 1 + i], 0, left))
+        left = left - w[-1]
+    w.append(left)
+    j = np.arange(4)
+    cols = c[:, :, (cell[:, None] + j)]                              # [B, g3, tile, 4, 2]
+    stage1 = (sum(w[i][None, None, :, None] * cols[:, :, :, i] for i in range(4)) + 2048) >> 12
+    rows = stage1[:, (cell[:, None] + j)]                            # [B, tile, 4, tile, 2]
+    return (sum(w[i][None, :, None, None] * rows[:, :, i] for i in range(4)) + 2048) >> 12
+
+
+def elastic_gather_reference(scenes, labels, table, wparams, color, ctrl, spline, tile: int
+                             ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """numpy twin of the ``elastic_gather`` kernels: ``warp_gather_reference`` at the coordinates
+    of the displaced pixels."""
+    spline = torch.as_tensor(spline)
+    if tuple(spline.shape) != (tile, 5) or tile > ELASTIC_MAX_TILE:
+        raise ValueError(f"spline must be [tile, 5] and tile <= {ELASTIC_MAX_TILE}")
+    return warp_gather_reference(scenes, labels, table, wparams, color, tile,
+                                 field=elastic_displacement(ctrl, spline))
 
 
 # ---------------------------------------------------------------------- directory loader
@@ -315,7 +403,8 @@ class SceneCropDataset:
     def __init__(self, scenes: Sequence[Scene], tile: int, crops_per_epoch: int = 0,
                  augment: str = "none", gain_jitter: float = 0.0, bias_jitter: float = 0.0,
                  seed: int = 0, layout: str = "nchw", params=None, zoom_min: float = 1.0,
-                 zoom_max: float = 1.0, rotate_deg: float = 0.0):
+                 zoom_max: float = 1.0, rotate_deg: float = 0.0, elastic_sigma: float = 0.0,
+                 elastic_grid: int = 3):
         if augment not in AUGMENT_MODES:
             raise ValueError(f"augment={augment!r} not in {AUGMENT_MODES}")
         if layout not in ("nchw", "engine"):
@@ -344,10 +433,18 @@ class SceneCropDataset:
         self.params = None if params is None else \
             torch.as_tensor(params, dtype=torch.int32).reshape(-1, 4).contiguous()
         # random zoom / rotation: the integer tables of warp_params (None = the crop kernels)
-        self.steps = self.rot = None
-        if self.warped:
+        # elastic deformation: the spline table of elastic_gather (None = no deformation); its rows
+        # come from warp_params, with the identity tables when there is no zoom or rotation
+        self.elastic_sigma, self.elastic_grid = float(elastic_sigma), int(elastic_grid)
+        self.elastic_amp = elastic_amp(self.elastic_sigma)
+        self.steps = self.rot = self.spline = None
+        if self.warped or self.elastic:
             self.steps = torch.from_numpy(zoom_steps(self.zoom_min, self.zoom_max))
             self.rot = torch.from_numpy(rotation_table(self.rotate_deg))
+        if self.elastic:
+            if self.tile > ELASTIC_MAX_TILE:
+                raise ValueError(f"elastic deformation needs tile <= {ELASTIC_MAX_TILE}")
+            self.spline = torch.from_numpy(spline_table(self.tile, self.elastic_grid))
         t2 = self.tile * self.tile
         self.length = len(self.params) if self.params is not None else \
             int(crops_per_epoch) if crops_per_epoch > 0 else -(-off // t2)
@@ -396,7 +493,7 @@ class SceneCropDataset:
                 raise MemoryError(f"scene set of {nbytes} bytes exceeds the HBM budget of "
                                   f"{budget_bytes} bytes; scene sets are served from HBM only "
                                   f"(raise data_hbm_gb or train on fewer scenes)")
-        for name in ("pixels", "labels", "table", "cum", "params", "steps", "rot"):
+        for name in ("pixels", "labels", "table", "cum", "params", "steps", "rot", "spline"):
             t = getattr(self, name)
             if t is not None:
                 setattr(self, name, t.to(device))
@@ -413,6 +510,12 @@ class SceneCropDataset:
         (an explicit ``params`` list, the evaluation grid, stays un-warped)."""
         return self.params is None and (self.zoom_min != 1.0 or self.zoom_max != 1.0 or
                                         self.rotate_deg != 0.0)
+
+    @property
+    def elastic(self) -> bool:
+        """Random crops are deformed: batches go through ``warp_params`` / ``elastic_field`` /
+        ``elastic_gather`` (the evaluation grid stays un-deformed)."""
+        return self.params is None and self.elastic_sigma > 0.0
 
     def __len__(self):
         return self.length
@@ -435,10 +538,10 @@ class SceneCropDataset:
             return self.params.index_select(0, device_indices(idx, self.device)), None
         s = self.sample_numbers(idx)
         jitter = (self.seed, self.tile, self.mode, self.gain_jitter, self.bias_jitter)
-        if self.warped and self.layout == "engine":
+        if (self.warped or self.elastic) and self.layout == "engine":
             from ..ops import _ext
             p, c = _ext.ops().warp_params(s, self.cum, self.table, self.steps, self.rot, *jitter)
-        elif self.warped:
+        elif self.warped or self.elastic:
             p, c = warp_params_reference(s, self.cum, self.table, self.steps, self.rot, *jitter)
         elif self.layout == "engine":
             from ..ops import _ext
@@ -451,6 +554,15 @@ class SceneCropDataset:
 
     def get(self, idx) -> Tuple[torch.Tensor, torch.Tensor]:
         p, c = self.crop_rows(idx)
+        if self.elastic:
+            field = (self.sample_numbers(idx), self.seed, self.elastic_amp, self.elastic_grid)
+            if self.layout == "engine":
+                from ..ops import _ext
+                xp, y = _ext.ops().elastic_gather(self.pixels, self.labels, self.table, p, c,
+                                                  _ext.ops().elastic_field(*field), self.spline, self.tile, 8)
+                return engine_input(xp, self.in_channels), y
+            return elastic_gather_reference(self.pixels, self.labels, self.table, p, c,
+                                            elastic_field_reference(*field), self.spline, self.tile)
         if self.layout == "engine":
             from ..ops import _ext
             gather = _ext.ops().warp_gather if self.warped else _ext.ops().crop_gather

@@ -331,7 +331,8 @@ class Trainer:
             # un-augmented through crop_gather
             crop = dict(crops_per_epoch=c.crops_per_epoch, augment=c.augment, seed=c.seed,
                         gain_jitter=c.gain_jitter, bias_jitter=c.bias_jitter, layout=layout,
-                        zoom_min=c.zoom_min, zoom_max=c.zoom_max, rotate_deg=c.rotate_deg)
+                        zoom_min=c.zoom_min, zoom_max=c.zoom_max, rotate_deg=c.rotate_deg,
+                        elastic_sigma=c.elastic_sigma, elastic_grid=c.elastic_grid)
             if c.data == "scene_dir":
                 tr, te = SceneCropDataset.from_dir(c.data_dir, c.tile, c.test_holdout, **crop)
             else:

@@ -13,8 +13,15 @@ timed at the same batch in the same rounds: ``warp_unit`` with the identity matr
 ``crop_params`` drew (it must write ``crop_gather``'s bits: the cost of the resampling
 arithmetic alone), ``warp_z0.5-2_r30`` on rows ``warp_params`` draws from the tables of
 ``--zoom-min 0.5 --zoom-max 2 --rotate-deg 30``, and ``warp_z0.5_r45`` with every row at zoom
-0.5 and 45 degrees (the widest source footprint of that range).  Prints one JSON line per
-entry, a markdown table, and the ``warp_gather / crop_gather`` ratios against ``coded4_lds``."""
+0.5 and 45 degrees (the widest source footprint of that range).
+
+``elastic_gather`` (``elastic_g3_s10``: a 3 x 3-cell lattice of sigma 10 pixels from
+``elastic_field``) is timed on the ``warp_unit`` rows and on the ``warp_z0.5-2_r30`` rows, on both
+forms of the spline: ``lds`` (knob ELASTIC_LDS = 1, the shipped kernel: the first stage once per
+block in LDS) and ``direct`` (ELASTIC_LDS = 0: the 16-term tensor product per pixel).
+
+Prints one JSON line per entry, a markdown table, the ``warp_gather / crop_gather`` ratios
+against ``coded4_lds`` and the ``elastic_gather / warp_gather`` ratios on the same rows."""
 import argparse
 import json
 import os
@@ -48,7 +55,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("crop_micro.py measures on the GPU; none found")
-    from ddlpc.data.scenes import ONE, crop_cum, rotation_table, zoom_steps
+    from ddlpc.data.scenes import ONE, crop_cum, elastic_amp, rotation_table, spline_table, zoom_steps
     from ddlpc.ops import _ext
     F = _ext.ops()
     dev = "cuda"
@@ -75,7 +82,7 @@ def main():
         if code != "d4":
             p[:, 3] = code
         for path, knob in (("lds", 1), ("direct", 0)):
-            entries[f"code{code}_{path}"] = (knob, lambda p=p: F.crop_gather(pixels, labels, table, p, color, T, 8))
+            entries[f"code{code}_{path}"] = (("CROP_LDS_T", knob), lambda p=p: F.crop_gather(pixels, labels, table, p, color, T, 8))
     # warp_gather: the identity on crop_params' rows, rows drawn from the zoom / rotation
     # tables, and the widest footprint (zoom 0.5 at 45 degrees) for every row
     pl = params.long()
@@ -90,12 +97,21 @@ def main():
     warps = {"warp_unit": unit, "warp_z0.5-2_r30": drawn, "warp_z0.5_r45": wide}
     for name, w in warps.items():
         entries[name] = (None, lambda w=w: F.warp_gather(pixels, labels, table, w, color, T, 8))
+    # elastic_gather on the unit and on the drawn rows, both forms of the spline
+    ctrl = F.elastic_field(idx, 0, elastic_amp(10.0), 3)
+    spline = torch.from_numpy(spline_table(T, 3)).to(dev)
+    elastics = {}
+    for rows in ("warp_unit", "warp_z0.5-2_r30"):
+        for path, knob in (("lds", 1), ("direct", 0)):
+            elastics[f"elastic_g3_s10@{rows}_{path}"] = rows
+            entries[f"elastic_g3_s10@{rows}_{path}"] = (("ELASTIC_LDS", knob), lambda w=warps[rows]: F.elastic_gather(
+                pixels, labels, table, w, color, ctrl, spline, T, 8))
     times = {k: [] for k in entries}
 
     def run(name, iters):
         knob, fn = entries[name]
         if knob is not None:
-            F.set_knob("CROP_LDS_T", knob)
+            F.set_knob(*knob)
         return timed(fn, iters)
 
     for name in entries:
@@ -104,7 +120,7 @@ def main():
         outs = []
         for path in ("lds", "direct"):
             knob, fn = entries[f"code{code}_{path}"]
-            F.set_knob("CROP_LDS_T", knob)
+            F.set_knob(*knob)
             outs.append(fn())
         if not (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])):
             raise SystemExit(f"code {code}: the lds and the direct path differ")
@@ -112,11 +128,24 @@ def main():
     outs = [entries["coded4_lds"][1](), entries["warp_unit"][1]()]
     if not (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])):
         raise SystemExit("warp_gather with the identity matrix differs from crop_gather")
-    del outs
+    for rows in ("warp_unit", "warp_z0.5-2_r30"):        # the two spline forms write the same bits,
+        outs = []                                        # and a zero lattice warp_gather's
+        for path in ("lds", "direct"):
+            knob, fn = entries[f"elastic_g3_s10@{rows}_{path}"]
+            F.set_knob(*knob)
+            outs.append(fn())
+            outs.append(F.elastic_gather(pixels, labels, table, warps[rows], color, torch.zeros_like(ctrl), spline, T, 8))
+        want = entries[rows][1]()
+        if not (torch.equal(outs[0][0], outs[2][0]) and torch.equal(outs[0][1], outs[2][1])):
+            raise SystemExit(f"elastic_gather on {rows}: the lds and the direct form differ")
+        if not all(torch.equal(o[0], want[0]) and torch.equal(o[1], want[1]) for o in (outs[1], outs[3])):
+            raise SystemExit(f"elastic_gather with a zero lattice differs from warp_gather on {rows}")
+    del outs, want
     for _ in range(a.rounds):
         for name in entries:
             times[name].append(run(name, a.iters))
-    F.set_knob("CROP_LDS_T", -(2 ** 63))                 # clear the override
+    F.set_knob("CROP_LDS_T", -(2 ** 63))                 # clear the overrides
+    F.set_knob("ELASTIC_LDS", -(2 ** 63))
     out_bytes = B * T * T * (16 + 8)
     res = {}
     for name, ts in times.items():
@@ -134,6 +163,8 @@ def main():
     for name in warps:
         print(json.dumps({"ratio": f"{name} / coded4_lds", "value": round(res[name] / res["coded4_lds"], 3)}),
               flush=True)
+    for name, rows in elastics.items():
+        print(json.dumps({"ratio": f"{name} / {rows}", "value": round(res[name] / res[rows], 3)}), flush=True)
 
 
 if __name__ == "__main__":

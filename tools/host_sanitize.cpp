@@ -11,7 +11,8 @@
 //   bn_bwd_reduce_blocks, reduce_rows_chunks, reduce_rows_scatter_tmp, head_supported
 // and the host side of csrc/data_math.h, the input pipeline's recipe (the text the kernels and
 // the CPU twins both run): mirror index, D4 maps, scene choice, and the warp's fixed-point
-// coordinates at the extremes its validity predicate admits (no signed overflow: UBSan)
+// coordinates at the extremes its validity predicate admits (no signed overflow: UBSan), the
+// elastic stage (control draw, spline_row on wild rows, both stages, elastic_coord) at its own
 // and of csrc/bn_math.h, the BatchNorm / gradient-tail recipe: the slab permutation is a
 // bijection, stats4 at its edge inputs, the three summation orders at the regime borders
 // and of csrc/lamb_math.h, the LAMB step's recipe: the scalar table over schedules and steps, the
@@ -463,6 +464,65 @@ static void sweep_data_math() {
                 check_big_reflect(warp_tap(q) + 1);
               }
             }
+  // the elastic stage at its admitted extremes (tile <= 4096, |A|, |Bm| = 2^20, |c| = 2^17; UBSan
+  // watches every int32 / int64 intermediate): a control value is inside +-2^17 Q8 for every draw
+  for (int amp : {0, 1, kElasticMaxAmp})
+    for (uint32_t key : {0u, 1u, 0x9E3779B9u, 0xffffffffu})
+      for (int point = 0; point < 19 * 19; ++point)
+        for (int axis = 0; axis < 2; ++axis) {
+          const long long c = elastic_control(key, point, axis, amp);
+          EXPECT(c >= -510LL * amp / 256 - 1 && c <= 510LL * amp / 256, "control %lld at amp %d", c, amp);
+        }
+  // spline_row: any row becomes a partition of 4096 over a cell inside the lattice; a valid one is kept
+  const int wild[][5] = {{0, 683, 2730, 683, 0}, {2, 0, 683, 2730, 683}, {-5, INT_MIN, INT_MAX, -1, 7},
+                         {99, INT_MAX, INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, 4096, 1, 1, 1}, {INT_MAX, 0, 0, 0, 0}};
+  for (auto& row : wild)
+    for (int grid : {1, 3, kElasticMaxGrid}) {
+      const SplineRow r = spline_row(row, grid);
+      EXPECT(r.cell >= 0 && r.cell <= grid - 1 && r.w[0] >= 0 && r.w[1] >= 0 && r.w[2] >= 0 && r.w[3] >= 0 &&
+             r.w[0] + r.w[1] + r.w[2] + r.w[3] == kSplineOne, "spline_row cell %d", r.cell);
+      if (&row == &wild[0] || (&row == &wild[1] && grid >= 3))
+        EXPECT(r.cell == row[0] && r.w[0] == row[1] && r.w[1] == row[2] && r.w[2] == row[3] && r.w[3] == row[4], "valid row kept");
+    }
+  // the two stages on lattices of +-2^17, INT_MIN / INT_MAX (clamped) and alternating signs: |T|, |d| <= 2^17,
+  // a constant lattice gives d = c; then the coordinate at the corners of the largest tile
+  for (int grid : {1, kElasticMaxGrid}) {
+    const int g3 = grid + 3;
+    std::vector<int> lat((size_t)(g3 * g3 * 2));
+    for (int fill = 0; fill < 5; ++fill) {
+      for (int i = 0; i < g3 * g3 * 2; ++i)
+        lat[(size_t)i] = fill == 0 ? kCtrlMax : fill == 1 ? -kCtrlMax : fill == 2 ? (i % 3 ? INT_MAX : INT_MIN)
+                       : fill == 3 ? ((i / 2) % 2 ? kCtrlMax : -kCtrlMax) : 12345 - 777 * (i % 2);
+      for (auto& ra : wild)
+        for (auto& rb : wild) {
+          const Index2<int> d = elastic_displace(lat.data(), grid, spline_row(ra, grid), spline_row(rb, grid));
+          EXPECT(d.a >= -kCtrlMax && d.a <= kCtrlMax && d.b >= -kCtrlMax && d.b <= kCtrlMax, "displacement (%d, %d)", d.a, d.b);
+          if (fill == 0) EXPECT(d.a == kCtrlMax && d.b == kCtrlMax, "constant lattice, +2^17");
+          if (fill == 1) EXPECT(d.a == -kCtrlMax && d.b == -kCtrlMax, "constant lattice, -2^17");
+          if (fill == 4) EXPECT(d.a == 12345 && d.b == 12345 - 777, "constant lattice (%d, %d)", d.a, d.b);
+        }
+    }
+  }
+  for (int et : {1, 40, kElasticMaxTile})
+    for (long long cy : {kCentre - 1, 1 - kCentre})
+      for (int A : {(int)kCoef, -(int)kCoef})
+        for (int Bm : {(int)kCoef, -(int)kCoef})
+          for (int a : {0, et - 1})
+            for (int b : {0, et - 1})
+              for (int dy : {-kCtrlMax, 0, kCtrlMax})
+                for (int dx : {-kCtrlMax, 0, kCtrlMax}) {
+                  const Index2<long long> p = elastic_coord(cy, -cy, A, Bm, et, a, b, dy, dx);
+                  if (dy == 0 && dx == 0) {
+                    const Index2<long long> w = warp_coord(cy, -cy, A, Bm, et, a, b);
+                    EXPECT(p.a == w.a && p.b == w.b, "elastic_coord without a displacement is warp_coord");
+                  }
+                  for (long long q : {p.a, p.b}) {
+                    EXPECT(q > -(kCentre + (1LL << 34)) && q < kCentre + (1LL << 34), "elastic coordinate %lld", q);
+                    EXPECT((q >> 16) >= INT_MIN && (q >> 16) + 1 <= INT_MAX && warp_nearest(q) == ((q + 32768) >> 16), "tap of %lld", q);
+                    check_big_reflect(warp_tap(q));
+                    check_big_reflect(warp_tap(q) + 1);
+                  }
+                }
 }
 
 // ------------------------------------------------------------------ the plan table
